@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- descriptors/s (SHOT + FPFH) of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Run directly with N > 1 (no WORLD_SIZE in the environment) it starts N child processes itself, one per GPU, BEFORE
 touching the GPU; under a launcher (torchrun: RANK / LOCAL_RANK / WORLD_SIZE set) it is one of the ranks.  The ranks'
@@ -18,7 +18,13 @@ HBM -- K1 grid build, K2 radius search, K6 SPFH (+ the SHOT frame moments), K7 F
 eigen-solves, K5 SHOT (rows x 352 float64 out); outputs stay in HBM.  value = 2 x (N x 1M) descriptors / step time
 (max over ranks).  Same definition at every N, so the driver's scaling efficiency compares like with like.
 
-After the timed region the SAME process measures the rest of the path north_star names and reports it under extra keys:
+A plain run sets up, warms up, times the K steps and prints its line: nothing else runs (at N = 1 not even the RCCL
+communicator is built -- the step has no collective there).  --dump-outputs DIR then writes the rows the last step left in HBM
+for a fixed, seeded sample of the cloud's points (dump_outputs).
+
+With --full, after the timed region the SAME process measures the rest of the path north_star names and reports it under
+extra keys (and the timed steps carry the per-kernel HIP events of the roofline):
+  * `sustained`       -- the same step for >= 2 s; if it disagrees with the K steps by more than 2 % it is what `value` reports;
   * `roofline_all`    -- every kernel of the step: algorithmic bytes, average launch time, fraction of the 8.0 TB/s spec
     peak and of the 6.29 TB/s measured-copy peak; for K5 also the float64 issue ceiling its SQ counters give;
   * `normals`         -- (N = 1) compute_normals(radius) on the same cloud: K2 + K3, resident and host to host;
@@ -699,6 +705,45 @@ def fold_checksums(parts: list) -> dict:
     return {k: format(sum(p[k] for p in parts) % 2**64, "016x") for k in parts[0]}
 
 
+DUMP_POINTS = 8192  # 8192 x (125 + 352) float64 = 31 MB: the sample stays under 64 MB however the descriptors are chosen
+
+
+def dump_outputs(job, n_total: int, ctl, lead: bool, out_dir: str) -> None:
+    """--dump-outputs: what the timed steps left in HBM, as a caller of the descriptor path receives it -- float64 rows in the
+    cloud's original point order -- for a fixed sample of DUMP_POINTS points (seed 11, ascending point index), so that two
+    builds can be compared row for row: <out_dir>/fpfh.npy (sample x 125) and <out_dir>/shot.npy (sample x 352).  Every rank
+    gathers the sampled points of its own block and rank 0 writes them all (an emulated rank writes its own)."""
+    eng = job.engine
+    want = np.sort(np.random.default_rng(11).choice(n_total, min(DUMP_POINTS, n_total), replace=False))
+    orig = job.block_original_indices()
+    rows = np.flatnonzero(np.isin(orig, want))
+    rows = rows[np.argsort(orig[rows])]
+    mine = {"point": orig[rows]}
+    for name, arr in (("fpfh", job.fpfh_out), ("shot", job.shot_out)):
+        if arr is None:
+            continue
+        if rows.size == 0:
+            mine[name] = np.empty((0, arr.shape[1]))
+            continue
+        sel = eng.empty((rows.size,), np.int64).from_host(rows)
+        dst = eng.empty((rows.size, arr.shape[1]))
+        try:
+            eng.rows_gather_device(arr, sel, dst)
+            eng.sync()
+            mine[name] = dst.to_host()
+        finally:
+            sel.free()
+            dst.free()
+    parts = [mine] if ctl is None else ctl.allgather(mine)
+    if not lead:
+        return
+    order = np.argsort(np.concatenate([p["point"] for p in parts]))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in ("fpfh", "shot"):
+        if name in mine:
+            np.save(os.path.join(out_dir, f"{name}.npy"), np.concatenate([p[name] for p in parts])[order])
+
+
 COUNTERS_APPLY = True  # (main(): False for a workload other than the one the counter passes ran -- 1M points per GPU, radius 0.03)
 
 
@@ -726,12 +771,12 @@ def time_steps(job, eng, steps: int, warmup: int, barrier, max_over_ranks, with_
     # two or more), and the breakdown of the other kernels from a few untimed steps after the timed ones.
     warm_rep = {}
     for w in range(warmup):
-        if w == min(1, warmup - 1):
+        if with_timers and w == min(1, warmup - 1):
             eng.sync()
             eng.profile_reset()
             eng.profile(True)
         job.step()
-    if warmup:
+    if warmup and with_timers:
         eng.sync()
         eng.profile(False)
         warm_rep = eng.profile_report()
@@ -860,7 +905,16 @@ def main() -> int:
     ap.add_argument("--emulate-rank", type=int, default=None, metavar="R",
                     help="single process, no rendezvous: run rank R's share of a --gpus N descriptor pass on this GPU (the rows "
                          "the adjacent ranks would send are computed once beforehand; the exchange call itself is skipped)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the descriptor rows of the last step for a fixed sample of points as "
+                         "DIR/fpfh.npy and DIR/shot.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: per-kernel roofline, sustained window, parity, CPU "
+                         "baselines, strong scaling, config 5's tail, RANSAC, normals, other clouds, reference defaults, drop-in "
+                         "calls (each still subject to its --no-* switch)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global COUNTERS_APPLY
     COUNTERS_APPLY = args.points_per_gpu == 1_000_000 and abs(args.radius - 0.03) < 1e-12
 
@@ -886,7 +940,7 @@ def main() -> int:
     os.dup2(2, 1)
 
     shaped = None
-    if single and not args.no_cpu_baseline:  # (forks a Pool: must start before this process touches the GPU)
+    if single and args.full and not args.no_cpu_baseline:  # (forks a Pool: must start before this process touches the GPU)
         shaped = finish_numpy_shaped_baseline(start_numpy_shaped_baseline(args.points_per_gpu, args.radius, args.cpu_sample))
 
     ctl = Control(rank, world) if world > 1 and not emulated else None
@@ -952,7 +1006,7 @@ def main() -> int:
             raise SystemExit("the staged exchange supports the neighbor and halo SPFH modes only")
         return f"control plane, staged through host memory -- {why}"
 
-    if not emulated:
+    if not emulated and (world > 1 or args.full):
         if oversub:
             exchange = stage_through_host("oversubscribed functional test, NOT RCCL")
         else:
@@ -1016,7 +1070,9 @@ def main() -> int:
 
     # ---- timed region: K descriptor passes ---------------------------------------------------------------------------
     elapsed, rep, timed_only, warm_rep, warm_steps = time_steps(job, eng, args.steps, args.warmup, barrier, max_over_ranks,
-                                                                not args.no_kernel_timers)
+                                                                args.full and not args.no_kernel_timers)
+    if args.dump_outputs:
+        dump_outputs(job, n_total, ctl, lead, args.dump_outputs)
     kinds = (1 if job.do_fpfh else 0) + (1 if job.do_shot else 0)
     n_desc = kinds * n_total
     ms_per_step = 1000.0 * elapsed / args.steps
@@ -1028,7 +1084,7 @@ def main() -> int:
     sustained = None
     value_source = (f"the {args.steps} timed steps (every step repeats the search of the same range: planned from the previous "
                     f"search's record, no read-back -- `k2_slot_capacity` in the detail file has the step without it)")
-    if args.sustained_seconds > 0 and not args.no_kernel_timers:
+    if args.full and args.sustained_seconds > 0 and not args.no_kernel_timers:
         sustained = sustained_window(job, eng, ms_per_step, args.sustained_seconds, args.sustained_steps, barrier, max_over_ranks)
         sustained["vs_timed_steps"] = sustained["ms_per_step_median"] / ms_per_step
         ck, ck_src = load_stamped(f"{PROFILE_TAG}_sustained_clock.json", build)
@@ -1049,6 +1105,55 @@ def main() -> int:
                                            "steps": args.steps}) + "\n").encode())
         return 0
     out = {}
+    if lead:
+        out = {
+            "metric": "descriptors/sec (SHOT+FPFH) on 1M-pt cloud",
+            # an EMULATED record (--emulate-rank) is ONE GPU running one rank's share with the exchange call skipped: it has no
+            # multi-GPU value; what its step time would project to is named as what it is
+            "value": None if emulated else value,
+            "unit": "descriptors/s",
+            "n_gpus": 1 if emulated else world,
+            "emulated": emulated,
+            "emulated_rank": rank if emulated else None,
+            "emulated_world": world if emulated else None,
+            "projected_value_upper_bound": value if emulated else None,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": f"uniform cloud, {args.points_per_gpu} points per GPU ({n_total} total), all points "
+                f"keypoints, radius {radius:.5f}, {'FPFH(5 bins)' if job.do_fpfh else ''}"
+                f"{'+' if kinds == 2 else ''}{'SHOT(352, normalize, min_nb 10)' if job.do_shot else ''}, "
+                f"mean neighbourhood {job.last_pairs / max(job.plan.end - job.plan.begin, 1):.1f}",
+                "sharding": f"query blocks over {world} GPU(s), cloud replicated, SPFH {args.spfh_exchange}"
+                + (f" -- EMULATED: rank {rank} of {world} alone on one GPU, the exchange call skipped (c_exchange not in the step)" if emulated else ""),
+                "points_per_gpu": args.points_per_gpu,
+                "exchange": exchange,
+                "library": build,
+            },
+            "value_source": value_source,
+            "sustained": sustained,
+            "per_rank_ms_per_step": [round(x, 4) for x in per_rank_ms],
+            "rccl_ranks": rccl_ranks,
+            "value_includes": "the descriptor pass of every rank (K1 K2 K6 K7 K4 K5) INCLUDING the neighbour exchange of SPFH rows it "
+                              "contains at N > 1 (sf_spfh_exchange_rows on the side stream; `exchange_ms` below is its own launch "
+                              "bracket); EXCLUDING the all-gather of descriptor rows and the matching, which are measured under "
+                              "`exchange_match`" if not emulated else "one rank's share on one GPU, exchange call skipped",
+        }
+    if not args.full:  # a plain run ends here: the headline figure (and, with --dump-outputs, the rows behind it)
+        job.close()
+        if lead:
+            emit_record(json_fd, out, DETAIL_FILE if not emulated else f"bench_detail_rank{rank}_of_{world}.json")
+        os.close(json_fd)
+        if ctl is not None:
+            ctl.barrier()
+            ctl.close()
+        return 0
     if lead:
         kern = {k: (v[0], v[1] / max(v[0], 1)) for k, v in rep.items() if v[0] > 0 and v[1] > 0}
         per_step_ms = {k: rep[k][1] / args.steps for k in kern}
@@ -1092,44 +1197,7 @@ def main() -> int:
                 "note": "counters and clock were taken under the profiler (the kernel runs ~8 % slower there, at a lower clock): a "
                         "ratio within a few per cent of 1 means the kernel's time IS its vector-issue time",
                 "source": sq_src}
-        out = {
-            "metric": "descriptors/sec (SHOT+FPFH) on 1M-pt cloud",
-            # an EMULATED record (--emulate-rank) is ONE GPU running one rank's share with the exchange call skipped: it has no
-            # multi-GPU value; what its step time would project to is named as what it is
-            "value": None if emulated else value,
-            "unit": "descriptors/s",
-            "n_gpus": 1 if emulated else world,
-            "emulated": emulated,
-            "emulated_rank": rank if emulated else None,
-            "emulated_world": world if emulated else None,
-            "projected_value_upper_bound": value if emulated else None,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"uniform cloud, {args.points_per_gpu} points per GPU ({n_total} total), all points "
-                f"keypoints, radius {radius:.5f}, {'FPFH(5 bins)' if job.do_fpfh else ''}"
-                f"{'+' if kinds == 2 else ''}{'SHOT(352, normalize, min_nb 10)' if job.do_shot else ''}, "
-                f"mean neighbourhood {job.last_pairs / max(job.plan.end - job.plan.begin, 1):.1f}",
-                "sharding": f"query blocks over {world} GPU(s), cloud replicated, SPFH {args.spfh_exchange}"
-                + (f" -- EMULATED: rank {rank} of {world} alone on one GPU, the exchange call skipped (c_exchange not in the step)" if emulated else ""),
-                "points_per_gpu": args.points_per_gpu,
-                "exchange": exchange,
-                "library": build,
-            },
-            "value_source": value_source,
-            "sustained": sustained,
-            "per_rank_ms_per_step": [round(x, 4) for x in per_rank_ms],
-            "rccl_ranks": rccl_ranks,
-            "value_includes": "the descriptor pass of every rank (K1 K2 K6 K7 K4 K5) INCLUDING the neighbour exchange of SPFH rows it "
-                              "contains at N > 1 (sf_spfh_exchange_rows on the side stream; `exchange_ms` below is its own launch "
-                              "bracket); EXCLUDING the all-gather of descriptor rows and the matching, which are measured under "
-                              "`exchange_match`" if not emulated else "one rank's share on one GPU, exchange call skipped",
+        out.update({
             "exchange_ms": {k: round(v, 4) for k, v in sorted(per_step_ms.items()) if k.startswith("c_")},
             "kernels_ms_per_step": {k: round(v, 4) for k, v in sorted(per_step_ms.items())},
             "kernels_ms_per_step_source": "HIP events around every launch of the timed steps" if timed_only is None else
@@ -1158,7 +1226,7 @@ def main() -> int:
             "whole_step_hbm": {"algorithmic_bytes": sum(ALG_BYTES[k] for k in ("k6_spfh", "k7_fpfh", "k5_shot")) * units,
                                "achieved_gbs": sum(ALG_BYTES[k] for k in ("k6_spfh", "k7_fpfh", "k5_shot")) * units / (ms_per_step * 1e-3) / 1e9}
             if kinds == 2 else None,
-        }
+        })
 
     # ---- K2's slot capacity: the timed steps size it from the statistics of the previous search with this radius on the cloud
     #      (a capacity hint, never an output: a list that outgrows its slot is re-done exactly).  What the step costs when

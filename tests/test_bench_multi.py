@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
-COMMON = ["--points-per-gpu", "60000", "--radius", "0.08", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sustained-seconds", "0",
+COMMON = ["--full", "--points-per-gpu", "60000", "--radius", "0.08", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sustained-seconds", "0",
           "--no-density", "--no-defaults", "--no-dropin", "--no-normals", "--no-ransac", "--parity-rows", "60"]
 
 
@@ -87,9 +87,9 @@ def test_emulated_rank_record_cannot_be_read_as_a_multi_gpu_result():
 
 
 def test_secondary_keys_of_the_one_rank_record():
-    """The keys the default run adds behind the timed steps, at a small size: the sustained window, the slot-capacity line and
+    """The keys a --full run adds behind the timed steps, at a small size: the sustained window, the slot-capacity line and
     the two-stream step (same rows, the two chains side by side) -- and the parity block, read AFTER them, still holds."""
-    r = run_program([sys.executable, "bench.py", "--points-per-gpu", "60000", "--radius", "0.08", "--steps", "3", "--warmup", "1",
+    r = run_program([sys.executable, "bench.py", "--full", "--points-per-gpu", "60000", "--radius", "0.08", "--steps", "3", "--warmup", "1",
                      "--no-cpu-baseline", "--sustained-seconds", "0.05", "--sustained-steps", "20", "--no-density", "--no-defaults",
                      "--no-dropin", "--no-normals", "--no-match", "--parity-rows", "60"], timeout=900)
     d = record_of(r)
@@ -97,3 +97,39 @@ def test_secondary_keys_of_the_one_rank_record():
     assert d["sustained"]["steps"] >= 20 and d["k2_slot_capacity"]["ms_per_step_with_a_sample_counted_in_every_search"] > 0
     assert d["two_streams"]["ms_per_step"] > 0 and 0.5 < d["two_streams"]["vs_timed_steps"] < 1.5
     assert d["parity"]["ok"]
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_timed_rows(tmp_path):
+    """Without --full the run is the headline figure alone: the contract's keys, exactly --steps timed steps, none of the blocks
+    --full adds.  --dump-outputs writes the rows the timed steps left in HBM for the fixed point sample, in point order, and
+    every one of them is the CPU oracle's row for that point."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle as O
+
+    r = run_program([sys.executable, "bench.py", "--points-per-gpu", "60000", "--radius", "0.08", "--steps", "3", "--warmup", "1",
+                     "--dump-outputs", str(tmp_path)], timeout=900)
+    assert r["rc"] == 0, r["stderr"][-2000:]
+    lines = [ln for ln in r["stdout"].splitlines() if ln.strip()]
+    assert len(lines) == 1, r["stdout"][-2000:]
+    line = json.loads(lines[0])
+    assert LINE_KEYS <= set(line), sorted(LINE_KEYS - set(line))
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "descriptors/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert abs(line["value"] - 2 * 60000 / (line["ms_per_step"] * 1e-3)) <= 1e-4 * line["value"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["sustained"] is None and line["parity"] is None
+    with open(os.path.join(ROOT, line["detail"])) as f:
+        d = json.load(f)
+    for k in ("kernels_ms_per_step", "two_streams", "graph_replay", "k2_slot_capacity", "normals", "dropin_host_to_host"):
+        assert k not in d, k
+    points, normals = bench.make_cloud(60000, 3)
+    sample = np.sort(np.random.default_rng(11).choice(60000, bench.DUMP_POINTS, replace=False))
+    fpfh, shot = np.load(tmp_path / "fpfh.npy"), np.load(tmp_path / "shot.npy")
+    assert fpfh.dtype == shot.dtype == np.float64 and fpfh.shape == (sample.size, 125) and shot.shape == (sample.size, 352)
+    assert sorted(os.listdir(tmp_path)) == ["fpfh.npy", "shot.npy"]
+    want_f = O.compute_fpfh_descriptor_sample(sample, points, normals, 0.08, 5)
+    want_s = O.shot_single_scale(points, normals, points[sample], 0.08, True, 10)
+    assert np.all(np.abs(fpfh - want_f) <= 1e-5 * np.maximum(1.0, np.abs(want_f))), np.abs(fpfh - want_f).max()
+    assert np.all(np.abs(shot - want_s) <= 1e-5 * np.maximum(1.0, np.abs(want_s))), np.abs(shot - want_s).max()

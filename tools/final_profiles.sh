@@ -18,9 +18,9 @@ python tools/team_sq_md.py gpurun_out/pmc_team_${TAG} ${TAG} 0.04 >> gpurun_out/
 # 2c. what the SIMDs do during every kernel of the step -> profiles/<tag>_step_sq.md
 bash tools/pmc_step.sh ${TAG} > gpurun_out/${TAG}_step_sq.log 2>&1
 # 3. the bench record itself (now quoting 1. and 2.), the emulated ranks of an 8-GPU job, config 4
-python bench.py > profiles/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err   # the line the driver parses (ONE run: the first of this build)
+python bench.py --full > profiles/${TAG}_bench.json 2> "${TMPDIR:-/tmp}/${TAG}_bench.err"   # the line the driver parses (ONE run: the first of this build)
 cp bench_detail.json profiles/${TAG}_bench_detail.json                            # every other block of that run
-for r in 0 3 7; do python bench.py --gpus 8 --emulate-rank $r --no-strong > profiles/${TAG}_emulated_rank${r}_of_8.json 2>/dev/null; cp bench_detail_rank${r}_of_8.json profiles/${TAG}_emulated_rank${r}_of_8_detail.json; done
+for r in 0 3 7; do python bench.py --full --gpus 8 --emulate-rank $r --no-strong > profiles/${TAG}_emulated_rank${r}_of_8.json 2>/dev/null; cp bench_detail_rank${r}_of_8.json profiles/${TAG}_emulated_rank${r}_of_8_detail.json; done
 python tools/run_config4.py > profiles/${TAG}_config4.txt 2>&1
 # 4. K8 / K9 at config 4's size under rocprofv3 (kernel trace, fabric traffic, L2, SQ incl. the matrix-core busy counter)
 #    -> profiles/<tag>_match_summary.md ; the 8-rank dry run on this one GPU -> profiles/<tag>_dry_run_n8.json (+ detail)

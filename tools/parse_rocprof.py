@@ -70,7 +70,7 @@ def read_counter(path, counter):
 
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
-    cmd = sys.argv[2] if len(sys.argv) > 2 else ("python3 bench.py --no-cpu-baseline --no-dropin --no-parity --no-density --no-defaults "
+    cmd = sys.argv[2] if len(sys.argv) > 2 else ("python3 bench.py --full --no-cpu-baseline --no-dropin --no-parity --no-density --no-defaults "
                                                  "--no-match --no-normals (20 timed steps + the >= 2 s sustained window)")
     bench_run = len(sys.argv) <= 2  # only the bench profile feeds bench.py's roofline.traffic
     base = os.path.join(ROOT, "gpurun_out", f"prof_{tag}")
