@@ -12,8 +12,8 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "common.h"
 #include "device_util.h"
+#include "match.h"
 
 namespace {
 
@@ -296,10 +296,6 @@ int sf_match_exact(sf_ctx *ctx, const double *da, int64_t m1, const double *db, 
     return match_one_way(ctx, da, m1, db, m2, d, didx, ddist, name, 1, a_ok ? a_ok : ones, b_ok, INFINITY);
 }
 
-int sf_match_gemm(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
-                  double *ddist, const char *name, int64_t *n_slow, const unsigned char *a_ok,
-                  const unsigned char *b_ok); // match_gemm.hip
-
 // Large problems go through the FP64 matrix cores (same result, see match_gemm.hip); small ones, where the
 // fixed costs of the fast path dominate, straight through the exact kernel.  SF_MATCH_EXACT=1 forces the latter.
 static int match_dispatch(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d,
@@ -572,9 +568,84 @@ extern "C" int sf_rows_abs_max(sf_ctx *ctx, const double *rows_dev, int64_t m, i
     return SF_OK;
 }
 
-// (what sf_match_stream_end falls back to: the resident, masked one-shot arg-min)
-int sf_match_argmin_masked_generic(sf_ctx *ctx, const double *a, const double *b, int64_t m1, int64_t m2, int64_t d,
-                                   const unsigned char *a_ok, const unsigned char *b_ok, int64_t *idx, double *dist)
+// ---- shared by the matrix-core paths (match.h) ------------------------------------------------------------------------------------
+namespace {
+__global__ void k_gather_rows(const double *__restrict__ a, int64_t d, const int64_t *__restrict__ rows, int64_t nr,
+                              double *__restrict__ out)
 {
-    return sf_match_argmin_multiscale(ctx, a, b, 1, m1, m2, d, a_ok, b_ok, INFINITY, idx, dist, SF_IN_DEVICE | SF_OUT_DEVICE);
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nr * d) return;
+    const int64_t r = g / d, t = g - r * d;
+    out[g] = a[rows[r] * d + t];
+}
+
+__global__ void k_scatter_results(const int64_t *__restrict__ rows, int64_t nr, const int64_t *__restrict__ sidx,
+                                  const double *__restrict__ sdist, int64_t *__restrict__ idx, double *__restrict__ dist)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nr) return;
+    idx[rows[g]] = sidx[g];
+    if (dist) dist[rows[g]] = sdist[g];
+}
+
+// max over i of v[i] (v >= 0; non-finite entries propagate so that the host can refuse them) -> partial[blockIdx]
+__global__ void k_match_max(const double *__restrict__ v, int64_t n, double *__restrict__ partial)
+{
+    double mx = 0.0;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const double x = v[i];
+        bad |= !(x <= 1.7976931348623157e308) || !(x >= 0.0); // inf or NaN
+        mx = fmax(mx, x);
+    }
+    if (bad) mx = INFINITY;
+    for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
+    __shared__ double s[4];
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(s[0], s[1]), fmax(s[2], s[3]));
+}
+} // namespace
+
+int sf_match_rescue(sf_ctx *ctx, const double *da, int64_t m1, int64_t d, const int *flag, int nf, const sf_match_next &next,
+                    int64_t *didx, double *ddist, int64_t *n_slow)
+{
+    if (n_slow) *n_slow = 0;
+    if (nf <= 0) return SF_OK;
+    std::vector<int> hflag((size_t)m1);
+    SF_HIP(hipMemcpyAsync(hflag.data(), flag, (size_t)m1 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<int64_t> rows;
+    rows.reserve((size_t)nf);
+    for (int64_t i = 0; i < m1; ++i)
+        if (hflag[(size_t)i]) rows.push_back(i);
+    const int64_t nr = (int64_t)rows.size();
+    if (n_slow) *n_slow = nr;
+    sf_pool_guard tmp(ctx);
+    int64_t *drows = nullptr, *sidx = nullptr;
+    double *sub = nullptr, *sdist = nullptr;
+    SF_CHECK(tmp.alloc(&drows, (size_t)nr));
+    SF_CHECK(tmp.alloc(&sidx, (size_t)nr));
+    SF_CHECK(tmp.alloc(&sdist, (size_t)nr));
+    SF_CHECK(tmp.alloc(&sub, (size_t)(nr * d)));
+    SF_HIP(hipMemcpyAsync(drows, rows.data(), (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream)); // rows.data() is a host buffer: the copy is done before any return below
+    SF_LAUNCH(ctx, "k8_gather_rows", k_gather_rows, dim3((unsigned)sf_div_up(nr * d, 256)), dim3(256), da, d,
+              (const int64_t *)drows, nr, sub);
+    SF_CHECK(next(sub, nr, sidx, sdist));
+    SF_LAUNCH(ctx, "k8_scatter_results", k_scatter_results, dim3((unsigned)sf_div_up(nr, 256)), dim3(256),
+              (const int64_t *)drows, nr, (const int64_t *)sidx, (const double *)sdist, didx, ddist);
+    return SF_OK;
+}
+
+int sf_match_max(sf_ctx *ctx, const char *name, const double *v, int64_t n, double *part, double *out)
+{
+    SF_LAUNCH(ctx, name, k_match_max, dim3(256), dim3(256), v, n, part);
+    std::vector<double> h(256);
+    SF_HIP(hipMemcpyAsync(h.data(), part, 256 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    double mx = 0.0;
+    for (double x : h) mx = std::max(mx, x);
+    *out = mx;
+    return SF_OK;
 }

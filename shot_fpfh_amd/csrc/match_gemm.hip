@@ -22,11 +22,8 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
 #include "device_util.h"
-
-int sf_match_exact(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
-                   double *ddist, const char *name, const unsigned char *a_ok, const unsigned char *b_ok); // match.hip
+#include "match.h"
 
 namespace {
 
@@ -59,13 +56,6 @@ __global__ void k_max_partial(const double *__restrict__ v, int64_t n, double *_
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = mx;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(s[0], s[1]), fmax(s[2], s[3]));
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false),
-                            __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false));
 }
 
 // best / second-best bookkeeping for one row; ties count as "second best equal to best" (-> slow path)
@@ -200,8 +190,8 @@ __global__ __launch_bounds__(256, 2) void k_match_gemm(const double *__restrict_
         // insert + butterfly + merge below is skipped (wave-uniformly) for almost every row of almost every tile.
 #define SF_TOP2_STEP(CTRL)                                                                                          \
     {                                                                                                               \
-        const double om1 = dpp_f64<CTRL>(t.m1), om2 = dpp_f64<CTRL>(t.m2);                                          \
-        const int oj = __builtin_amdgcn_update_dpp(0, jloc, CTRL, 0xf, 0xf, false);                                 \
+        const double om1 = sf_dpp<CTRL>(t.m1), om2 = sf_dpp<CTRL>(t.m2);                                            \
+        const int oj = sf_dpp<CTRL>(jloc);                                                                          \
         if (om1 < t.m1 || (om1 == t.m1 && oj < jloc)) {                                                             \
             const double keep = t.m1;                                                                               \
             t.m2 = fmin(om2, keep);                                                                                 \
@@ -213,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void k_match_gemm(const double *__restrict_
     }
 #define SF_EPI_ROW(TI, R)                                                                                           \
     {                                                                                                               \
-        const double thr = dpp_f64<0x150 + 4 * (TI) + (R)>(run.m2);                                                 \
+        const double thr = sf_dpp<0x150 + 4 * (TI) + (R)>(run.m2);                                                  \
         double key[4];                                                                                              \
         bool below = false;                                                                                         \
         _Pragma("unroll") for (int tj = 0; tj < 4; ++tj) {                                                          \
@@ -306,24 +296,6 @@ __global__ void k_match_decide(const double *__restrict__ a, int64_t m1, const d
     if (!decided) atomicAdd(n_flagged, 1);
 }
 
-__global__ void k_gather_rows(const double *__restrict__ a, int64_t d, const int64_t *__restrict__ rows, int64_t nr,
-                              double *__restrict__ out)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nr * d) return;
-    const int64_t r = g / d, t = g - r * d;
-    out[g] = a[rows[r] * d + t];
-}
-
-__global__ void k_scatter_results(const int64_t *__restrict__ rows, int64_t nr, const int64_t *__restrict__ sidx,
-                                  const double *__restrict__ sdist, int64_t *__restrict__ idx, double *__restrict__ dist)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nr) return;
-    idx[rows[g]] = sidx[g];
-    if (dist) dist[rows[g]] = sdist[g];
-}
-
 } // namespace
 
 // Row arg-min of cdist(a, b) with the exact kernel's result; returns the number of rows that needed the slow path.
@@ -372,45 +344,11 @@ int sf_match_gemm_f64(sf_ctx *ctx, const double *da, int64_t m1, const double *d
     int nf = 0;
     SF_HIP(hipMemcpyAsync(&nf, nflag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
-    int rc = SF_OK;
-    if (nf > 0) {
-        // slow path for the undecided rows: exact kernel on the gathered rows, results scattered back
-        std::vector<int> hflag((size_t)m1);
-        SF_HIP(hipMemcpyAsync(hflag.data(), flag, (size_t)m1 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SF_HIP(hipStreamSynchronize(ctx->stream));
-        std::vector<int64_t> rows;
-        rows.reserve((size_t)nf);
-        for (int64_t i = 0; i < m1; ++i)
-            if (hflag[(size_t)i]) rows.push_back(i);
-        const int64_t nr = (int64_t)rows.size();
-        int64_t *drows = nullptr, *sidx = nullptr;
-        double *sub = nullptr, *sdist = nullptr;
-        SF_CHECK(tmp.alloc(&drows, (size_t)nr));
-        SF_CHECK(tmp.alloc(&sidx, (size_t)nr));
-        SF_CHECK(tmp.alloc(&sdist, (size_t)nr));
-        SF_CHECK(tmp.alloc(&sub, (size_t)(nr * d)));
-        SF_HIP(hipMemcpyAsync(drows, rows.data(), (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-        SF_LAUNCH(ctx, "k8_gather_rows", k_gather_rows, dim3((unsigned)sf_div_up(nr * d, 256)), dim3(256), da, d,
-                  (const int64_t *)drows, nr, sub);
-        rc = sf_match_exact(ctx, sub, nr, db, m2, d, sidx, sdist, "k8_match_tile_slowpath", nullptr, b_ok);
-        if (rc == SF_OK) {
-            SF_LAUNCH(ctx, "k8_scatter_results", k_scatter_results, dim3((unsigned)sf_div_up(nr, 256)), dim3(256),
-                      (const int64_t *)drows, nr, (const int64_t *)sidx, (const double *)sdist, didx, ddist);
-        }
-        SF_HIP(hipStreamSynchronize(ctx->stream)); // rows.data() is a host buffer
-        if (n_slow) *n_slow = nr;
-    }
-    return rc;
+    // slow path for the undecided rows: the exact kernel on the gathered rows
+    return sf_match_rescue(ctx, da, m1, d, flag, nf, [&](const double *sub, int64_t nr, int64_t *sidx, double *sdist) {
+        return sf_match_exact(ctx, sub, nr, db, m2, d, sidx, sdist, "k8_match_tile_slowpath", nullptr, b_ok);
+    }, didx, ddist, n_slow);
 }
-
-int sf_match_half_mode(); // match_half.hip
-int sf_match_i8_mode();   // match_i8.hip
-int sf_match_i8(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
-                double *ddist, const char *name, int64_t *n_slow, const unsigned char *a_ok, const unsigned char *b_ok,
-                int *used);
-int sf_match_half(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
-                  double *ddist, const char *name, int64_t *n_slow, const unsigned char *a_ok, const unsigned char *b_ok,
-                  int *used);
 
 // The matrix-core paths: FP16 pre-filter + float64 decision (match_half.hip) when the problem is large enough to
 // pay for the conversion passes, the FP64 GEMM otherwise.  Same result either way.

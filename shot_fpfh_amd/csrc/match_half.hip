@@ -36,14 +36,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <vector>
 
-#include "common.h"
 #include "device_util.h"
-
-int sf_match_gemm_f64(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
-                      double *ddist, const char *name, int64_t *n_slow, const unsigned char *a_ok,
-                      const unsigned char *b_ok); // match_gemm.hip
+#include "match.h"
 
 namespace {
 
@@ -88,24 +83,6 @@ __global__ __launch_bounds__(256) void k_half_convert(const double *__restrict__
     }
 }
 
-// max over i of v[i] (v >= 0; non-finite entries propagate so that the host can refuse them) -> partial[blockIdx]
-__global__ void k_half_max(const double *__restrict__ v, int64_t n, double *__restrict__ partial)
-{
-    double mx = 0.0;
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const double x = v[i];
-        bad |= !(x <= 1.7976931348623157e308) || !(x >= 0.0); // inf or NaN
-        mx = fmax(mx, x);
-    }
-    if (bad) mx = INFINITY;
-    for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
-    __shared__ double s[4];
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(s[0], s[1]), fmax(s[2], s[3]));
-}
-
 // W_i of the header, rounded up to float; rows beyond m get 0 (their thresholds start at -inf and never move)
 __global__ void k_half_window(const double *__restrict__ ea, const double *__restrict__ qa, const double *__restrict__ na2,
                               int64_t m, int64_t m_pad, double bmax, double ebmax, double qbmax, double nbmax,
@@ -122,12 +99,6 @@ __global__ void k_half_window(const double *__restrict__ ea, const double *__res
     float wf = (float)w;
     if ((double)wf < w) wf = nextafterf(wf, INFINITY);
     win[i] = wf;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
 
 // The pass.  ah: m1_pad x DP (m1_pad a multiple of 256), bh: m2_pad x DP (m2_pad a multiple of 64), row-major FP16.
@@ -320,10 +291,10 @@ __global__ __launch_bounds__(512, 1) void k_match_half(const _Float16 *__restric
                     const bool hit = (key <= T[r]) & (key < INFINITY);
                     if (__ballot(hit)) {
                         float v = hit ? key : INFINITY;
-                        v = fminf(v, dpp_f32<0xB1>(v));  // quad_perm [1,0,3,2]
-                        v = fminf(v, dpp_f32<0x4E>(v));  // quad_perm [2,3,0,1]
-                        v = fminf(v, dpp_f32<0x141>(v)); // row_half_mirror
-                        v = fminf(v, dpp_f32<0x140>(v)); // row_mirror: min of the 16-lane row in every lane
+                        v = fminf(v, sf_dpp<0xB1>(v));  // quad_perm [1,0,3,2]
+                        v = fminf(v, sf_dpp<0x4E>(v));  // quad_perm [2,3,0,1]
+                        v = fminf(v, sf_dpp<0x141>(v)); // row_half_mirror
+                        v = fminf(v, sf_dpp<0x140>(v)); // row_mirror: min of the 16-lane row in every lane
                         v = fminf(v, __shfl_xor(v, 16)); // the two DPP rows of this 32-lane half
                         const int64_t row = rowbase + (r & 3) + 8 * (r >> 2);
                         const float tn = fminf(T[r], v + win[row]);
@@ -399,83 +370,25 @@ __global__ void k_half_final(const double *__restrict__ a, int64_t m1, const dou
     const float w = win[i] * 1.001f;
     for (int s = 0; s < nsplit; ++s)
         overflow |= cnt[(int64_t)s * m1_pad + i] > HCAP && !(thr[(int64_t)s * m1_pad + i] - w > t);
-    double best = INFINITY;
-    int64_t bj = -1;
-    bool model_ok = true;
+    sf_recheck r;
     if (!overflow) {
         const double *ai = a + i * d;
-        const double half_w = 0.5 * (double)win[i], na = na2[i];
+        const double half_w = 0.5 * (double)win[i], na = na2[i]; // (the pre-filter's key is within eps_i < W_i / 2 of the float64 one)
         for (int s = 0; s < nsplit; ++s) {
             const int64_t base = ((int64_t)s * m1_pad + i) * HCAP;
             const int n = min(cnt[(int64_t)s * m1_pad + i], HCAP);
-            for (int c = sub; c < n; c += LPR) {
-                if (!(cand_k[base + c] <= t)) continue;
-                const int64_t j = cand_j[base + c];
-                const double *bjp = b + j * d;
-                double acc = 0.0;
-                for (int64_t u = 0; u < d; ++u) {
-                    const double df = ai[u] - bjp[u];
-                    acc += df * df; // left to right, no FMA: scipy's euclidean loop
-                }
-                // safety net for the error model: the pre-filter's key of this pair must be within eps_i (< W_i / 2)
-                // of the float64 one, ||a - b||^2 - ||a||^2; a row where it is not is handed to the FP64 path
-                model_ok &= fabs((acc - na) * unit - (double)cand_k[base + c]) <= half_w;
-                const double dj = sqrt(acc);
-                if (dj < best || (dj == best && j < bj) || bj < 0) {
-                    if (!(dj == dj)) continue; // NaN: leave the row to the float64 path
-                    best = dj;
-                    bj = j;
-                }
-            }
+            for (int c = sub; c < n; c += LPR)
+                if (cand_k[base + c] <= t)
+                    sf_recheck_candidate(r, ai, b, d, cand_j[base + c], (double)cand_k[base + c], na, unit, half_w);
         }
     }
-#pragma unroll
-    for (int off = LPR / 2; off > 0; off >>= 1) { // (minimum with the smaller column on ties: the order of the fold does not matter)
-        const double ob = __shfl_xor(best, off);
-        const int64_t oj = __shfl_xor(bj, off);
-        const int om = __shfl_xor((int)model_ok, off);
-        if (oj >= 0 && (bj < 0 || ob < best || (ob == best && oj < bj))) {
-            best = ob;
-            bj = oj;
-        }
-        model_ok = model_ok && om;
-    }
+    sf_recheck_fold<LPR>(r);
     if (sub != 0) return;
-    const bool decided = bj >= 0 && model_ok;
-    idx[i] = decided ? bj : 0;
-    if (dist) dist[i] = best;
+    const bool decided = r.bj >= 0 && r.ok;
+    idx[i] = decided ? r.bj : 0;
+    if (dist) dist[i] = r.best;
     flag[i] = decided ? 0 : 1;
     if (!decided) atomicAdd(n_flagged, 1);
-}
-
-__global__ void k_half_gather_rows(const double *__restrict__ a, int64_t d, const int64_t *__restrict__ rows, int64_t nr,
-                                   double *__restrict__ out)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nr * d) return;
-    const int64_t r = g / d, t = g - r * d;
-    out[g] = a[rows[r] * d + t];
-}
-
-__global__ void k_half_scatter(const int64_t *__restrict__ rows, int64_t nr, const int64_t *__restrict__ sidx,
-                               const double *__restrict__ sdist, int64_t *__restrict__ idx, double *__restrict__ dist)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nr) return;
-    idx[rows[g]] = sidx[g];
-    if (dist) dist[rows[g]] = sdist[g];
-}
-
-int host_max(sf_ctx *ctx, const double *v, int64_t n, double *part, double *out)
-{
-    SF_LAUNCH(ctx, "k8_half_max", k_half_max, dim3(256), dim3(256), v, n, part);
-    std::vector<double> h(256);
-    SF_HIP(hipMemcpyAsync(h.data(), part, 256 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream));
-    double mx = 0.0;
-    for (double x : h) mx = std::max(mx, x);
-    *out = mx;
-    return SF_OK;
 }
 
 // power of two p with p * sqrt(n2max) in [2^13, 2^14]: FP16 keeps 11 significant bits down to 2^-14, so entries
@@ -529,8 +442,8 @@ int sf_match_half(sf_ctx *ctx, const double *da, int64_t m1, const double *db, i
                   1.0, (const unsigned char *)nullptr, (_Float16 *)nullptr, ea, qa, na2, (float *)nullptr, 1.0);
         SF_LAUNCH(ctx, "k8_half_convert", k_half_convert, dim3((unsigned)sf_div_up(m2p, 4)), dim3(256), db, m2, m2p, d, dp,
                   1.0, b_ok, (_Float16 *)nullptr, eb, qb, nb2, (float *)nullptr, 1.0);
-        int rc = host_max(ctx, na2, m1, part, &namax);
-        if (rc == SF_OK) rc = host_max(ctx, nb2, m2, part, &nbmax);
+        int rc = sf_match_max(ctx, "k8_half_max", na2, m1, part, &namax);
+        if (rc == SF_OK) rc = sf_match_max(ctx, "k8_half_max", nb2, m2, part, &nbmax);
         if (rc != SF_OK) return rc;
     }
     if (!pick_scale(namax, &sa) || !pick_scale(nbmax, &sb)) return SF_OK;
@@ -543,20 +456,13 @@ int sf_match_half(sf_ctx *ctx, const double *da, int64_t m1, const double *db, i
               b_ok, bh, eb, qb, nb2, nbf, unit);
     double ebmax = 0.0, qbmax = 0.0;
     {
-        int rc = host_max(ctx, eb, m2, part, &ebmax);
-        if (rc == SF_OK) rc = host_max(ctx, qb, m2, part, &qbmax);
+        int rc = sf_match_max(ctx, "k8_half_max", eb, m2, part, &ebmax);
+        if (rc == SF_OK) rc = sf_match_max(ctx, "k8_half_max", qb, m2, part, &qbmax);
         if (rc != SF_OK) return rc;
     }
     if (!std::isfinite(ebmax) || !std::isfinite(qbmax)) return SF_OK;
-    // column splits: (1) each split is short enough for an XCD's workgroups to share its tiles through their L2 (8 MB: hit rate
-    // 0.83 against 0.90 / 0.89 at 2 / 4 MB with fewer lists to walk, profiles/r03_match_summary.md) -- see the note above k_match_half; (2) with few row blocks,
-    // enough workgroups for two per CU's worth of the chip, each with at least 32 tiles to scan
     const int64_t col_tiles = m2p / HN;
-    const int64_t chunk_kb = 8192;
-    const int64_t tiles_in_l2 = std::max<int64_t>(8, chunk_kb * 1024 / ((int64_t)HN * dp * 2));
-    int64_t nsplit = sf_div_up(col_tiles, tiles_in_l2);
-    if ((m1p / HM) * nsplit < 512) nsplit = std::max<int64_t>(nsplit, std::min<int64_t>(sf_div_up(512, m1p / HM), std::max<int64_t>(col_tiles / 32, 1)));
-    if (const char *e = getenv("SF_MATCH_HALF_SPLITS")) nsplit = std::max<int64_t>(1, std::min<int64_t>(atoll(e), col_tiles));
+    int64_t nsplit = sf_match_splits(col_tiles, (int64_t)HN * dp * 2, m1p / HM, "SF_MATCH_HALF_SPLITS");
     const int64_t tiles_per_split = sf_div_up(col_tiles, nsplit);
     nsplit = sf_div_up(col_tiles, tiles_per_split);
     const bool seed = true; // (a row's threshold shared between its splits: without it the pass runs 2.3 x longer, same result)
@@ -601,32 +507,10 @@ int sf_match_half(sf_ctx *ctx, const double *da, int64_t m1, const double *db, i
     int nf = 0;
     SF_HIP(hipMemcpyAsync(&nf, nflag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
-    int rc = SF_OK;
-    if (n_slow) *n_slow = 0;
-    if (nf > 0) { // overflowing / non-finite rows: the FP64 path on the gathered rows
-        std::vector<int> hflag((size_t)m1);
-        SF_HIP(hipMemcpyAsync(hflag.data(), flag, (size_t)m1 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SF_HIP(hipStreamSynchronize(ctx->stream));
-        std::vector<int64_t> rows;
-        rows.reserve((size_t)nf);
-        for (int64_t i = 0; i < m1; ++i)
-            if (hflag[(size_t)i]) rows.push_back(i);
-        const int64_t nr = (int64_t)rows.size();
-        int64_t *drows = nullptr, *sidx = nullptr;
-        double *sub = nullptr, *sdist = nullptr;
-        SF_HALLOC(drows, nr); SF_HALLOC(sidx, nr); SF_HALLOC(sdist, nr); SF_HALLOC(sub, nr * d);
-        SF_HIP(hipMemcpyAsync(drows, rows.data(), (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-        SF_LAUNCH(ctx, "k8_gather_rows", k_half_gather_rows, dim3((unsigned)sf_div_up(nr * d, 256)), dim3(256), da, d,
-                  (const int64_t *)drows, nr, sub);
-        int64_t slow2 = 0;
-        rc = sf_match_gemm_f64(ctx, sub, nr, db, m2, d, sidx, sdist, "k8_match_gemm_overflow", &slow2, nullptr, b_ok);
-        if (rc == SF_OK) {
-            SF_LAUNCH(ctx, "k8_scatter_results", k_half_scatter, dim3((unsigned)sf_div_up(nr, 256)), dim3(256),
-                      (const int64_t *)drows, nr, (const int64_t *)sidx, (const double *)sdist, didx, ddist);
-        }
-        SF_HIP(hipStreamSynchronize(ctx->stream)); // rows.data() is a host buffer
-        if (n_slow) *n_slow = nr;
-    }
+    // overflowing / non-finite rows: the FP64 path on the gathered rows
+    const int rc = sf_match_rescue(ctx, da, m1, d, flag, nf, [&](const double *sub, int64_t nr, int64_t *sidx, double *sdist) {
+        return sf_match_gemm_f64(ctx, sub, nr, db, m2, d, sidx, sdist, "k8_match_gemm_overflow", nullptr, nullptr, b_ok);
+    }, didx, ddist, n_slow);
 #undef SF_HALLOC
     *used = 1;
     return rc;

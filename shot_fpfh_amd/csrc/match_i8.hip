@@ -41,15 +41,8 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.h"
 #include "device_util.h"
-
-int sf_match_half(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
-                  double *ddist, const char *name, int64_t *n_slow, const unsigned char *a_ok, const unsigned char *b_ok,
-                  int *used); // match_half.hip
-int sf_match_gemm_f64(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
-                      double *ddist, const char *name, int64_t *n_slow, const unsigned char *a_ok,
-                      const unsigned char *b_ok); // match_gemm.hip
+#include "match.h"
 
 namespace {
 
@@ -127,24 +120,6 @@ __global__ __launch_bounds__(256) void k_i8_convert(const double *__restrict__ a
     }
 }
 
-// max over i of v[i] (v >= 0; non-finite entries propagate) -> partial[blockIdx]
-__global__ void k_i8_max(const double *__restrict__ v, int64_t n, double *__restrict__ partial)
-{
-    double mx = 0.0;
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const double x = v[i];
-        bad |= !(x <= 1.7976931348623157e308) || !(x >= 0.0);
-        mx = fmax(mx, x);
-    }
-    if (bad) mx = INFINITY;
-    for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
-    __shared__ double s[4];
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(s[0], s[1]), fmax(s[2], s[3]));
-}
-
 // W_i of the header in integer key units (unit = 1 / u = sa sb / 2); rows beyond m get 0 (their thresholds never move)
 __global__ void k_i8_window(const double *__restrict__ ea, const double *__restrict__ qa, const double *__restrict__ na2, int64_t m,
                             int64_t m_pad, double bmax, double ebmax, double nbmax, double unit, int *__restrict__ win)
@@ -156,12 +131,6 @@ __global__ void k_i8_window(const double *__restrict__ ea, const double *__restr
     const double eps = 2.0 * (ea[i] * bmax + qa[i] * ebmax) * (1.0 + 1e-6) + 1e-12 * (na2[i] + nbmax);
     const double w = ceil(2.0 * eps * unit * (1.0 + 1e-9)) + 2.0;
     win[i] = w < (double)(1 << 27) ? (int)w : (1 << 27); // (an absurd window only floods the row's lists: it is then flagged)
-}
-
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v)
-{
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
 }
 
 // LDS image and fragment addressing shared by the two passes: two column tiles, filled by LDS-DMA (global_load_lds_dwordx4),
@@ -292,10 +261,10 @@ __global__ __launch_bounds__(512, 1) void k_i8_min(const unsigned char *__restri
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             int v = best[b][r];
-            v = max(v, dpp_i32<0xB1>(v));  // quad_perm [1,0,3,2]
-            v = max(v, dpp_i32<0x4E>(v));  // quad_perm [2,3,0,1]
-            v = max(v, dpp_i32<0x141>(v)); // row_half_mirror
-            v = max(v, dpp_i32<0x140>(v)); // row_mirror: max of the 16-lane row in every lane
+            v = max(v, sf_dpp<0xB1>(v));  // quad_perm [1,0,3,2]
+            v = max(v, sf_dpp<0x4E>(v));  // quad_perm [2,3,0,1]
+            v = max(v, sf_dpp<0x141>(v)); // row_half_mirror
+            v = max(v, sf_dpp<0x140>(v)); // row_mirror: max of the 16-lane row in every lane
             v = max(v, __shfl_xor(v, 16)); // the two DPP rows of this 32-lane half
             if (r31 == 0) smin[split * m1_pad + row0 + 32 * b + (r & 3) + 8 * (r >> 2) + 4 * h] = -v;
         }
@@ -492,85 +461,27 @@ __global__ void k_i8_final(const double *__restrict__ a, int64_t m1, const doubl
     const int sub = (int)(gid % LPR);
     if (i >= m1) return; // (whole groups of LPR lanes: LPR divides the wave)
     if ((a_ok && !a_ok[i]) || flag[i]) return; // (masked: written by k_i8_live; flagged there: the FP16 pass's)
-    double best = INFINITY;
-    int64_t bj = -1;
-    bool ok = true;
+    sf_recheck r;
     const double *ai = a + i * d;
-    const double slack = (double)win[i], na = na2[i];
+    const double half_w = 0.5 * (double)win[i], na = na2[i]; // (the integer key is within eps_i / u + 1/2 < W_i / 2 of the float64 one)
     for (int l = 0; l < I_LIVE; ++l) {
         const int p = live[i * I_LIVE + l];
         if (p < 0) continue;
         const int n = cnt[p];
-        if (n > ICAP) { ok = false; continue; } // more columns within the window than the list holds: the FP16 pass
+        if (n > ICAP) { r.ok = false; continue; } // more columns within the window than the list holds: the FP16 pass
         const int64_t base = (int64_t)p * ICAP;
-        for (int c = sub; c < n; c += LPR) {
-            const int64_t j = cand_j[base + c];
-            const double *bjp = b + j * d;
-            double acc = 0.0;
-            for (int64_t u = 0; u < d; ++u) {
-                const double df = ai[u] - bjp[u];
-                acc += df * df; // left to right, no FMA: scipy's euclidean loop
-            }
-            // safety net for the error model: the integer key of this pair must be within eps_i / u + 1/2 (< W_i / 2) of the
-            // float64 one, (||a - b||^2 - ||a||^2) / u; a row where it is not is handed on
-            ok &= fabs((acc - na) * unit - (double)cand_k[base + c]) <= 0.5 * slack;
-            const double dj = sqrt(acc);
-            if (dj < best || (dj == best && j < bj) || bj < 0) {
-                if (!(dj == dj)) continue; // NaN: leave the row to the float64 path
-                best = dj;
-                bj = j;
-            }
-        }
+        for (int c = sub; c < n; c += LPR)
+            sf_recheck_candidate(r, ai, b, d, cand_j[base + c], (double)cand_k[base + c], na, unit, half_w);
     }
-#pragma unroll
-    for (int off = LPR / 2; off > 0; off >>= 1) { // (minimum with the smaller column on ties: the order of the fold does not matter)
-        const double ob = __shfl_xor(best, off);
-        const int64_t oj = __shfl_xor(bj, off);
-        const int om = __shfl_xor((int)ok, off);
-        if (oj >= 0 && (bj < 0 || ob < best || (ob == best && oj < bj))) {
-            best = ob;
-            bj = oj;
-        }
-        ok = ok && om;
-    }
+    sf_recheck_fold<LPR>(r);
     if (sub != 0) return;
-    const bool decided = bj >= 0 && ok;
-    idx[i] = decided ? bj : 0;
-    if (dist) dist[i] = best;
+    const bool decided = r.bj >= 0 && r.ok;
+    idx[i] = decided ? r.bj : 0;
+    if (dist) dist[i] = r.best;
     if (!decided) {
         flag[i] = 1;
         atomicAdd(n_flagged, 1);
     }
-}
-
-__global__ void k_i8_gather_rows(const double *__restrict__ a, int64_t d, const int64_t *__restrict__ rows, int64_t nr,
-                                 double *__restrict__ out)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nr * d) return;
-    const int64_t r = g / d, t = g - r * d;
-    out[g] = a[rows[r] * d + t];
-}
-
-__global__ void k_i8_scatter(const int64_t *__restrict__ rows, int64_t nr, const int64_t *__restrict__ sidx,
-                             const double *__restrict__ sdist, int64_t *__restrict__ idx, double *__restrict__ dist)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nr) return;
-    idx[rows[g]] = sidx[g];
-    if (dist) dist[rows[g]] = sdist[g];
-}
-
-int i8_host_max(sf_ctx *ctx, const double *v, int64_t n, double *part, double *out)
-{
-    SF_LAUNCH(ctx, "k8_i8_max", k_i8_max, dim3(256), dim3(256), v, n, part);
-    std::vector<double> h(256);
-    SF_HIP(hipMemcpyAsync(h.data(), part, 256 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream));
-    double mx = 0.0;
-    for (double x : h) mx = std::max(mx, x);
-    *out = mx;
-    return SF_OK;
 }
 
 } // namespace
@@ -644,8 +555,8 @@ int st_begin(sf_match_stream *st, double b_entry_max, int64_t max_ranges, bool *
     SF_CHECK(st_alloc(st, &st->amx, std::max(m1, m2)));
     double namax = 0.0, aamax = 0.0;
     SF_LAUNCH(ctx, "k8_i8_convert", k_i8_rowstat, dim3((unsigned)sf_div_up(m1, 4)), dim3(256), st->da, m1, d, st->na2, st->amx);
-    SF_CHECK(i8_host_max(ctx, st->na2, m1, st->part, &namax));
-    SF_CHECK(i8_host_max(ctx, st->amx, m1, st->part, &aamax));
+    SF_CHECK(sf_match_max(ctx, "k8_i8_max", st->na2, m1, st->part, &namax));
+    SF_CHECK(sf_match_max(ctx, "k8_i8_max", st->amx, m1, st->part, &aamax));
     if (!(aamax > 0.0) || !(b_entry_max > 0.0) || !std::isfinite(namax) || !std::isfinite(aamax) || !std::isfinite(b_entry_max)) return SF_OK;
     st->sa = 127.0 / aamax;
     st->sb = 127.0 / b_entry_max;
@@ -656,14 +567,8 @@ int st_begin(sf_match_stream *st, double b_entry_max, int64_t max_ranges, bool *
     if (m1p > m1) SF_HIP(hipMemsetAsync(st->na2 + m1, 0, (size_t)(m1p - m1) * sizeof(double), ctx->stream));
     SF_LAUNCH(ctx, "k8_i8_convert", k_i8_convert, dim3((unsigned)sf_div_up(m1p, 4)), dim3(256), st->da, m1, m1p, d, st->dp, st->sa,
               (const unsigned char *)nullptr, reinterpret_cast<unsigned *>(st->ai), st->ea, st->qa, (const double *)st->na2, (int *)nullptr, st->unit);
-    // column splits: 8 MB of reference rows each, so that an XCD's workgroups share the split they stream in their L2 (as
-    // sf_match_half); with few row blocks, enough splits to fill the chip
     const int64_t col_tiles = m2p / IN;
-    const int64_t chunk_kb = 8192;
-    const int64_t tiles_in_l2 = std::max<int64_t>(8, chunk_kb * 1024 / ((int64_t)IN * st->dp));
-    int64_t nsplit = sf_div_up(col_tiles, tiles_in_l2);
-    if ((m1p / st->IM) * nsplit < 512) nsplit = std::max<int64_t>(nsplit, std::min<int64_t>(sf_div_up(512, m1p / st->IM), std::max<int64_t>(col_tiles / 32, 1)));
-    if (const char *e = getenv("SF_MATCH_I8_SPLITS")) nsplit = std::max<int64_t>(1, std::min<int64_t>(atoll(e), col_tiles));
+    const int64_t nsplit = sf_match_splits(col_tiles, (int64_t)IN * st->dp, m1p / st->IM, "SF_MATCH_I8_SPLITS");
     st->tiles_target = sf_div_up(col_tiles, nsplit);
     st->split_cap = sf_div_up(col_tiles, st->tiles_target) + std::max<int64_t>(max_ranges, 1);
     if (st->split_cap > 65536) return SF_OK;
@@ -721,8 +626,8 @@ int st_window(sf_match_stream *st, bool *suitable)
 {
     sf_ctx *ctx = st->ctx;
     *suitable = false;
-    SF_CHECK(i8_host_max(ctx, st->nb2, st->m2, st->part, &st->nbmax));
-    SF_CHECK(i8_host_max(ctx, st->eb, st->m2, st->part, &st->ebmax));
+    SF_CHECK(sf_match_max(ctx, "k8_i8_max", st->nb2, st->m2, st->part, &st->nbmax));
+    SF_CHECK(sf_match_max(ctx, "k8_i8_max", st->eb, st->m2, st->part, &st->ebmax));
     if (!std::isfinite(st->nbmax) || !std::isfinite(st->ebmax) || !(st->nbmax * st->unit < 4e6)) return SF_OK;
     SF_LAUNCH(ctx, "k8_i8_window", k_i8_window, dim3((unsigned)sf_div_up(st->m1p, 256)), dim3(256), (const double *)st->ea, (const double *)st->qa,
               (const double *)st->na2, st->m1, st->m1p, std::sqrt(st->nbmax), st->ebmax, st->nbmax, st->unit, st->win);
@@ -801,36 +706,13 @@ int st_flagged(sf_match_stream *st, int *nf)
 // the flagged rows -- no clear nearest descriptor, or overflowing lists -- through the FP16 pass on the gathered rows
 int st_fallback(sf_match_stream *st, int nf, int64_t *didx, double *ddist, int64_t *n_slow)
 {
-    sf_ctx *ctx = st->ctx;
-    const int64_t m1 = st->m1, d = st->d;
-    if (n_slow) *n_slow = 0;
-    if (nf <= 0) return SF_OK;
-    std::vector<int> hflag((size_t)m1);
-    SF_HIP(hipMemcpyAsync(hflag.data(), st->flag, (size_t)m1 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream));
-    std::vector<int64_t> rows;
-    rows.reserve((size_t)nf);
-    for (int64_t i = 0; i < m1; ++i)
-        if (hflag[(size_t)i]) rows.push_back(i);
-    const int64_t nr = (int64_t)rows.size();
-    sf_pool_guard tmp(ctx);
-    int64_t *drows = nullptr, *sidx = nullptr;
-    double *sub = nullptr, *sdist = nullptr;
-    SF_CHECK(tmp.alloc(&drows, (size_t)nr)); SF_CHECK(tmp.alloc(&sidx, (size_t)nr)); SF_CHECK(tmp.alloc(&sdist, (size_t)nr)); SF_CHECK(tmp.alloc(&sub, (size_t)(nr * d)));
-    SF_HIP(hipMemcpyAsync(drows, rows.data(), (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    SF_LAUNCH(ctx, "k8_gather_rows", k_i8_gather_rows, dim3((unsigned)sf_div_up(nr * d, 256)), dim3(256), st->da, d, (const int64_t *)drows, nr, sub);
-    SF_HIP(hipStreamSynchronize(ctx->stream)); // rows.data() is a host buffer
-    int64_t slow2 = 0;
-    int used2 = 0;
-    int rc = sf_match_half(ctx, sub, nr, st->db, st->m2, d, sidx, sdist, "k8_match_half", &slow2, nullptr, st->b_ok, &used2);
-    if (rc == SF_OK && !used2) // (norms the FP16 image cannot hold: float64 all the way)
-        rc = sf_match_gemm_f64(ctx, sub, nr, st->db, st->m2, d, sidx, sdist, "k8_match_gemm_overflow", &slow2, nullptr, st->b_ok);
-    if (rc == SF_OK) {
-        SF_LAUNCH(ctx, "k8_scatter_results", k_i8_scatter, dim3((unsigned)sf_div_up(nr, 256)), dim3(256), (const int64_t *)drows, nr,
-                  (const int64_t *)sidx, (const double *)sdist, didx, ddist);
-    }
-    if (n_slow) *n_slow = nr;
-    return rc;
+    return sf_match_rescue(st->ctx, st->da, st->m1, st->d, st->flag, nf, [st](const double *sub, int64_t nr, int64_t *sidx, double *sdist) {
+        int used = 0;
+        int rc = sf_match_half(st->ctx, sub, nr, st->db, st->m2, st->d, sidx, sdist, "k8_match_half", nullptr, nullptr, st->b_ok, &used);
+        if (rc == SF_OK && !used) // (norms the FP16 image cannot hold: float64 all the way)
+            rc = sf_match_gemm_f64(st->ctx, sub, nr, st->db, st->m2, st->d, sidx, sdist, "k8_match_gemm_overflow", nullptr, nullptr, st->b_ok);
+        return rc;
+    }, didx, ddist, n_slow);
 }
 
 } // namespace
@@ -853,7 +735,7 @@ int sf_match_i8(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int
         double *n2 = nullptr, *mx = nullptr, *part = nullptr;
         SF_CHECK(tmp.alloc(&n2, (size_t)m2)); SF_CHECK(tmp.alloc(&mx, (size_t)m2)); SF_CHECK(tmp.alloc(&part, 256));
         SF_LAUNCH(ctx, "k8_i8_convert", k_i8_rowstat, dim3((unsigned)sf_div_up(m2, 4)), dim3(256), db, m2, d, n2, mx);
-        SF_CHECK(i8_host_max(ctx, mx, m2, part, &abmax));
+        SF_CHECK(sf_match_max(ctx, "k8_i8_max", mx, m2, part, &abmax));
     }
     bool ok = false;
     SF_CHECK(st_begin(st, abmax, 1, &ok));
@@ -887,9 +769,6 @@ int sf_match_i8(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int
 }
 
 // ---- the streamed form (include/shotfpfh.h: sf_match_stream_*) ---------------------------------------------------------------------
-int sf_match_argmin_masked_generic(sf_ctx *ctx, const double *a, const double *b, int64_t m1, int64_t m2, int64_t d,
-                                   const unsigned char *a_ok, const unsigned char *b_ok, int64_t *idx, double *dist); // match.hip
-
 extern "C" sf_match_stream *sf_match_stream_begin(sf_ctx *ctx, const double *a_dev, const unsigned char *a_ok_dev, int64_t m1,
                                                   const double *b_dev, const unsigned char *b_ok_dev, int64_t m2, int64_t d,
                                                   double b_entry_max, int64_t max_ranges)
@@ -936,7 +815,9 @@ extern "C" int sf_match_stream_end(sf_ctx *ctx, sf_match_stream *st, int64_t *id
             // (most rows without a clear nearest descriptor: the one-shot paths for everything)
         }
     }
-    return sf_match_argmin_masked_generic(ctx, st->da, st->db, st->m1, st->m2, st->d, st->a_ok, st->b_ok, idx_dev, dist_dev);
+    // the resident, masked one-shot arg-min
+    return sf_match_argmin_multiscale(ctx, st->da, st->db, 1, st->m1, st->m2, st->d, st->a_ok, st->b_ok, INFINITY, idx_dev, dist_dev,
+                                      SF_IN_DEVICE | SF_OUT_DEVICE);
 }
 
 extern "C" void sf_match_stream_abort(sf_ctx *ctx, sf_match_stream *st)

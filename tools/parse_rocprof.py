@@ -25,7 +25,7 @@ SHORT = [
     ("k_radius<true>", "k2_radius_fill"), ("k_radius<false>", "k2_radius_count"), ("k_export_lists", "k2_export_lists"),
     ("k_radius", "k2_radius"), ("k_normals_max", "k1_normals_max"), ("k_pca_cov", "k3_normals"), ("k_pca_solve", "k3_normals"), ("k_normals", "k3_normals"), ("k_match_tile", "k8_match_tile"), ("k_ransac", "k9_ransac_score"),
     ("k_match_half", "k8_match_half"), ("k_half_convert", "k8_half_convert"), ("k_half_final", "k8_half_final"),
-    ("k_half_window", "k8_half_window"), ("k_half_max", "k8_half_max"), ("k_match_gemm", "k8_match_gemm"),
+    ("k_half_window", "k8_half_window"), ("k_match_max", "k8_match_max"), ("k_match_gemm", "k8_match_gemm"),
     ("k_match_decide", "k8_match_decide"), ("k_row_sqnorm", "k8_row_sqnorm"),
     ("k_gather_sorted", "k1_gather_sorted"), ("k_gather_normals", "k1_gather_normals"), ("k_count_stats", "k2_reduce"),
     ("k_layer_hist", "k1_layer_hist"), ("k_select_slab", "k1_select_slab"), ("k_extract_z", "k1_extract_z"), ("k_col_candidates", "k8_col_candidates"), ("k_lrf_eigen", "k4_lrf_eigen"), ("k_pca", "k3_pca"), ("k_cell_ids", "k1_cell_ids"), ("k_cell_start", "k1_cell_start"),
@@ -37,8 +37,8 @@ SHORT = [
 # round 4: second launches and selections (checked before the table above; template arguments as rocprofv3 prints them)
 SHORT_RE = [
     (r"k_i8_min", "k8_match_i8"), (r"k_i8_collect", "k8_i8_collect"), (r"k_i8_final", "k8_i8_final"), (r"k_i8_live|k_i8_place", "k8_i8_live"),
-    (r"k_i8_convert|k_i8_rowstat", "k8_i8_convert"), (r"k_i8_max", "k8_i8_max"), (r"k_i8_window", "k8_i8_window"),
-    (r"k_i8_gather_rows|k_half_gather_rows", "k8_gather_rows"), (r"k_i8_scatter|k_half_scatter", "k8_scatter_results"),
+    (r"k_i8_convert|k_i8_rowstat", "k8_i8_convert"), (r"k_i8_window", "k8_i8_window"),
+    (r"k_gather_rows", "k8_gather_rows"), (r"k_scatter_results", "k8_scatter_results"),
     (r"radix_sort", "rocprim_radix_sort"), (r"k_radius<2, ", "k2_radius_slots"), (r"k_radius<1, true>", "k2_radius_refill"), (r"k_radius<1, false>", "k2_radius_fill"),
     (r"k_radius<0, true>", "k2_sample"), (r"k_radius<0, false>", "k2_radius_count"), (r"k_iota_stride", "k2_sample"),
     (r"k_patch_offsets", "k2_select"), (r"select|partition", "rocprim_select"), (r"k_shot_long|k_shot_team", "k5_shot_tail"), (r"k_fpfh_mcl", "k7_fpfh_tail"),
