@@ -39,12 +39,14 @@ extern "C" {
 #define SF_ERR_COMM (-4)
 #define SF_ERR_STATE (-5)
 #define SF_ERR_UNSUPPORTED (-6)
+#define SF_ERR_BIN_RANGE (-7) /* sf_shot_serial_bins: a neighbour in cosine bin n (the reference's IndexError) */
 
 #define SF_HOST 0
 #define SF_OUT_DEVICE 1
 #define SF_IN_DEVICE 2
 
 #define SF_SHOT_LEN 352 /* 11 cosine x 8 azimuth x 2 elevation x 2 radial bins (shot.py:195) */
+#define SF_SHOT_MAX_COSINE_BINS 64 /* sf_shot_serial_bins: rows of up to 32 x 64 = 2048 bins */
 #define SF_FAST_FPFH_BINS 8 /* n_bins up to here: LDS-histogram K6 and the matrix-core / streaming K7 */
 #define SF_MAX_FPFH_BINS 1290 /* n_bins^3 must fit an int; the reference takes any n_bins (fpfh.py:16).  What bounds n_bins in
                                 practice is the table of n x n_bins^3 32-bit counts in HBM (the reference holds twice that in host RAM) */
@@ -203,6 +205,15 @@ int sf_azimuth_idx(sf_ctx *ctx, const double *x, const double *y, int64_t n, int
  * statements of sf_shot, and a row that is always L2-normalised (:496-497). */
 int sf_shot_serial(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, int64_t min_neighborhood_size, double *out /* m x 352 */,
                    int flags);
+/* sf_shot_serial with n_cosine_bins = n, the one bin count the reference lets a caller change (shot.py:316, 328): rows of 32 n
+ * bins, (cosine, azimuth, elevation, shell) in C order, the cosine bin rint((cosine + 1) n / 2 - 0.5) and its neighbour bin
+ * wrapped modulo n (:386-401).  1 <= n <= SF_SHOT_MAX_COSINE_BINS, else SF_ERR_ARG; every n, 11 included, runs K4 with the
+ * zero-distance neighbours left out and then a kernel of its own (shot_bins.hip), not K5.  Returns SF_ERR_BIN_RANGE when a
+ * neighbour of a keypoint that passes the gate has a clipped cosine of exactly +1 with n even (rint(n - 0.5) = n: the reference
+ * raises IndexError for the whole call); `out` is then undefined.  flags: SF_HOST, or SF_OUT_DEVICE with `out` on the device.
+ * The call waits for its kernels (it reads the range flag back). */
+int sf_shot_serial_bins(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, int64_t n_cosine_bins, int64_t min_neighborhood_size,
+                        double *out /* m x 32 n */, int flags);
 
 /* ---- a repeated step as ONE launch (HIP graph) -------------------------------------------------------------------------
  * sf_graph_begin .. sf_graph_end capture every device operation the calls in between issue on the context's streams (nothing

@@ -14,6 +14,8 @@ LIB_PATH = os.path.join(_HERE, "libshotfpfh.so")
 
 SF_HOST, SF_OUT_DEVICE, SF_IN_DEVICE = 0, 1, 2
 SHOT_LEN = 352
+MAX_COSINE_BINS = 64  # SF_SHOT_MAX_COSINE_BINS: sf_shot_serial_bins takes 1 .. 64 cosine bins (rows of 32 n)
+SF_ERR_BIN_RANGE = -7  # sf_shot_serial_bins: a neighbour in cosine bin n (the reference's IndexError)
 MAX_FPFH_BINS = 1290  # SF_MAX_FPFH_BINS: n_bins^3 fits an int (n_bins above 8 take the generic kernels; memory is the real bound)
 
 
@@ -72,6 +74,7 @@ SIGNATURES = {
     "sf_shot_single_scale": (_int, [_vp, _vp, _vp, _int, _i64, _vp, _vp, _int]),
     "sf_azimuth_idx": (_int, [_vp, _vp, _vp, _i64, _vp, _int]),
     "sf_shot_serial": (_int, [_vp, _vp, _vp, _i64, _vp, _int]),
+    "sf_shot_serial_bins": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int]),
     "sf_sync_count": (C.c_ulonglong, []),
     "sf_graph_begin": (_int, [_vp]),
     "sf_graph_end": (_vp, [_vp]),

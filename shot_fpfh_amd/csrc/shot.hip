@@ -9,6 +9,7 @@
 #include "common.h"
 #include "device_util.h"
 #include "host_stage.h"
+#include "shot_core.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 int sf_launch_shot_lrf(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int raw, int skip_zero, double *dlrf); // normals_lrf.hip
@@ -32,249 +33,14 @@ namespace {
 // One wave per keypoint: the register-cached form (k_shot_cached, 5.5 KB of LDS, two phases) takes every list of at most
 // 255 points, the streamed form (k_shot_long) the longer ones.
 // --------------------------------------------------------------------------------------------------
-#define SHOT_PI 3.141592653589793
-
-__device__ inline int azimuth_octant(double x, double y) // get_azimuth_idx, shot.py:51-70
-{
-    const bool a = (y > 0.0) || ((y == 0.0) && (x < 0.0));
-    const bool b = ((x > 0.0) || ((x == 0.0) && (y > 0.0))) != a;
-    const bool c = ((x * y > 0.0) || (x == 0.0)) ? (fabs(x) < fabs(y)) : (fabs(x) > fabs(y));
-    return 4 * (int)a + 2 * (int)b + (int)c;
-}
-
-// The same function for a whole wave with the special cases (a zero coordinate, |x| = |y|, a product that underflows)
-// moved behind a wave-uniform test: off them the three bits are two sign tests and one magnitude comparison.
-__device__ inline int azimuth_octant_wave(double x, double y)
-{
-    const double ax = fabs(x), ay = fabs(y);
-    const bool special = !(fmin(ax, ay) > 1e-150) || ax == ay; // (also catches NaN)
-    if (__ballot(special)) return azimuth_octant(x, y);
-    const bool a = y > 0.0, xp = x > 0.0, lt = ax < ay;
-    return 4 * (int)a + 2 * (int)(xp != a) + (int)(xp == a ? lt : !lt);
-}
+// (the helpers that do not depend on the number of cosine bins -- octant, roots, polynomials, weights, slot tags -- are in
+// shot_core.h, shared with the serial SHOT of any bin count, shot_bins.hip)
 
 // get_azimuth_idx as an elementwise function (shot.py:51-70): the very device function K5 bins with
 __global__ void k_azimuth_idx(const double *__restrict__ x, const double *__restrict__ y, int64_t n, int64_t *__restrict__ out)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = azimuth_octant(x[i], y[i]);
-}
-
-// A resolved slot holds the NEGATED value (values are >= 0, so the sign bit marks it); an unresolved key is
-// the bit pattern of rho > 0 and an empty slot is +0.  Decoding is therefore max(-x, 0): one instruction.
-__device__ inline unsigned long long tag_value(double v)
-{
-    return (unsigned long long)__double_as_longlong(v) | 0x8000000000000000ull;
-}
-
-__device__ inline double sf_dot3(double a0, double a1, double a2, double b0, double b1, double b2)
-{
-    return __builtin_fma(a2, b2, __builtin_fma(a1, b1, a0 * b0));
-}
-
-// --------------------------------------------------------------------------------------------------
-// K5, register-cached form for neighbourhoods of at most 64*NCH points (the common case; the streaming
-// kernel above stays as the fallback for larger ones).  The neighbour coordinates are gathered ONCE,
-// all NCH chunks in flight together; sweep 1 does the geometry (local coordinates, bins, rho) and keeps
-// the five numbers sweep 2 needs per neighbour in VGPRs, so sweep 2 is only the transcendental /
-// interpolation part.  The azimuth-neighbour decision in sweep 1 uses the sign of the cross product with
-// the octant's centre direction (no atan2); when that is not clearly non-zero it falls back to the
-// reference's own expression, so the decision equals shot.py:283-288 in every case.
-// --------------------------------------------------------------------------------------------------
-// sqrt(x) and 1/sqrt(x) together.  The root is ocml's own f64 sequence (v_rsq_f64 and three coupled Newton steps)
-// minus its exponent pre/post-scaling, which only matters outside [1e-290, 1e290]: bit-identical to sqrt() there
-// (tools/ubench/sqrt_check.hip: 0 differences in 1.6e7 inputs), 10 instructions instead of 22; the half-inverse
-// the iteration carries along, refined once more, is 1/sqrt(x) to ~1 ulp for two more instructions.
-__device__ inline void sf_sqrt_rsqrt(double x, double &root, double &inv)
-{
-    const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = 0.5 * y;
-    double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g);
-    h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    r = __builtin_fma(-h, g, 0.5);
-    h = __builtin_fma(h, r, h);
-    root = g;
-    inv = h + h;
-    // (wave-uniform, never taken for real clouds; the test is on the exponent -- 2^-964 <= x < 2^963, i.e. 4.6e-291 .. 7.8e289,
-    // positive, finite, not NaN -- one integer subtraction and comparison with 32-bit literals instead of two comparisons
-    // against 64-bit constants that each cost two scalar moves)
-    if (__ballot(!((unsigned)__double2hiint(x) - 0x03b00000u < 0x7c200000u - 0x03b00000u))) {
-        root = sqrt(x);
-        inv = 1.0 / root;
-    }
-}
-
-// The same pair for a WAVE-UNIFORM argument (the squared norm of a row: a sum of squares of weights, each 0 or >= 1e-19, so
-// either 0 or far inside the fast range): the range test is two scalar instructions on the exponent instead of two vector
-// comparisons against 64-bit literals (six vector instructions with their moves).
-__device__ inline void sf_sqrt_rsqrt_uniform(double x, double &root, double &inv)
-{
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane(__double2hiint(x));
-    if (hi - 0x03b00000u < 0x7c200000u - 0x03b00000u) { // 2^-964 <= x < 2^963, positive, finite
-        const double y = __builtin_amdgcn_rsq(x);
-        double g = x * y, h = 0.5 * y;
-        double r = __builtin_fma(-h, g, 0.5);
-        g = __builtin_fma(g, r, g);
-        h = __builtin_fma(h, r, h);
-        double d = __builtin_fma(-g, g, x);
-        g = __builtin_fma(d, h, g);
-        d = __builtin_fma(-g, g, x);
-        g = __builtin_fma(d, h, g);
-        r = __builtin_fma(-h, g, 0.5);
-        h = __builtin_fma(h, r, h);
-        root = g;
-        inv = h + h;
-    } else {
-        root = sqrt(x);
-        inv = 1.0 / root;
-    }
-}
-
-// ---- the frame of a fused SHOT kernel ---------------------------------------------------------------------------------
-// K4's raw mode leaves, in the frame's final row-major layout [x y z] per component, the largest / smallest eigenvectors as
-// returned (x, z) and y = cross(z, x) of THOSE.  The fused kernels count the sign votes (shot.py:40-45) from the neighbours they
-// have gathered anyway and flip: x and z by their own vote, y when exactly one of the two flipped (every product of the cross
-// product changes sign, so the rounded difference does too; a component that cancelled to zero stays +0, as -a + a does).  All of
-// it is wave-uniform: the nine numbers arrive by scalar loads and a flip is a scalar xor (y: plus one vector "+ 0").
-// (sign: 0 or the sign bit as a 64-bit mask, one scalar select per axis -- pinned, or the compiler distributes the select over
-// the components; a flip is then ONE 64-bit scalar xor per component)
-__device__ inline double shot_flip(double v, unsigned long long sign) { return __longlong_as_double(__double_as_longlong(v) ^ (long long)sign); }
-// raw: the nine raw numbers; E: the finished frame.  Returns whether anything changed (the caller writes E back if so).
-__device__ inline bool shot_finish_frame(const double (&raw)[9], int k, int xneg, int zneg, double (&E)[9])
-{
-    // coordinates are finite (checked at upload), so "not < 0" is ">= 0": flip when strictly more neighbours project negative
-    const bool fx = xneg > k - xneg, fz = zneg > k - zneg;
-    if (k == 0) { // shot.py:24-25
-        E[0] = 1.0; E[1] = 0.0; E[2] = 0.0; E[3] = 0.0; E[4] = 1.0; E[5] = 0.0; E[6] = 0.0; E[7] = 0.0; E[8] = 1.0;
-        return true;
-    }
-    unsigned long long sx = fx ? 0x8000000000000000ull : 0ull, sz = fz ? 0x8000000000000000ull : 0ull;
-    asm volatile("" : "+s"(sx), "+s"(sz));
-    const unsigned long long sy = sx ^ sz;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        E[3 * i + 0] = shot_flip(raw[3 * i + 0], sx);
-        // (-a + a is +0: a component of y that cancelled stays +0 when y flips -- what "flipped + 0.0" would do, as integer
-        // operations on the scalar unit: the vector add put y's three components into six vector registers for the whole
-        // kernel, the difference between five and six waves per SIMD for the fused four-chunk form)
-        unsigned long long yb = (unsigned long long)__double_as_longlong(raw[3 * i + 1]) ^ sy;
-        yb = (yb << 1) ? yb : 0ull;
-        E[3 * i + 1] = __longlong_as_double((long long)yb);
-        E[3 * i + 2] = shot_flip(raw[3 * i + 2], sz);
-    }
-    return fx | fz;
-}
-
-// Phase markers for tools/k5_phases.py (an ANALYSIS build only, -DSF_K5_MARK_BUILD: scheduling barriers + an assembler
-// comment; the shipped build compiles them to nothing): instruction counts per phase of the register-cached K5.
-#ifdef SF_K5_MARK_BUILD
-#define SF_K5_MARK(id, nch)                                                     \
-    do {                                                                        \
-        __builtin_amdgcn_sched_barrier(0);                                      \
-        asm volatile("; K5MARK %0 %1" ::"n"(id), "n"(nch));                     \
-        __builtin_amdgcn_sched_barrier(0);                                      \
-    } while (0)
-// (pure arithmetic sinks to its first use whatever barrier stands between: the values a phase produces are pinned in front
-// of the next mark)
-#define SF_K5_PIN(x) asm volatile("" : "+v"(x))
-#else
-#define SF_K5_MARK(id, nch) do { } while (0)
-#define SF_K5_PIN(x) (void)(x)
-#endif
-// ids: 1 header+clear, 2 gather, 3 frame votes, 4 gate, 5 geometry (sub: 50 sqrt/rsqrt, 51 local coords + cosine, 52 cosine bin,
-// 53 octant, 54 centre-ray cross/dot + neighbour octant, 55 lz/rho + packing), 6 election A (atomic max), 7 who-writes-what
-// (key reads), 8 weights (sub: 80 atan fraction, 81 radial shells, 82 acos, 83 elevation + sum), 9 A store (CAS), 10 S3/S4 S6/S7
-// adds, 11 S1 S9 elections + adds, 12 read-back + normalise + store
-
-struct shot_kept {
-    double rho, dc, tcross, tdot, lzr; // tcross / tdot: (lx, ly) against the octant's centre ray; lzr = lz / rho
-    unsigned bins0, bins1;            // base | bcos << 9 | bth << 18 ; bins1: bit 31 = valid, bits 28-30 = election flags
-};
-
-// ---- short double-precision helpers for sweep 2 (coefficients: tools/fit_poly.py) ------------------------
-// The interpolation weights are continuous in theta / phi, so these only have to be accurate, not
-// correctly rounded: each is within ~2e-16 (absolute) of the libm value the reference uses, far inside the
-// 1e-5 parity tolerance, at a quarter of the instruction count of ocml's atan2 / acos / sqrt / division.
-__device__ inline double sf_rcp(double d) { return sf_rcp_fast(d); } // v_rcp_f64 + 2 Newton steps, ~1 ulp
-
-__device__ inline double sf_sqrt_small(double x) // sqrt(x), 0 <= x <= 1/4, no denormal / huge handling
-{
-    const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = 0.5 * y;
-    const double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g);
-    h = __builtin_fma(h, r, h);
-    const double d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    return x > 0.0 ? g : 0.0;
-}
-
-
-// The two polynomials' coefficients live in device memory (a 26-double table the context owns, reached through a kernel argument)
-// and arrive by scalar loads -- sixteen dwords per instruction -- right where they are used.  As immediates every coefficient
-// costs two s_mov_b32 in front of its FMA (the instruction takes one scalar operand, and keeping 24 of them live across the
-// kernel is 48 scalar registers the kernel does not have): 96 scalar moves per keypoint, a quarter of its scalar instructions,
-// and the scalar stream is what holds the vector pipe back at seven waves per SIMD (tools/pmc_k5.sh: vector instructions
-// 783 -> 701 per keypoint bought nothing until the scalar ones followed).  (A __constant__ array with an initialiser is folded
-// back into immediates by the compiler.)
-#define SF_K_ATAN 1.2732395447351628  // 4 / pi
-#define SF_K_ACOS 0.6366197723675814  // 2 / pi
-#define SF_ATAN_TERMS 11
-#define SF_ACOS_TERMS 13
-#define SF_ACOS_AT 12 // (offset of the second table: both start on a 32-byte boundary)
-static const double SF_SHOT_COEF[SF_ACOS_AT + SF_ACOS_TERMS + 1] = {
-    // atan(t) / t / (pi/4) in s = t^2, highest power first
-    0.021102961440831885 * SF_K_ATAN, -0.04345403041920663 * SF_K_ATAN, 0.05687431322104835 * SF_K_ATAN, -0.06640058350060206 * SF_K_ATAN,
-    0.07689933264608774 * SF_K_ATAN,  -0.09090771637100807 * SF_K_ATAN, 0.11111106118508882 * SF_K_ATAN, -0.14285714179450393 * SF_K_ATAN,
-    0.19999999998836118 * SF_K_ATAN,  -0.33333333333328347 * SF_K_ATAN, SF_K_ATAN, 0.0,
-    // asin(r) / r / (pi/2) in s = r^2, highest power first
-    0.028169218060881414 * SF_K_ACOS, -0.010749050339697808 * SF_K_ACOS, 0.01603551434914882 * SF_K_ACOS, 0.0078029494773533175 * SF_K_ACOS,
-    0.011875494382636922 * SF_K_ACOS, 0.013929652902326633 * SF_K_ACOS,  0.017355259955786323 * SF_K_ACOS, 0.02237204763174451 * SF_K_ACOS,
-    0.03038194736709848 * SF_K_ACOS,  0.044642857103423646 * SF_K_ACOS,  0.07500000000020764 * SF_K_ACOS,  0.1666666666666665 * SF_K_ACOS,
-    SF_K_ACOS, 0.0};
-
-// atan(t) / (pi/4) for 0 <= t <= tan(pi/8) (1 + 1e-3): the minimax polynomial of tools/fit_poly.py with 4/pi folded into its
-// coefficients at compile time -- the azimuth weight is |dth| = angle / (pi/4), so the angle itself is never needed
-// (passing a loaded coefficient through an empty asm with a scalar-register constraint keeps it the FMA's scalar operand; left
-// alone the compiler selects the accumulate form v_fmac_f64, whose addend is the destination: two v_mov_b32 per coefficient)
-__device__ inline double sf_scalar_operand(double c)
-{
-    asm("" : "+s"(c));
-    return c;
-}
-typedef const __attribute__((address_space(4))) double *sf_const_doubles; // (read through the scalar cache: never written by a kernel)
-__device__ inline double sf_atan_octant_fraction(double t, const double *__restrict__ coef_)
-{
-    sf_const_doubles coef = (sf_const_doubles)coef_;
-    const double s = t * t;
-    double p = coef[0];
-#pragma unroll
-    for (int i = 1; i < SF_ATAN_TERMS; ++i) p = __builtin_fma(p, s, sf_scalar_operand(coef[i]));
-    return t * p;
-}
-
-// acos(|z|) / (pi/2) for |z| <= 1 (result in [0, 1]; |z| = 0 gives exactly 1, |z| = 1 exactly 0): the asin-form minimax
-// polynomial with 2/pi folded into its coefficients.  The elevation weights are linear in phi / (pi/2) and symmetric about
-// the equator -- acos(-z) = pi - acos(z) -- so the angle of |z| is all they need (shot_weights).
-__device__ inline double sf_acos_abs_quadrants(double az, const double *__restrict__ coef_)
-{
-    sf_const_doubles coef = (sf_const_doubles)coef_;
-    const bool big = az > 0.5;
-    const double xb = __builtin_fma(-0.5, az, 0.5), xs = az * az; // (1 - |z|) / 2 is exact
-    const double rb = sf_sqrt_small(fmin(xb, 0.25));
-    const double x = big ? xb : xs;
-    const double r = big ? rb : az;
-    double p = coef[SF_ACOS_AT]; // asin(r) = r + r s R(s), s = r^2 <= 1/4
-#pragma unroll
-    for (int i = 1; i < SF_ACOS_TERMS; ++i) p = __builtin_fma(p, x, sf_scalar_operand(coef[SF_ACOS_AT + i]));
-    const double as = r * p; // asin(r) / (pi/2)
-    // |z| <= 1/2: 1 - as ;  |z| > 1/2: 2 as
-    return big ? as + as : 1.0 - as;
 }
 
 __device__ inline void shot_geometry(double cx, double cy, double cz, double d2, double nx, double ny, double nz,
@@ -348,71 +114,6 @@ __device__ inline void shot_geometry(double cx, double cy, double cz, double d2,
     o.bins1 = 0x80000000u | (base & 3u); // (bits 0-1: shell and half-space, for the form that re-maps its slot numbers)
 }
 
-// Radius-derived constants of the interpolation, computed once on the host (as kernel arguments they live in SGPRs;
-// computed in the kernel the wave-uniform division 1 / (r/2) was a 14-instruction vector sequence per chunk)
-struct shot_consts {
-    double radius, half_r, q1, q3, inv_hr;
-    const double *coef; // SF_SHOT_COEF in device memory
-};
-
-// The interpolation weights of one neighbour (shot.py:73-171, 244-298), reduced to what the elections consume:
-//   vA   = S2 + S5 + S8 + S10 = (1 - |dc|) + current radial + current elevation + (1 - |dth|)
-//   v_cd = S3's `outer` if the neighbour is in the inner shell, S4's `inner` if in the outer one (the other is 0)
-//   v_ef = S6's `upper` if it is in the lower half space, S7's `lower` if in the upper one (the other is 0)
-//   adth = |dth| (S9's value; S1's is |dc|, already in g)
-// Written so that only the shell / half-space the neighbour is actually in gets evaluated: the centre of ITS bin is
-// selected first, the distance to that centre computed once.  theta and phi enter as fractions of their bin size
-// (sf_atan_octant_fraction, sf_acos_quadrants).  All weights are continuous in rho / phi / theta except at
-// rho = r/2 (decided on rho itself, as the reference does) and phi = pi/2 (decided by the sign of z inside the
-// reference's 1e-10 band), so last-bit differences of the short polynomial forms cannot flip a term.
-__device__ inline void shot_weights(const shot_kept &g, const shot_consts &k, double &vA, double &v_cd, double &v_ef, double &adth)
-{
-    const bool z_pos = g.bins1 & 2u; // lz > 0, decided in shot_geometry
-    const double rho = g.rho;
-    const double adc = fabs(g.dc);
-    // |dth|: angle off the octant's centre ray as a fraction of the octant, clipped to 1/2.  lx = ly = 0 has dot = 0:
-    // the reference's atan2(0, 0) = 0 sits 3.5 octants from octant 0's start -> 1/2.
-    SF_K5_MARK(80, 0);
-    const bool fwd = g.tdot > 0.0;
-    const double tq = fmin(fabs(g.tcross) * sf_rcp(fwd ? g.tdot : 1.0), 0.4146);
-    const double at = fmin(sf_atan_octant_fraction(tq, k.coef), 0.5);
-    adth = fwd ? at : 0.5;
-    SF_K5_PIN(adth);
-    // radial shells (interpolate_on_adjacent_husks): rho == r/2 belongs to neither and gets all three terms zero
-    // The two shells mirror each other about rho = r/2: with s = |rho - r/2| the distance to the current shell's centre
-    // is |s - r/4| and the distance "towards the other shell" (3r/4 - rho outside, rho - r/4 inside) is r/4 - s, in both.
-    SF_K5_MARK(81, 0);
-    const bool off_half = rho != k.half_r;
-    const double ds = fabs(rho - k.half_r) - k.q1;
-    const double cur = off_half ? 1.0 - fabs(ds) * k.inv_hr : 0.0;
-    v_cd = off_half ? fmax(-ds, 0.0) * k.inv_hr : 0.0;
-    { double curp = cur; SF_K5_PIN(curp); SF_K5_PIN(v_cd); }
-    // elevation (interpolate_vertical_volumes).  With u = phi / (pi/2) the reference's terms are
-    //   current = 1 - |u - 1/2| for phi < pi/2, 1 - |u - 3/2| for phi >= pi/2;
-    //   lower  = [phi < pi/2 and (not near or z > 0) and phi >= pi/4] (u - 1/2), counted for z > 0 writers;
-    //   upper  = [(phi > pi/2 or (near and z <= 0)) and phi <= 3pi/4] (3/2 - u), counted for z <= 0 writers
-    // (near: |phi - pi/2| < 1e-10).  phi = acos(z) is symmetric about the equator, u(-z) = 2 - u(z), so in terms of
-    // t = acos(|z|) / (pi/2) in [0, 1] all three are ONE expression per neighbour whatever the sign of z:
-    //   current = 1 - |t - 1/2| ;  lower resp. upper = max(t - 1/2, 0), with the single exception the masks leave:
-    //   a writer with z > 0 whose phi ROUNDS to pi/2 (t = 1 exactly) fails "phi < pi/2" and gets 0.
-    SF_K5_MARK(82, 0);
-    double t = sf_acos_abs_quadrants(fmin(fabs(g.lzr), 1.0), k.coef);
-    SF_K5_PIN(t);
-    SF_K5_MARK(83, 0);
-    const double curv = 1.0 - fabs(t - 0.5);
-    const bool side = !z_pos | (t < 1.0);
-    v_ef = side ? fmax(t - 0.5, 0.0) : 0.0;
-    vA = (((1.0 - adc) + cur) + curv) + (1.0 - adth);
-}
-
-// The waves of a K5 workgroup are independent (one keypoint and one LDS region each): what orders a wave's LDS phases is
-// the in-order execution of its own LDS instructions, so the "barrier" is a compiler fence, never an s_barrier.
-#define SF_SHOT_SYNC()                                                                                               \
-    do {                                                                                                            \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                      \
-        __builtin_amdgcn_wave_barrier();                                                                            \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                                      \
-    } while (0)
 #ifndef SF_SHOT_WPB
 #define SF_SHOT_WPB 2 // waves (= keypoints) per workgroup: 1.61 / 1.54 / 1.55 / 1.80 ms at C3 for 1 / 2 / 4 / 8
 #endif
@@ -912,8 +613,6 @@ struct shot_team_lds {
     double vx[352];                                      // S3/S4 + S6/S7 by destination bin (two addends at most: see below)
     __attribute__((aligned(16))) int red[16][4];         // per wave: gate count and the two sign votes
 };
-
-__device__ inline double shot_untag(unsigned long long x) { return fmax(-__longlong_as_double((long long)x), 0.0); }
 
 template <int NCH, int NW, bool FUSED>
 __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict__ rec, const double *__restrict__ qx,

@@ -9,6 +9,7 @@ must not be used across fork() -- and `n_procs` is kept as an inert field for si
 from __future__ import annotations
 
 import logging
+import operator
 from dataclasses import dataclass, field
 from types import TracebackType
 from typing import Optional, Sequence
@@ -18,6 +19,7 @@ import numpy.typing as npt
 
 from ..core import grid_subsampling
 from ..core.geometry import grid_subsampling_many
+from .._ffi import MAX_COSINE_BINS
 from ..engine import Cloud, Engine, default_engine
 
 __all__ = ["ShotMultiprocessor", "compute_shot_descriptor", "get_azimuth_idx"]
@@ -213,18 +215,44 @@ def compute_shot_descriptor(
     as ShotMultiprocessor's -- the frame of a keypoint is computed WITHOUT the keypoint itself (and without any
     duplicate of it) in the support (:361-363), and the rows are always normalised (:496-497).  One K2 search, K4 with
     the zero-distance neighbours left out, K5.  `debug_mode` only adds assertions / warnings in the reference and
-    `disable_progress_bars` a tqdm bar; both are accepted and have nothing to act on here."""
+    `disable_progress_bars` a tqdm bar; both are accepted and have nothing to act on here.
+
+    `n_cosine_bins` (the one bin count the reference lets a caller change, :328) gives (M, 32 n) rows: 11 takes the tuned
+    K5, every other count in 1 .. 64 a kernel with the bin count as an argument.  As in the reference, a count that is not an
+    integer raises TypeError and a negative one ValueError; 0 gives (M, 0) rows, or IndexError when some keypoint passes the
+    gate; an even count raises IndexError when a neighbour's clipped cosine is exactly +1 (its bin rounds to n).  Counts above
+    64 raise NotImplementedError."""
     assert n_azimuth_bins == 8, "Generic function for other than 8 azimuth divisions not implemented"
     assert n_elevation_bins == 2, "Generic function for other than 2 elevation divisions not implemented"
     assert n_radial_bins == 2, "Generic function for other than 2 radial divisions not implemented"
-    if n_cosine_bins != 11:
-        raise NotImplementedError("the device SHOT kernel has the 11 cosine bins of ShotMultiprocessor (352-bin rows)")
+    n = _cosine_bins(n_cosine_bins)
     cloud = Cloud(default_engine(), cloud_points, normals)
     try:
         nb = cloud.radius_search(keypoints, radius)
         try:
-            return nb.shot_serial(min_neighborhood_size)
+            if n == 11:
+                return nb.shot_serial(min_neighborhood_size)
+            if n == 0:
+                # the reference indexes a zero-length axis for any keypoint that passes the gate with a neighbour; at one bin
+                # exactly those keypoints have a non-zero row (the S2 weight 1 - |dc| of a neighbour is at least 1/2 there)
+                if np.any(nb.shot_serial(min_neighborhood_size, 1)):
+                    raise IndexError("index 0 is out of bounds for axis 0 with size 0 (n_cosine_bins = 0)")
+                return np.zeros((nb.m, 0))
+            return nb.shot_serial(min_neighborhood_size, n)
         finally:
             nb.free()
     finally:
         cloud.free()
+
+
+def _cosine_bins(n_cosine_bins) -> int:
+    """The checks compute_shot_descriptor makes of `n_cosine_bins` before any device work: an integer (TypeError, like the
+    reference's np.zeros), not negative (ValueError, the same), at most 64 (NotImplementedError: the device kernel's limit)."""
+    n = operator.index(n_cosine_bins)
+    if n < 0:
+        raise ValueError(f"negative dimensions are not allowed (n_cosine_bins = {n})")
+    if n > MAX_COSINE_BINS:
+        raise NotImplementedError(
+            f"n_cosine_bins = {n}: the device SHOT kernel takes at most {MAX_COSINE_BINS} cosine bins (rows of {32 * MAX_COSINE_BINS})"
+        )
+    return n

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import operator
 import os
 import threading
 import weakref
@@ -829,13 +830,36 @@ class Neighbors:
         )
         return res
 
-    def shot_serial(self, min_neighborhood_size: int = 10) -> np.ndarray:
-        """compute_shot_descriptor (shot.py:310-499): frames from the neighbours at non-zero distance, rows normalised."""
-        res = self.engine.host_empty((self.m, _ffi.SHOT_LEN))
-        _ffi.check(
-            self.engine.lib.sf_shot_serial(self.engine.h, self.cloud.h, self.h, int(min_neighborhood_size), _ptr(res), SF_HOST),
-            "sf_shot_serial",
-        )
+    def shot_serial(self, min_neighborhood_size: int = 10, n_cosine_bins: Optional[int] = None,
+                    out: Optional[DeviceArray] = None):
+        """compute_shot_descriptor (shot.py:310-499): frames from the neighbours at non-zero distance, rows normalised.
+        Without `n_cosine_bins`: the 11-bin rows of the tuned K5 (sf_shot_serial).  With it: (m, 32 n) rows of the kernel for
+        any bin count (sf_shot_serial_bins, 1 <= n <= 64 -- 11 included), on the host, or into `out` (a device array of
+        m x 32 n float64) when given.  A neighbour in cosine bin n (a clipped cosine of +1 with n even) raises IndexError, as
+        the reference does."""
+        if n_cosine_bins is None:
+            if out is not None:
+                raise ValueError("shot_serial: `out` needs n_cosine_bins")
+            res = self.engine.host_empty((self.m, _ffi.SHOT_LEN))
+            _ffi.check(
+                self.engine.lib.sf_shot_serial(self.engine.h, self.cloud.h, self.h, int(min_neighborhood_size), _ptr(res), SF_HOST),
+                "sf_shot_serial",
+            )
+            return res
+        n = operator.index(n_cosine_bins)
+        if not 1 <= n <= _ffi.MAX_COSINE_BINS:
+            raise ValueError(f"shot_serial: n_cosine_bins = {n} outside [1, {_ffi.MAX_COSINE_BINS}]")
+        if out is None:
+            res = self.engine.host_empty((self.m, 32 * n))
+            ptr, flags = _ptr(res), SF_HOST
+        else:
+            if out.nbytes < self.m * 32 * n * 8:
+                raise ValueError(f"shot_serial: `out` holds {out.nbytes} bytes, the rows need {self.m * 32 * n * 8}")
+            res, ptr, flags = out, out.ptr, SF_OUT_DEVICE
+        rc = self.engine.lib.sf_shot_serial_bins(self.engine.h, self.cloud.h, self.h, n, int(min_neighborhood_size), ptr, flags)
+        if rc == _ffi.SF_ERR_BIN_RANGE:
+            raise IndexError(_ffi.last_error())
+        _ffi.check(rc, "sf_shot_serial_bins")
         return res
 
     def shot_from_moments(self, moments: DeviceArray, first_row: int, normalize: bool, min_neighborhood_size: int,
