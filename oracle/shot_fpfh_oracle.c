@@ -924,10 +924,12 @@ static void spfh_row(const double *xyz, const double *normals, int64_t i, const 
         /* v = cross(c, u) (50); w = cross(u, v) (51) */
         double v[3] = {c[1] * u[2] - c[2] * u[1], c[2] * u[0] - c[0] * u[2], c[0] * u[1] - c[1] * u[0]};
         double w[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-        double alpha = (v[0] * nj[0] + v[1] * nj[1]) + v[2] * nj[2];          /* 52 */
-        double phi = ((c[0] * u[0] + c[1] * u[1]) + c[2] * u[2]) / dist;      /* 53 */
-        double theta = atan2((nj[0] * w[0] + nj[1] * w[1]) + nj[2] * w[2],    /* 54-57 */
-                             (nj[0] * u[0] + nj[1] * u[1]) + nj[2] * u[2]);
+        /* np.einsum("ij,ij->i") sums (x0 y0 + x2 y2) + x1 y1 from +0 (numpy 2.2); `.dot(u)` is a gemv whose rounding
+         * is OpenBLAS's: index order here, with a zero result +0 as a BLAS accumulator leaves it (FPFH) */
+        double alpha = ((v[0] * nj[0] + v[2] * nj[2]) + v[1] * nj[1]) + 0.0;  /* 52 */
+        double phi = (((c[0] * u[0] + c[1] * u[1]) + c[2] * u[2]) + 0.0) / dist; /* 53 */
+        double theta = atan2(((nj[0] * w[0] + nj[2] * w[2]) + nj[1] * w[1]) + 0.0, /* 54-57 */
+                             ((nj[0] * u[0] + nj[1] * u[1]) + nj[2] * u[2]) + 0.0);
         int ba = hist_bin(ea, n_bins, alpha), bp = hist_bin(ep, n_bins, phi), bt = hist_bin(et, n_bins, theta);
         if (ba < 0 || bp < 0 || bt < 0) continue;
         row[((int64_t)ba * n_bins + bp) * n_bins + bt] += 1.0;

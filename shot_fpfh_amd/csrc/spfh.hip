@@ -154,7 +154,9 @@ __global__ __launch_bounds__(64 * SF_SPFH_WPB) __attribute__((amdgpu_waves_per_e
     __builtin_amdgcn_wave_barrier();
     const double p_inv_width = ed.p_inv_width; // np.linspace edges: equal widths up to rounding
     // theta_bin_fast's margin: |a_fast - a_reference| <= ~24 eps |n_j| |u|^2 |c| (a dozen roundings on either side, each
-    // relative to a product of those norms); 64 eps max|n| |u|^2 per unit of |c| is the bound used
+    // relative to a product of those norms); 64 eps max|n| |u|^2 per unit of |c| is the bound used.  The reference's a is
+    // np.einsum's (n0 w0 + n2 w2) + n1 w1: two additions, each rounding by at most eps times the sum of |n_i w_i| <= |n_j| |w|
+    // <= |n_j| |u|^2 |c| -- the same bound as any other order of the three products, so the margin holds unchanged
     const double uu = (ux * ux + uy * uy) + uz * uz;
     const double e_per_dist = 1.5e-14 * nrm_max * uu;
     auto pair = [&](double cx, double cy, double cz, double njx, double njy, double njz) {
@@ -169,7 +171,11 @@ __global__ __launch_bounds__(64 * SF_SPFH_WPB) __attribute__((amdgpu_waves_per_e
             double phi = num * y1;
             const double pos = (phi - ed.p[0]) * p_inv_width;
             if (fabs(pos - rint(pos)) <= 1e-9) phi = num / sqrt(d2);
-            const double b = (njx * ux + njy * uy) + njz * uz;
+            // n_j . u: the reference's `.dot(u)` is a gemv -- index order here, and a zero result is +0 as a BLAS accumulator
+            // leaves it (atan2(+-0, -0) = +-pi would drop a pair the reference counts at theta = +-0).  fma(z, u, +0) is the
+            // rounded product with a zero made +0, so this is ((x + y) + z) + 0.0 without the extra add (equal unless the last
+            // product underflows to -0 with x + y = -0).  (c . u above needs none: the sign of a zero phi moves no bin.)
+            const double b = (njx * ux + njy * uy) + __builtin_fma(njz, uz, 0.0);
             // alpha = v . n_j with v = c x u NOT normalised (fpfh.py:60): |alpha| <= |c| |u| |n_j| <= radius when no normal
             // is longer than 1, so with the radius below the smallest |edge| of the alpha histogram every sample is in the
             // bin around 0 -- the host passes that bin (alpha_bin >= 0, wave-uniform) and alpha is never formed.  Then v and
@@ -187,18 +193,18 @@ __global__ __launch_bounds__(64 * SF_SPFH_WPB) __attribute__((amdgpu_waves_per_e
             if (!EVEN) {
                 if (bt == -2) { // the reference's own expressions (fpfh.py:58-66)
                     const double vx = cy * uz - cz * uy, vy = cz * ux - cx * uz, vz = cx * uy - cy * ux; // cross(c, u)
+                    if (alpha_bin < 0) ba = hist_bin(ed.a, nb, (vx * njx + vz * njz) + vy * njy); // np.einsum's order
                     const double wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx; // cross(u, v)
-                    bt = theta_bin(ed, nb, (njx * wx + njy * wy) + njz * wz, b);
-                    if (alpha_bin < 0) ba = hist_bin(ed.a, nb, (vx * njx + vy * njy) + vz * njz);
+                    bt = theta_bin(ed, nb, (njx * wx + njz * wz) + njy * wy, b); // (x0 y0 + x2 y2) + x1 y1
                 }
             } else if (bt == -2 || alpha_bin < 0) {
                 const double vx = cy * uz - cz * uy, vy = cz * ux - cx * uz, vz = cx * uy - cy * ux; // cross(c, u)
                 if (bt == -2) {
                     const double wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx; // cross(u, v)
-                    bt = theta_bin(ed, nb, (njx * wx + njy * wy) + njz * wz, b);
+                    bt = theta_bin(ed, nb, (njx * wx + njz * wz) + njy * wy, b); // np.einsum's order
                 }
                 if (alpha_bin < 0) {
-                    const double alpha = (vx * njx + vy * njy) + vz * njz;
+                    const double alpha = (vx * njx + vz * njz) + vy * njy; // np.einsum's order
                     ba = alpha_pair >= 0 ? alpha_pair + (alpha >= ed.a[alpha_pair + 1] ? 1 : 0) : hist_bin(ed.a, nb, alpha);
                 }
             }
@@ -422,9 +428,10 @@ __global__ __launch_bounds__(256) void k_spfh_generic(const double *__restrict__
         if (!(dist > 0.0)) continue;
         const double vx = cy * uz - cz * uy, vy = cz * ux - cx * uz, vz = cx * uy - cy * ux; // cross(c, u)  :50
         const double wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx; // cross(u, v)  :51
-        const double alpha = (vx * nx + vy * ny) + vz * nz;                                   // :52
-        const double phi = ((cx * ux + cy * uy) + cz * uz) / dist;                            // :53
-        const double theta = atan2((nx * wx + ny * wy) + nz * wz, (nx * ux + ny * uy) + nz * uz); // :54-57
+        // (np.einsum: (x0 y0 + x2 y2) + x1 y1; `.dot(u)`: index order, a zero result +0 as a BLAS accumulator leaves it)
+        const double alpha = (vx * nx + vz * nz) + vy * ny;                                         // :52
+        const double phi = (((cx * ux + cy * uy) + cz * uz) + 0.0) / dist;                          // :53
+        const double theta = atan2((nx * wx + nz * wz) + ny * wy, ((nx * ux + ny * uy) + nz * uz) + 0.0); // :54-57
         const int ba = hist_bin_search(ea, nb, alpha), bp = hist_bin_search(ep, nb, phi), bt = hist_bin_search(et, nb, theta);
         if (ba < 0 || bp < 0 || bt < 0) continue;
         atomicAdd(&row[(ba * nb + bp) * nb + bt], 1u);
