@@ -299,6 +299,13 @@ int sf_fpfh(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *self_nbrs, sf_spfh *spfh, con
  * (nullable, m2) = argmin over axis 0 (for the reciprocity test). */
 int sf_match_argmin(sf_ctx *ctx, const double *a, int64_t m1, const double *b, int64_t m2, int64_t d,
                     int64_t *idx, double *dist, int64_t *col_idx, int flags);
+/* Two nearest reference rows of every scan row: idx[2i], idx[2i+1] = j1, j2; dist (nullable) = d1, d2
+ * (j2 = -1, d2 = +inf when m2 == 1).  n_exact (nullable, host) = rows decided by the exact kernel.
+ * flags: SF_HOST, or SF_IN_DEVICE | SF_OUT_DEVICE with a, b, idx, dist on the device.
+ * Rows rank by (distance, column), the distance as in sf_match_argmin: j1, d1 are its idx, dist.  A non-finite entry of a or
+ * b is refused with SF_ERR_ARG, as is m2 == 0 with m1 > 0. */
+int sf_match_top2(sf_ctx *ctx, const double *a, int64_t m1, const double *b, int64_t m2, int64_t d,
+                  int64_t *idx, double *dist, int64_t *n_exact, int flags);
 
 /* Multi-scale ("minimum over scales") form of match_descriptors (matching.py:77-136).  a: n_scales x m1 x d,
  * b: n_scales x m2 x d; a_ok / b_ok: n_scales x m bytes, 1 where the row has a non-zero entry at that scale.

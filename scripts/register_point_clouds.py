@@ -39,7 +39,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--n-scales", type=int, default=2)
     p.add_argument("--no-support-subsampling", action="store_true")
     p.add_argument("--min-neighborhood-size", type=int, default=100)
-    p.add_argument("--matching", default="simple", choices=["simple", "double", "threshold"])
+    p.add_argument("--matching", default="simple", choices=["simple", "double", "threshold", "ratio"])
     p.add_argument("--reject-threshold", type=float, default=0.8), p.add_argument("--threshold-multiplier", type=float, default=10)
     p.add_argument("--ransac-draws", type=int, default=10000), p.add_argument("--ransac-draw-size", type=int, default=4)
     p.add_argument("--ransac-threshold", type=float, default=1.0)

@@ -366,6 +366,37 @@ class Engine:
             "sf_match_argmin",
         )
 
+    def match_top2(self, a, b):
+        """The two nearest rows of b for every row of a, ranked by (distance, row) with the distance of match_argmin:
+        idx (M1, 2) int64 (second column -1 when b has one row), dist (M1, 2) float64 (+inf there), and the number of rows
+        the exact kernel decided."""
+        a, b = _f64(a), _f64(b)
+        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+            raise ValueError("descriptor matrices must be 2-D with equal width")
+        m1, m2 = a.shape[0], b.shape[0]
+        idx, dist = np.zeros((m1, 2), dtype=np.int64), np.zeros((m1, 2), dtype=np.float64)
+        if m1 and not m2:
+            raise ValueError("attempt to get the nearest neighbours in an empty reference set")
+        if not (np.isfinite(a).all() and np.isfinite(b).all()):
+            raise ValueError("descriptor entries must be finite")
+        n_exact = C.c_int64(0)
+        if m1:
+            _ffi.check(self.lib.sf_match_top2(self.h, _ptr(a), m1, _ptr(b), m2, a.shape[1], _ptr(idx), _ptr(dist),
+                                              C.byref(n_exact), SF_HOST), "sf_match_top2")
+        return idx, dist, int(n_exact.value)
+
+    def match_top2_device(self, a: DeviceArray, b: DeviceArray, idx: DeviceArray, dist: Optional[DeviceArray] = None) -> int:
+        """Resident variant of match_top2: idx (M1, 2) int64 and dist (M1, 2) float64 stay on the device; returns the
+        number of rows the exact kernel decided.  A non-finite entry raises ShotFpfhError."""
+        m1, d = a.shape[0], a.shape[1]
+        if b.shape[1] != d or idx.shape != (m1, 2) or idx.dtype != np.int64 or (
+                dist is not None and (dist.shape != (m1, 2) or dist.dtype != np.float64)):
+            raise ValueError("match_top2_device: (M1, D) and (M2, D) float64 inputs, (M1, 2) int64 / float64 outputs expected")
+        n_exact = C.c_int64(0)
+        _ffi.check(self.lib.sf_match_top2(self.h, a.ptr, m1, b.ptr, b.shape[0], d, idx.ptr, None if dist is None else dist.ptr,
+                                          C.byref(n_exact), SF_IN_DEVICE | SF_OUT_DEVICE), "sf_match_top2")
+        return int(n_exact.value)
+
     def match_argmin_multiscale(self, a, b, max_val: float = 1000.0):
         """a: (S, M1, D), b: (S, M2, D).  Arg-min over j of min over scales of the per-scale distance, with
         max_val wherever either descriptor is all-zero at that scale (matching.py:77-136)."""

@@ -1,9 +1,10 @@
 """Descriptor matching on the GPU -- drop-ins for shot_fpfh.matching.basic_matching and the 2-D
-(Euclidean) branch of match_descriptors (matching.py:39-74, 138-169).
+(Euclidean) branch of match_descriptors (matching.py:39-74, 138-169), and the ratio test.
 
 The M1 x M2 distance matrix of the reference (scipy cdist, 8 TB at 1M x 1M) is never formed: kernel
 K8 returns, per scan descriptor, the first arg-min over the reference descriptors and its distance,
-and per reference descriptor the arg-min over the scan side for the reciprocity test.
+and per reference descriptor the arg-min over the scan side for the reciprocity test.  Its top-2 form
+(sf_match_top2) returns the two nearest reference descriptors, which the ratio test needs.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ import numpy.typing as npt
 
 from ..engine import Engine, default_engine
 
-__all__ = ["basic_matching", "match_descriptors", "double_matching_with_rejects"]
+__all__ = ["basic_matching", "match_descriptors", "double_matching_with_rejects", "match_two_nearest", "ratio_test_matching"]
 
 
 def _non_empty_rows(desc: np.ndarray) -> np.ndarray:
@@ -120,3 +121,50 @@ def double_matching_with_rejects(scan_descriptors, ref_descriptors, threshold, v
     if shape[0] != s:  # np.divide(..., out=np.ones(S)), :204-209
         raise ValueError(f"non-broadcastable output operand with shape ({s},) doesn't match the broadcast shape ({shape[0]},)")
     raise IndexError("arrays used as indices must be of integer (or boolean) type")  # :220
+
+
+def match_two_nearest(
+    scan_descriptors: npt.NDArray[np.float64],
+    ref_descriptors: npt.NDArray[np.float64],
+    *,
+    engine: Optional[Engine] = None,
+) -> tuple[npt.NDArray[np.int64], npt.NDArray[np.int64], npt.NDArray[np.float64]]:
+    """The two nearest reference descriptors of every non-empty scan descriptor.
+
+    Returns (scan rows (k,), ref rows (k, 2), distances (k, 2)) in the original row numbering.  All-zero rows are skipped on
+    both sides, as in basic_matching.  Reference rows rank by (Euclidean distance, row): column 0 is basic_matching's match,
+    and duplicated reference rows come out at equal distances in ascending row order.  With a single non-empty reference
+    row the second match is -1 at distance +inf."""
+    eng = engine or default_engine()
+    scan_rows, ref_rows = _non_empty_rows(scan_descriptors), _non_empty_rows(ref_descriptors)
+    idx, dist, _ = eng.match_top2(np.asarray(scan_descriptors)[scan_rows], np.asarray(ref_descriptors)[ref_rows])
+    ref_idx = np.full(idx.shape, -1, dtype=np.int64)
+    found = idx >= 0
+    ref_idx[found] = ref_rows[idx[found]]
+    return scan_rows, ref_idx, dist
+
+
+def ratio_test_matching(
+    scan_descriptors: npt.NDArray[np.float64],
+    ref_descriptors: npt.NDArray[np.float64],
+    ratio: float = 0.8,
+    verbose: bool = True,
+    *,
+    engine: Optional[Engine] = None,
+) -> tuple[npt.NDArray[np.int64], npt.NDArray[np.int64]]:
+    """Nearest-neighbour matches that pass Lowe's ratio test: a scan descriptor is kept iff d1 < ratio * d2 (float64, strict),
+    d1 and d2 being the distances to its nearest and second-nearest reference descriptors (match_two_nearest).
+
+    `ratio` must satisfy 0 < ratio <= 1 (ValueError otherwise).  A scan descriptor with a single reference candidate
+    (d2 = +inf) is kept; one with d1 == d2 -- duplicated reference descriptors, or two at distance 0 -- is rejected.
+
+    This is what the reference's double_matching_with_rejects (matching.py:172-221) is meant to do, but that function always
+    raises, and its mask keeps d1 / d2 >= threshold: exactly the ambiguous matches its docstring says to reject.  There is no
+    behaviour to copy, so this follows Lowe's convention.  Returns (scan row indices, ref row indices) like match_descriptors."""
+    if not (0.0 < ratio <= 1.0):
+        raise ValueError(f"the ratio must satisfy 0 < ratio <= 1, got {ratio!r}")
+    scan_rows, ref_idx, dist = match_two_nearest(scan_descriptors, ref_descriptors, engine=engine)
+    keep = dist[:, 0] < np.float64(ratio) * dist[:, 1]
+    if verbose:
+        logging.info(f"Kept {keep.sum()} matches out of {np.shape(scan_descriptors)[0]} descriptors.")
+    return scan_rows[keep], ref_idx[keep, 0]

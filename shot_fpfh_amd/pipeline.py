@@ -25,6 +25,7 @@ from .matching import (
     double_matching_with_rejects,
     match_descriptors,
     ransac_on_matches,
+    ratio_test_matching,
     threshold_filter,
 )
 
@@ -152,7 +153,7 @@ class RegistrationPipeline:
     # ---- stage 3: matching (pipeline.py:351-412) -------------------------------------------------------------
     def find_descriptors_matches(
         self,
-        matching_algorithm: Literal["simple", "double", "threshold"],
+        matching_algorithm: Literal["simple", "double", "threshold", "ratio"],
         *,
         reject_threshold: float,
         threshold_multiplier: float,
@@ -164,6 +165,8 @@ class RegistrationPipeline:
             "double": lambda: double_matching_with_rejects(self.scan_descriptors, self.ref_descriptors, reject_threshold),
             "threshold": lambda: match_descriptors(self.scan_descriptors, self.ref_descriptors, threshold_filter,
                                                    threshold_multiplier=threshold_multiplier),
+            # Lowe's ratio test with reject_threshold as the ratio (what "double" is meant to do; the reference's raises)
+            "ratio": lambda: ratio_test_matching(self.scan_descriptors, self.ref_descriptors, reject_threshold),
         }.get(matching_algorithm)
         if run is None:
             raise ValueError("Incorrect matching algorithm selection.")
