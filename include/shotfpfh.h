@@ -151,7 +151,9 @@ sf_nbrs *sf_knn_search(sf_ctx *ctx, sf_cloud *cloud, const double *queries, int6
  * SF_ERR_STATE otherwise). */
 sf_nbrs *sf_nbrs_import(sf_ctx *ctx, sf_cloud *cloud, const double *queries, int64_t m, const int64_t *offsets,
                         const int64_t *idx, double radius, int flags);
-/* non-owning view of queries [first, first+count) of `nbrs` (free it before the parent) */
+/* non-owning view of queries [first, first+count) of `nbrs` (free it before the parent).  sf_nbrs_total of a view is -1;
+ * sf_nbrs_export serves a view of a self search (a first call with idx == NULL returns the offsets: offsets[count] sizes idx
+ * and dist), which is how a sample of a search too large for the host is read. */
 sf_nbrs *sf_nbrs_slice(sf_ctx *ctx, sf_nbrs *nbrs, int64_t first, int64_t count);
 int64_t sf_nbrs_num_queries(const sf_nbrs *nbrs);
 int64_t sf_nbrs_total(const sf_nbrs *nbrs);

@@ -1222,10 +1222,13 @@ extern "C" int sf_nbrs_export(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int64_t *of
     // only orders each list by ascending index and the rows by the caller's query order.  For a self search
     // row i is the point at cell-sorted position self_begin + i.
     if (!ctx || !c || !nb || !offsets) { sf_set_error("sf_nbrs_export: null argument"); return SF_ERR_ARG; }
-    if (nb->view) { sf_set_error("sf_nbrs_export: not available on a slice view"); return SF_ERR_ARG; }
+    // (a slice view of a self search exports its own rows -- a sample of a search too large to leave the device whole; the rows
+    // of a coordinate-query search are in the caller's order, which a range of sorted queries is not)
+    if (nb->view && nb->qrow) { sf_set_error("sf_nbrs_export: a slice view of a coordinate-query search has no rows of its own"); return SF_ERR_ARG; }
     SF_CHECK(sf_nbrs_on_grid(nb, c, "sf_nbrs_export"));
     SF_HIP(hipSetDevice(ctx->device));
-    const int64_t m = nb->m, total = nb->total;
+    const int64_t m = nb->m;
+    int64_t total = nb->total;
     std::vector<int32_t> cnt((size_t)m + 1), qrow;
     SF_HIP(hipMemcpyAsync(cnt.data(), nb->count, (size_t)(m + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (nb->qrow && m) {
@@ -1242,6 +1245,7 @@ extern "C" int sf_nbrs_export(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int64_t *of
     offsets[0] = 0;
     for (int64_t r = 0; r < m; ++r) offsets[r + 1] = offsets[r] + cnt[(size_t)slot_of_row[(size_t)r]];
     if (!idx) return SF_OK;
+    if (nb->view) total = eoff[(size_t)m]; // (a view does not know its total: offsets[m] of a first call with idx == NULL sizes idx / dist)
     if (eoff[(size_t)m] != total) { sf_set_error("sf_nbrs_export: inconsistent counts"); return SF_ERR_STATE; }
     int64_t *d_eoff = nullptr;
     int32_t *d_idx = nullptr;

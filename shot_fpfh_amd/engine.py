@@ -764,7 +764,10 @@ class Neighbors:
 
     def export(self, return_distance: bool = False):
         """(offsets[m+1], idx[total]) with ascending original indices inside each list
-        [+ dist[total] = sqrt(d2)], the canonical form of KDTree.query_radius's output."""
+        [+ dist[total] = sqrt(d2)], the canonical form of KDTree.query_radius's output.  On a slice view of a self search:
+        the lists of its queries alone (a sample of a search too large to leave the device whole)."""
+        if self.total < 0:  # (a view learns its total from its counts)
+            self.total = int(self.counts().sum())
         off = np.zeros(self.m + 1, dtype=np.int64)
         idx = np.zeros(max(self.total, 1), dtype=np.int32)
         dist = np.zeros(max(self.total, 1), dtype=np.float64) if return_distance else None
