@@ -1,5 +1,6 @@
-// match.h -- internal to K8 (match.hip, match_gemm.hip, match_half.hip, match_i8.hip): the entry points these files call
-// across each other, the flagged-row rescue they share, and their common device helpers.  Not part of include/shotfpfh.h.
+// match.h -- internal to K8 (match.hip, match_gemm.hip, match_half.hip, match_i8.hip, match_top2.hip): the entry points these
+// files call across each other, the flagged-row rescue, the split and size rules they share, and their common device helpers.
+// Not part of include/shotfpfh.h.  (The main loops of the float64 kernels: match_mainloop.h.)
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -14,6 +15,8 @@ int sf_match_exact(sf_ctx *ctx, const double *da, int64_t m1, const double *db, 
 // match_gemm.hip: the matrix-core paths behind one size-based choice; *n_slow = rows that went to the next slower path
 int sf_match_gemm(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
                   double *ddist, const char *name, int64_t *n_slow, const unsigned char *a_ok, const unsigned char *b_ok);
+// out[i] = ||rows[i]||^2, or +inf where ok (nullable) is 0: such a row stays out of every arg-min without touching the GEMM
+int sf_match_sqnorm(sf_ctx *ctx, const char *name, const double *rows, int64_t m, int64_t d, const unsigned char *ok, double *out);
 int sf_match_gemm_f64(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
                       double *ddist, const char *name, int64_t *n_slow, const unsigned char *a_ok, const unsigned char *b_ok);
 // match_half.hip, match_i8.hip: the pre-filters; *used = 0 (nothing the caller relies on written) when the input does not suit
@@ -30,13 +33,32 @@ int sf_match_i8(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int
 // ---- host helpers (match.hip) ----------------------------------------------------------------------------------------------------
 // The rows a path could not decide (flag[i] != 0, nf of them among the m1 rows of da) through the next slower path:
 // next(sub, nr, sidx, sdist) matches the nr gathered rows `sub` and writes their results to sidx / sdist, which are then
-// scattered back into didx / ddist.  *n_slow = nr.
+// scattered back into didx / ddist.  *n_slow = nr.  per_row results per row (1: arg-min, 2: top-2) in all four arrays; the last
+// two arguments are the names of the gather and the scatter in the engine's profile.
 typedef std::function<int(const double *sub, int64_t nr, int64_t *sidx, double *sdist)> sf_match_next;
 int sf_match_rescue(sf_ctx *ctx, const double *da, int64_t m1, int64_t d, const int *flag, int nf, const sf_match_next &next,
-                    int64_t *didx, double *ddist, int64_t *n_slow);
+                    int64_t *didx, double *ddist, int64_t *n_slow, int per_row = 1, const char *gather_name = "k8_gather_rows",
+                    const char *scatter_name = "k8_scatter_results");
 // max over i < n of v[i] >= 0 (+inf when an entry is non-finite or negative, so that the caller can refuse it) -> *out (host);
 // part: 256 doubles of device scratch
 int sf_match_max(sf_ctx *ctx, const char *name, const double *v, int64_t n, double *part, double *out);
+
+// The size rule of the float64 paths: below it the fixed costs of the matrix-core path dominate and the exact tile kernel runs
+static inline bool sf_match_small(int64_t m1, int64_t m2, int64_t d)
+{
+    return (double)m1 * (double)m2 * (double)d < 5e8 || m2 < 256;
+}
+
+// Column splits of a float64 kernel's grid (row_tiles x splits workgroups, the second grid dimension): with fewer than `target`
+// row tiles the columns are split until about `target` workgroups exist.  Returns the count, every split non-empty.
+static inline int64_t sf_match_col_splits(int64_t row_tiles, int64_t col_tiles, int64_t target, int64_t *tiles_per_split)
+{
+    int64_t nsplit = 1;
+    if (row_tiles < target) nsplit = std::min<int64_t>(col_tiles, sf_div_up(target, row_tiles));
+    if (nsplit > 65535) nsplit = 65535;
+    *tiles_per_split = sf_div_up(col_tiles, nsplit);
+    return sf_div_up(col_tiles, *tiles_per_split);
+}
 
 // Column splits of a pre-filter pass (tile_bytes: one 64-column tile of the reference image): (1) each split is short enough for
 // an XCD's workgroups to share its tiles through their L2 (8 MB: hit rate 0.83 against 0.90 / 0.89 at 2 / 4 MB with fewer lists
@@ -68,6 +90,13 @@ template <int CTRL>
 __device__ __forceinline__ double sf_dpp(double v)
 {
     return __hiloint2double(sf_dpp<CTRL>(__double2hiint(v)), sf_dpp<CTRL>(__double2loint(v)));
+}
+
+// The gap between a row's keys above which their order is the reference's whatever the rounding (match_gemm.hip, "Exactness"):
+// 8 d eps (||a_i||^2 + max_j ||b_j||^2)
+__device__ __forceinline__ double sf_match_tol(int64_t d, double na, double nb_max)
+{
+    return 8.0 * (double)d * 1.1102230246251565e-16 * (na + nb_max);
 }
 
 // The float64 re-check of a pre-filter's candidates (k_half_final, k_i8_final): a scan row's best column so far, its reference

@@ -14,10 +14,9 @@
 
 #include "device_util.h"
 #include "match.h"
+#include "match_mainloop.h"
 
 namespace {
-
-constexpr int TM = 64, TN = 64, TK = 16;
 
 // n_scales == 1, masks null: plain cdist + argmin.  Otherwise the "minimum over scales" distance of
 // matching.py:77-136: dist(i,j) = min over scales s of (a_ok[s][i] && b_ok[s][j] ? ||a_s[i] - b_s[j]|| : max_val),
@@ -34,9 +33,8 @@ __global__ __launch_bounds__(256) void k_match_tile(const double *__restrict__ a
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int64_t i0 = (int64_t)blockIdx.x * TM;
     const int split = blockIdx.y;
-    const int64_t ntiles = (m2 + TN - 1) / TN;
-    const int64_t jt0 = (int64_t)split * tiles_per_split;
-    const int64_t jt1 = jt0 + tiles_per_split < ntiles ? jt0 + tiles_per_split : ntiles;
+    int64_t jt0, jt1;
+    sf_split_tiles(m2, TN, tiles_per_split, jt0, jt1);
     double best[4];
     int64_t bidx[4];
 #pragma unroll
@@ -50,38 +48,8 @@ __global__ __launch_bounds__(256) void k_match_tile(const double *__restrict__ a
 #pragma unroll
             for (int v = 0; v < 4; ++v) dmin[u][v] = a_ok ? max_val : INFINITY;
         for (int sc = 0; sc < n_scales; ++sc) {
-            const double *as = a + (int64_t)sc * m1 * d, *bs = b + (int64_t)sc * m2 * d;
             double acc[4][4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
-            for (int64_t t0 = 0; t0 < d; t0 += TK) {
-                // stage TM x TK of a and TN x TK of b (zero padded); 1024 elements each, 4 per thread
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int lin = tid + 256 * e; // 0..1023
-                    const int r = lin >> 4, cc = lin & 15;
-                    const int64_t t = t0 + cc;
-                    As[cc][r] = (i0 + r < m1 && t < d) ? as[(i0 + r) * d + t] : 0.0;
-                    Bs[cc][r] = (j0 + r < m2 && t < d) ? bs[(j0 + r) * d + t] : 0.0;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int t = 0; t < TK; ++t) {
-                    double av[4], bv[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) { av[u] = As[t][ty * 4 + u]; bv[u] = Bs[t][tx * 4 + u]; }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) {
-                            const double df = av[u] - bv[v];
-                            acc[u][v] += df * df;
-                        }
-                }
-                __syncthreads();
-            }
+            sf_tile_sqdist(As, Bs, a + (int64_t)sc * m1 * d, m1, i0, b + (int64_t)sc * m2 * d, m2, j0, d, acc);
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -264,11 +232,8 @@ static int match_one_way(sf_ctx *ctx, const double *da, int64_t m1, const double
                          const unsigned char *a_ok = nullptr, const unsigned char *b_ok = nullptr, double max_val = 0.0)
 {
     const int64_t row_tiles = sf_div_up(m1, TM), col_tiles = sf_div_up(m2, TN);
-    int64_t nsplit = 1;
-    if (row_tiles < 2048) nsplit = std::min<int64_t>(col_tiles, sf_div_up(2048, row_tiles));
-    if (nsplit > 65535) nsplit = 65535;
-    const int64_t tiles_per_split = sf_div_up(col_tiles, nsplit);
-    nsplit = sf_div_up(col_tiles, tiles_per_split);
+    int64_t tiles_per_split = 0;
+    const int64_t nsplit = sf_match_col_splits(row_tiles, col_tiles, 2048, &tiles_per_split);
     sf_pool_guard tmp(ctx); // stream-ordered release: safe to reuse by later launches on this stream
     double *pdist = nullptr;
     int64_t *pidx = nullptr;
@@ -302,8 +267,7 @@ static int match_dispatch(sf_ctx *ctx, const double *da, int64_t m1, const doubl
                           int64_t *didx, double *ddist, const char *name_exact, const char *name_gemm)
 {
     static const bool force_exact = getenv("SF_MATCH_EXACT") && getenv("SF_MATCH_EXACT")[0] == '1';
-    const double work = (double)m1 * (double)m2 * (double)d;
-    if (force_exact || work < 5e8 || m2 < 256) return match_one_way(ctx, da, m1, db, m2, d, didx, ddist, name_exact);
+    if (force_exact || sf_match_small(m1, m2, d)) return match_one_way(ctx, da, m1, db, m2, d, didx, ddist, name_exact);
     return sf_match_gemm(ctx, da, m1, db, m2, d, didx, ddist, name_gemm, nullptr, nullptr, nullptr);
 }
 
@@ -407,8 +371,7 @@ static int match_multiscale_fast(sf_ctx *ctx, const double *a, const double *b, 
 {
     *done = false;
     const char *fe = getenv("SF_MATCH_EXACT");
-    const double work = (double)m1 * (double)m2 * (double)d;
-    if ((fe && fe[0] == '1') || n_scales < 2 || work < 5e8 || m2 < 256 || !(max_val > 0.0) || std::isinf(max_val)) return SF_OK;
+    if ((fe && fe[0] == '1') || n_scales < 2 || sf_match_small(m1, m2, d) || !(max_val > 0.0) || std::isinf(max_val)) return SF_OK;
     sf_pool_guard tmp(ctx);
     int64_t *idx_s = nullptr;
     double *dist_s = nullptr;
@@ -443,8 +406,7 @@ extern "C" int sf_match_argmin_multiscale(sf_ctx *ctx, const double *a, const do
     if (flags == (SF_IN_DEVICE | SF_OUT_DEVICE)) { // everything resident: no copies
         if (!m1) return SF_OK;
         static const bool force_exact = getenv("SF_MATCH_EXACT") && getenv("SF_MATCH_EXACT")[0] == '1';
-        const double work = (double)m1 * (double)m2 * (double)d;
-        if (n_scales == 1 && std::isinf(max_val) && max_val > 0 && !force_exact && work >= 5e8 && m2 >= 256)
+        if (n_scales == 1 && std::isinf(max_val) && max_val > 0 && !force_exact && !sf_match_small(m1, m2, d))
             // single scale, masked rows at +inf: the matrix-core path with ||b_j||^2 = +inf for masked reference rows
             return sf_match_gemm(ctx, a, m1, b, m2, d, idx, dist, "k8_match_gemm", nullptr, a_ok, b_ok);
         bool done = false;
@@ -579,13 +541,17 @@ __global__ void k_gather_rows(const double *__restrict__ a, int64_t d, const int
     out[g] = a[rows[r] * d + t];
 }
 
-__global__ void k_scatter_results(const int64_t *__restrict__ rows, int64_t nr, const int64_t *__restrict__ sidx,
+// per_row results of gathered row g -> those of row rows[g]
+__global__ void k_scatter_results(const int64_t *__restrict__ rows, int64_t nr, int per_row, const int64_t *__restrict__ sidx,
                                   const double *__restrict__ sdist, int64_t *__restrict__ idx, double *__restrict__ dist)
 {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= nr) return;
-    idx[rows[g]] = sidx[g];
-    if (dist) dist[rows[g]] = sdist[g];
+    const int64_t i = rows[g];
+    for (int q = 0; q < per_row; ++q) {
+        idx[per_row * i + q] = sidx[per_row * g + q];
+        if (dist) dist[per_row * i + q] = sdist[per_row * g + q];
+    }
 }
 
 // max over i of v[i] (v >= 0; non-finite entries propagate so that the host can refuse them) -> partial[blockIdx]
@@ -608,7 +574,7 @@ __global__ void k_match_max(const double *__restrict__ v, int64_t n, double *__r
 } // namespace
 
 int sf_match_rescue(sf_ctx *ctx, const double *da, int64_t m1, int64_t d, const int *flag, int nf, const sf_match_next &next,
-                    int64_t *didx, double *ddist, int64_t *n_slow)
+                    int64_t *didx, double *ddist, int64_t *n_slow, int per_row, const char *gather_name, const char *scatter_name)
 {
     if (n_slow) *n_slow = 0;
     if (nf <= 0) return SF_OK;
@@ -625,16 +591,16 @@ int sf_match_rescue(sf_ctx *ctx, const double *da, int64_t m1, int64_t d, const 
     int64_t *drows = nullptr, *sidx = nullptr;
     double *sub = nullptr, *sdist = nullptr;
     SF_CHECK(tmp.alloc(&drows, (size_t)nr));
-    SF_CHECK(tmp.alloc(&sidx, (size_t)nr));
-    SF_CHECK(tmp.alloc(&sdist, (size_t)nr));
+    SF_CHECK(tmp.alloc(&sidx, (size_t)(per_row * nr)));
+    SF_CHECK(tmp.alloc(&sdist, (size_t)(per_row * nr)));
     SF_CHECK(tmp.alloc(&sub, (size_t)(nr * d)));
     SF_HIP(hipMemcpyAsync(drows, rows.data(), (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream)); // rows.data() is a host buffer: the copy is done before any return below
-    SF_LAUNCH(ctx, "k8_gather_rows", k_gather_rows, dim3((unsigned)sf_div_up(nr * d, 256)), dim3(256), da, d,
+    SF_LAUNCH(ctx, gather_name, k_gather_rows, dim3((unsigned)sf_div_up(nr * d, 256)), dim3(256), da, d,
               (const int64_t *)drows, nr, sub);
     SF_CHECK(next(sub, nr, sidx, sdist));
-    SF_LAUNCH(ctx, "k8_scatter_results", k_scatter_results, dim3((unsigned)sf_div_up(nr, 256)), dim3(256),
-              (const int64_t *)drows, nr, (const int64_t *)sidx, (const double *)sdist, didx, ddist);
+    SF_LAUNCH(ctx, scatter_name, k_scatter_results, dim3((unsigned)sf_div_up(nr, 256)), dim3(256),
+              (const int64_t *)drows, nr, per_row, (const int64_t *)sidx, (const double *)sdist, didx, ddist);
     return SF_OK;
 }
 

@@ -24,13 +24,9 @@
 
 #include "device_util.h"
 #include "match.h"
+#include "match_mainloop.h"
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-constexpr int GM = 128, GN = 128, GK = 16;
-// LDS tiles are row-major [row][k], 16 doubles per row, columns swizzled by sw() (see there).
-constexpr int LDS_P = 16; // no padding: bank conflicts are avoided by the XOR swizzle sw() below
 
 // ||row||^2; rows whose mask is 0 (all-zero descriptors that must never be matched) get +inf, which keeps them
 // out of every arg-min without touching the GEMM
@@ -74,15 +70,10 @@ __device__ inline void top2_merge(top2 &t, double om1, double om2, int64_t oj1)
     else t.m2 = fmin(t.m2, om1); // om1 >= t.m1 (ties land here: m2 = m1)
 }
 
-// VEC: the descriptor length is even and both matrices are 16-byte aligned -> a stage is fetched with 16-byte
-// loads, eight lanes per 128-byte row segment (8 cache lines per wave instruction instead of 64).
-// LDS column swizzle: a tile row holds GK = 16 doubles = four 32-byte groups; row r stores group g at slot
-// g ^ (r & 3).  An MFMA fragment read (16 consecutive rows x the 4 k of one group, 8 bytes per lane) then touches
-// every bank exactly once per 16 lanes -- the minimum of four passes per wave read -- where the padded layout
-// (pitch 18) had rows r and r + 8 and neighbouring k colliding; and without padding the tile pair is 64 KB, so
-// two workgroups fit a CU's LDS.
-__device__ __forceinline__ int sw(int row, int c) { return (((c >> 2) ^ (row & 3)) << 2) | (c & 3); }
-
+// The main loop below is sf_gemm_tile's (match_mainloop.h), which k_top2_gemm calls.  This kernel keeps its own copy: calling
+// the shared function changes the order of its instructions (same registers, same MFMA and LDS counts), and the VEC form then
+// measured 1.0-1.5 % slower at 65 536^2 x 352 and the other form 5 % slower at 16 384^2 x 351
+// (profiles/match_mainloop_ab.md).  A change to one loop is made in the other too.
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void k_match_gemm(const double *__restrict__ a, int64_t m1,
                                                     const double *__restrict__ b, int64_t m2, int64_t d,
@@ -288,8 +279,7 @@ __global__ void k_match_decide(const double *__restrict__ a, int64_t m1, const d
         na += av * av;
         acc += df * df; // left to right, no FMA: scipy's euclidean loop
     }
-    const double tol = 8.0 * (double)d * 1.1102230246251565e-16 * (na + nb_max);
-    const bool decided = (bm2 - bm1) > tol; // false for NaN as well
+    const bool decided = (bm2 - bm1) > sf_match_tol(d, na, nb_max); // false for NaN as well
     idx[i] = bj;
     if (dist) dist[i] = sqrt(acc);
     flag[i] = decided ? 0 : 1;
@@ -297,6 +287,12 @@ __global__ void k_match_decide(const double *__restrict__ a, int64_t m1, const d
 }
 
 } // namespace
+
+int sf_match_sqnorm(sf_ctx *ctx, const char *name, const double *rows, int64_t m, int64_t d, const unsigned char *ok, double *out)
+{
+    SF_LAUNCH(ctx, name, k_row_sqnorm, dim3((unsigned)sf_div_up(m, 4)), dim3(256), rows, m, d, ok, out);
+    return SF_OK;
+}
 
 // Row arg-min of cdist(a, b) with the exact kernel's result; returns the number of rows that needed the slow path.
 int sf_match_gemm_f64(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
@@ -308,14 +304,11 @@ int sf_match_gemm_f64(sf_ctx *ctx, const double *da, int64_t m1, const double *d
     double *nb = nullptr, *part = nullptr;
     SF_CHECK(tmp.alloc(&nb, (size_t)m2));
     SF_CHECK(tmp.alloc(&part, (size_t)256));
-    SF_LAUNCH(ctx, "k8_row_sqnorm", k_row_sqnorm, dim3((unsigned)sf_div_up(m2, 4)), dim3(256), db, m2, d, b_ok, nb);
+    SF_CHECK(sf_match_sqnorm(ctx, "k8_row_sqnorm", db, m2, d, b_ok, nb));
     SF_LAUNCH(ctx, "k8_max_partial", k_max_partial, dim3(256), dim3(256), (const double *)nb, m2, part);
     const int64_t row_tiles = sf_div_up(m1, GM), col_tiles = sf_div_up(m2, GN);
-    int64_t nsplit = 1;
-    if (row_tiles < 1024) nsplit = std::min<int64_t>(col_tiles, sf_div_up(1024, row_tiles));
-    if (nsplit > 65535) nsplit = 65535;
-    const int64_t tiles_per_split = sf_div_up(col_tiles, nsplit);
-    nsplit = sf_div_up(col_tiles, tiles_per_split);
+    int64_t tiles_per_split = 0;
+    const int64_t nsplit = sf_match_col_splits(row_tiles, col_tiles, 1024, &tiles_per_split);
     double *pm1 = nullptr, *pm2 = nullptr;
     int64_t *pj1 = nullptr;
     int *flag = nullptr, *nflag = nullptr;

@@ -19,15 +19,14 @@
 #include <cfloat>
 #include <climits>
 #include <cmath>
-#include <vector>
 
 #include "device_util.h"
 #include "match.h"
+#include "match_mainloop.h"
 
 namespace {
 
 // ---- exact tile kernel ----------------------------------------------------------------------------------------------------------
-constexpr int TM = 64, TN = 64, TK = 16;
 constexpr int64_t NONE = INT64_MAX; // an empty slot: (+inf, NONE) ranks after every reference row
 constexpr int NONE_L = INT_MAX;     // the same inside a tile (columns relative to the tile's first)
 
@@ -63,7 +62,7 @@ __device__ __forceinline__ void top2d_merge(top2d<J> &p, double od1, J oj1, doub
     }
 }
 
-// One 64 x 64 tile of dist(i, j) per workgroup, 4 x 4 per thread, exactly as k_match_tile (match.hip) forms it.  Partials of
+// One 64 x 64 tile of dist(i, j) per workgroup, 4 x 4 per thread, from the loop k_match_tile (match.hip) runs.  Partials of
 // split s: pd[(2 s + q) m1 + i], pj[(2 s + q) m1 + i] for q = 0, 1 (the first and the second of the split's columns).
 __global__ __launch_bounds__(256) void k_top2_tile(const double *__restrict__ a, int64_t m1, const double *__restrict__ b,
                                                    int64_t m2, int64_t d, int64_t tiles_per_split, double *__restrict__ pd,
@@ -74,9 +73,8 @@ __global__ __launch_bounds__(256) void k_top2_tile(const double *__restrict__ a,
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int64_t i0 = (int64_t)blockIdx.x * TM;
     const int split = blockIdx.y;
-    const int64_t ntiles = (m2 + TN - 1) / TN;
-    const int64_t jt0 = (int64_t)split * tiles_per_split;
-    const int64_t jt1 = jt0 + tiles_per_split < ntiles ? jt0 + tiles_per_split : ntiles;
+    int64_t jt0, jt1;
+    sf_split_tiles(m2, TN, tiles_per_split, jt0, jt1);
     top2d<int64_t> best[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) best[u] = {INFINITY, INFINITY, NONE, NONE};
@@ -84,35 +82,7 @@ __global__ __launch_bounds__(256) void k_top2_tile(const double *__restrict__ a,
     for (int64_t jt = jt0; jt < jt1; ++jt) {
         const int64_t j0 = jt * TN;
         double acc[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
-        for (int64_t t0 = 0; t0 < d; t0 += TK) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int lin = tid + 256 * e;
-                const int r = lin >> 4, cc = lin & 15;
-                const int64_t t = t0 + cc;
-                As[cc][r] = (i0 + r < m1 && t < d) ? a[(i0 + r) * d + t] : 0.0;
-                Bs[cc][r] = (j0 + r < m2 && t < d) ? b[(j0 + r) * d + t] : 0.0;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int t = 0; t < TK; ++t) {
-                double av[4], bv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { av[u] = As[t][ty * 4 + u]; bv[u] = Bs[t][tx * 4 + u]; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const double df = av[u] - bv[v];
-                        acc[u][v] += df * df;
-                    }
-            }
-            __syncthreads();
-        }
+        sf_tile_sqdist(As, Bs, a, m1, i0, b, m2, j0, d, acc);
         // per row: the first two of the thread's 4 columns, then of the 16 tx lanes of the row group, then of the running pair
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -164,21 +134,6 @@ __global__ void k_top2_merge(const double *__restrict__ pd, const int64_t *__res
 }
 
 // ---- FP64 matrix-core path --------------------------------------------------------------------------------------------------------
-typedef double d4 __attribute__((ext_vector_type(4)));
-constexpr int GM = 128, GN = 128, GK = 16;
-constexpr int LDS_P = 16; // rows of 16 doubles, columns swizzled by sw() (match_gemm.hip)
-
-__global__ __launch_bounds__(256) void k_top2_sqnorm(const double *__restrict__ a, int64_t m, int64_t d, double *__restrict__ out)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= m) return;
-    double s = 0.0;
-    for (int64_t t = lane; t < d; t += 64) s += a[i * d + t] * a[i * d + t];
-    s = sf_wave_sum(s);
-    if (lane == 0) out[i] = s;
-}
-
 // the three smallest keys of a set and the columns of the first two; ties between keys are broken by arrival, which only the
 // columns of equal keys depend on -- a row whose k2 equals k3 is never decided, and the two columns of k1, k2 are re-ordered by
 // their exact distances
@@ -203,11 +158,9 @@ __device__ __forceinline__ void top3k_merge(top3k<J> &t, double o1, J oj1, doubl
     t.k3 = fmin(t.k3, o3);
 }
 
-__device__ __forceinline__ int sw(int row, int c) { return (((c >> 2) ^ (row & 3)) << 2) | (c & 3); }
-
-// k_match_gemm's main loop (VEC: 16-byte staging loads) with a top-3 epilogue.  Partials of split s: pk[(3 s + q) m1 + i] for
-// the keys q = 0, 1, 2, pj[(2 s + q) m1 + i] for the columns of the first two.  The VEC form spills 8 VGPRs: four loop-invariant
-// row addresses of the staging loads, reloaded once per column tile, never inside the k loop.
+// sf_gemm_tile (match_mainloop.h), which is k_match_gemm's loop, with a top-3 epilogue.  Partials of split s: pk[(3 s + q) m1 + i] for
+// the keys q = 0, 1, 2, pj[(2 s + q) m1 + i] for the columns of the first two.  The VEC form spills 16 bytes: one loop-invariant
+// row address of the staging loads, reloaded once per column tile, and tid_end, reloaded behind the loop; nothing inside the k loop.
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void k_top2_gemm(const double *__restrict__ a, int64_t m1, const double *__restrict__ b,
                                                    int64_t m2, int64_t d, const double *__restrict__ nb,
@@ -215,96 +168,24 @@ __global__ __launch_bounds__(256, 2) void k_top2_gemm(const double *__restrict__
 {
     __shared__ __attribute__((aligned(16))) double As[2][GM][LDS_P];
     __shared__ __attribute__((aligned(16))) double Bs[2][GN][LDS_P];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
+    const int tid = threadIdx.x, lane = tid & 63, wc = (tid >> 6) & 1;
     const int64_t i0 = (int64_t)blockIdx.x * GM;
     const int split = blockIdx.y;
-    const int64_t ntiles = (m2 + GN - 1) / GN;
-    const int64_t jt0 = (int64_t)split * tiles_per_split;
-    const int64_t jt1 = jt0 + tiles_per_split < ntiles ? jt0 + tiles_per_split : ntiles;
-    const int srow = tid & 127, skh = tid >> 7;
-    const int nk = (int)((d + GK - 1) / GK);
-    const int l15 = lane & 15, l4 = lane >> 4;
+    int64_t jt0, jt1;
+    sf_split_tiles(m2, GN, tiles_per_split, jt0, jt1);
+    const int l15 = lane & 15;
 
+    int tid_end = tid; // for the hand-over behind the loop: one register kept across it instead of the four pieces of `own`
+    asm volatile("" : "+v"(tid_end));
     top3k<int64_t> run = {INFINITY, INFINITY, INFINITY, 0, 0}; // the row this lane owns in its DPP row (as k_match_gemm)
 
     for (int64_t jt = jt0; jt < jt1; ++jt) {
         const int64_t j0 = jt * GN;
         d4 acc[4][4];
-#pragma unroll
-        for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj) acc[ti][tj] = d4{0.0, 0.0, 0.0, 0.0};
-        double ra[8], rb[8];
-        auto fetch = [&](int kt) {
-            if (VEC) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int p = tid + 256 * u, row = p >> 3, kp = p & 7;
-                    const int64_t k = (int64_t)kt * GK + 2 * kp, ar = i0 + row, br = j0 + row;
-                    double2 va = make_double2(0.0, 0.0), vb = make_double2(0.0, 0.0);
-                    if (ar < m1 && k < d) va = *reinterpret_cast<const double2 *>(a + ar * d + k);
-                    if (br < m2 && k < d) vb = *reinterpret_cast<const double2 *>(b + br * d + k);
-                    ra[2 * u] = va.x; ra[2 * u + 1] = va.y;
-                    rb[2 * u] = vb.x; rb[2 * u + 1] = vb.y;
-                }
-            } else {
-                const int64_t kbase = (int64_t)kt * GK + skh * 8;
-                const int64_t ar = i0 + srow, br = j0 + srow;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int64_t k = kbase + u;
-                    ra[u] = (ar < m1 && k < d) ? a[ar * d + k] : 0.0;
-                    rb[u] = (br < m2 && k < d) ? b[br * d + k] : 0.0;
-                }
-            }
-        };
-        auto stash = [&](int buf) {
-            if (VEC) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int p = tid + 256 * u, row = p >> 3, kp = p & 7;
-                    *reinterpret_cast<double2 *>(&As[buf][row][sw(row, 2 * kp)]) = make_double2(ra[2 * u], ra[2 * u + 1]);
-                    *reinterpret_cast<double2 *>(&Bs[buf][row][sw(row, 2 * kp)]) = make_double2(rb[2 * u], rb[2 * u + 1]);
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    As[buf][srow][sw(srow, skh * 8 + u)] = ra[u];
-                    Bs[buf][srow][sw(srow, skh * 8 + u)] = rb[u];
-                }
-            }
-        };
-        fetch(0);
-        stash(0);
-        __syncthreads();
-        for (int kt = 0; kt < nk; ++kt) {
-            const int buf = kt & 1;
-            if (kt + 1 < nk) fetch(kt + 1);
-#pragma unroll
-            for (int kk = 0; kk < GK / 4; ++kk) {
-                double af[4], bf[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    af[t] = As[buf][64 * wr + 16 * t + l15][sw(l15, kk * 4 + l4)];
-                    bf[t] = Bs[buf][64 * wc + 16 * t + l15][sw(l15, kk * 4 + l4)];
-                }
-#pragma unroll
-                for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < 4; ++tj)
-                        acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[ti], bf[tj], acc[ti][tj], 0, 0, 0);
-            }
-            if (kt + 1 < nk) stash(buf ^ 1);
-            __syncthreads();
-        }
+        sf_gemm_tile<VEC>(As, Bs, a, m1, i0, b, m2, j0, d, acc);
         double nbv[4];
         int64_t jcol[4];
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj) {
-            jcol[tj] = j0 + 64 * wc + 16 * tj + l15;
-            nbv[tj] = jcol[tj] < m2 ? nb[jcol[tj]] : INFINITY;
-        }
+        sf_gemm_cols(j0, m2, nb, jcol, nbv);
         // Per row (TI, R): the lane's four keys against the row's running THIRD key (broadcast from its owner with
         // row_newbcast); only a key below it changes the triple, so the butterfly is skipped wave-uniformly for most tiles.
 #define SF_TOP3_STEP(CTRL)                                                                                          \
@@ -342,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void k_top2_gemm(const double *__restrict__
     __syncthreads();
     double *sk = &As[0][0][0];                                 // 3 x 128 keys
     int64_t *sj = reinterpret_cast<int64_t *>(&Bs[0][0][0]); // 2 x 128 columns
-    const int own = 64 * wr + 16 * (l15 >> 2) + l4 + 4 * (l15 & 3);
+    const int own = sf_gemm_own_row(tid_end);
     if (wc == 1) {
         sk[own] = run.k1; sk[GM + own] = run.k2; sk[2 * GM + own] = run.k3;
         sj[own] = run.j1; sj[GM + own] = run.j2;
@@ -382,8 +263,7 @@ __global__ void k_top2_decide(const double *__restrict__ a, int64_t m1, const do
         acc1 += df1 * df1; // left to right, no FMA: scipy's euclidean loop
         acc2 += df2 * df2;
     }
-    const double tol = 8.0 * (double)d * 1.1102230246251565e-16 * (na + nb_max);
-    const bool decided = (t.k3 - t.k2) > tol; // false for NaN as well
+    const bool decided = (t.k3 - t.k2) > sf_match_tol(d, na, nb_max); // false for NaN as well
     flag[i] = decided ? 0 : 1;
     if (!decided) {
         atomicAdd(n_flagged, 1);
@@ -403,42 +283,15 @@ __global__ void k_top2_decide(const double *__restrict__ a, int64_t m1, const do
     }
 }
 
-// ---- rescue of the undecided rows: gather, match, scatter two results per row -----------------------------------------------
-__global__ void k_top2_gather(const double *__restrict__ a, int64_t d, const int64_t *__restrict__ rows, int64_t nr,
-                              double *__restrict__ out)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nr * d) return;
-    const int64_t r = g / d, t = g - r * d;
-    out[g] = a[rows[r] * d + t];
-}
-
-__global__ void k_top2_scatter(const int64_t *__restrict__ rows, int64_t nr, const int64_t *__restrict__ sidx,
-                               const double *__restrict__ sdist, int64_t *__restrict__ idx, double *__restrict__ dist)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nr) return;
-    const int64_t i = rows[g];
-    idx[2 * i] = sidx[2 * g];
-    idx[2 * i + 1] = sidx[2 * g + 1];
-    if (dist) {
-        dist[2 * i] = sdist[2 * g];
-        dist[2 * i + 1] = sdist[2 * g + 1];
-    }
-}
-
 } // namespace
 
-// The exact path on device pointers (column splits for small m1 as match.hip's match_one_way).
+// The exact path on device pointers.
 static int top2_exact(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
                       double *ddist, const char *name)
 {
     const int64_t row_tiles = sf_div_up(m1, TM), col_tiles = sf_div_up(m2, TN);
-    int64_t nsplit = 1;
-    if (row_tiles < 2048) nsplit = std::min<int64_t>(col_tiles, sf_div_up(2048, row_tiles));
-    if (nsplit > 65535) nsplit = 65535;
-    const int64_t tiles_per_split = sf_div_up(col_tiles, nsplit);
-    nsplit = sf_div_up(col_tiles, tiles_per_split);
+    int64_t tiles_per_split = 0;
+    const int64_t nsplit = sf_match_col_splits(row_tiles, col_tiles, 2048, &tiles_per_split);
     sf_pool_guard tmp(ctx);
     double *pd = nullptr;
     int64_t *pj = nullptr;
@@ -451,37 +304,6 @@ static int top2_exact(sf_ctx *ctx, const double *da, int64_t m1, const double *d
     return SF_OK;
 }
 
-// The flagged rows of the matrix-core path through the exact kernel (the top-2 sibling of sf_match_rescue).
-static int top2_rescue(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, const int *flag, int nf,
-                       int64_t *didx, double *ddist, int64_t *n_exact)
-{
-    if (nf <= 0) return SF_OK;
-    std::vector<int> hflag((size_t)m1);
-    SF_HIP(hipMemcpyAsync(hflag.data(), flag, (size_t)m1 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream));
-    std::vector<int64_t> rows;
-    rows.reserve((size_t)nf);
-    for (int64_t i = 0; i < m1; ++i)
-        if (hflag[(size_t)i]) rows.push_back(i);
-    const int64_t nr = (int64_t)rows.size();
-    *n_exact = nr;
-    sf_pool_guard tmp(ctx);
-    int64_t *drows = nullptr, *sidx = nullptr;
-    double *sub = nullptr, *sdist = nullptr;
-    SF_CHECK(tmp.alloc(&drows, (size_t)nr));
-    SF_CHECK(tmp.alloc(&sidx, (size_t)(2 * nr)));
-    SF_CHECK(tmp.alloc(&sdist, (size_t)(2 * nr)));
-    SF_CHECK(tmp.alloc(&sub, (size_t)(nr * d)));
-    SF_HIP(hipMemcpyAsync(drows, rows.data(), (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream)); // rows.data() is a host buffer: the copy is done before any return below
-    SF_LAUNCH(ctx, "k8_top2_gather", k_top2_gather, dim3((unsigned)sf_div_up(nr * d, 256)), dim3(256), da, d,
-              (const int64_t *)drows, nr, sub);
-    SF_CHECK(top2_exact(ctx, sub, nr, db, m2, d, sidx, sdist, "k8_top2_tile_slowpath"));
-    SF_LAUNCH(ctx, "k8_top2_scatter", k_top2_scatter, dim3((unsigned)sf_div_up(nr, 256)), dim3(256), (const int64_t *)drows, nr,
-              (const int64_t *)sidx, (const double *)sdist, didx, ddist);
-    return SF_OK;
-}
-
 // The FP64 matrix-core path on device pointers; *n_exact = rows it handed to the exact kernel.
 static int top2_gemm(sf_ctx *ctx, const double *da, int64_t m1, const double *db, int64_t m2, int64_t d, int64_t *didx,
                      double *ddist, int64_t *n_exact)
@@ -490,15 +312,12 @@ static int top2_gemm(sf_ctx *ctx, const double *da, int64_t m1, const double *db
     double *nb = nullptr, *part = nullptr;
     SF_CHECK(tmp.alloc(&nb, (size_t)m2));
     SF_CHECK(tmp.alloc(&part, (size_t)256));
-    SF_LAUNCH(ctx, "k8_top2_sqnorm", k_top2_sqnorm, dim3((unsigned)sf_div_up(m2, 4)), dim3(256), db, m2, d, nb);
+    SF_CHECK(sf_match_sqnorm(ctx, "k8_top2_sqnorm", db, m2, d, nullptr, nb));
     double nb_max = 0.0;
     SF_CHECK(sf_match_max(ctx, "k8_top2_max", nb, m2, part, &nb_max));
     const int64_t row_tiles = sf_div_up(m1, GM), col_tiles = sf_div_up(m2, GN);
-    int64_t nsplit = 1;
-    if (row_tiles < 1024) nsplit = std::min<int64_t>(col_tiles, sf_div_up(1024, row_tiles));
-    if (nsplit > 65535) nsplit = 65535;
-    const int64_t tiles_per_split = sf_div_up(col_tiles, nsplit);
-    nsplit = sf_div_up(col_tiles, tiles_per_split);
+    int64_t tiles_per_split = 0;
+    const int64_t nsplit = sf_match_col_splits(row_tiles, col_tiles, 1024, &tiles_per_split);
     double *pk = nullptr;
     int64_t *pj = nullptr;
     int *flag = nullptr, *nflag = nullptr;
@@ -520,7 +339,10 @@ static int top2_gemm(sf_ctx *ctx, const double *da, int64_t m1, const double *db
     int nf = 0;
     SF_HIP(hipMemcpyAsync(&nf, nflag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
-    return top2_rescue(ctx, da, m1, db, m2, d, flag, nf, didx, ddist, n_exact);
+    // the undecided rows through the exact kernel, two results per row
+    return sf_match_rescue(ctx, da, m1, d, flag, nf, [&](const double *sub, int64_t nr, int64_t *sidx, double *sdist) {
+        return top2_exact(ctx, sub, nr, db, m2, d, sidx, sdist, "k8_top2_tile_slowpath");
+    }, didx, ddist, n_exact, 2, "k8_top2_gather", "k8_top2_scatter");
 }
 
 // The arg-min's size rule (match.hip: match_dispatch) and SF_MATCH_EXACT.  Entries so large that a squared norm could overflow
@@ -529,9 +351,8 @@ static int top2_dispatch(sf_ctx *ctx, const double *da, int64_t m1, const double
                          int64_t *didx, double *ddist, int64_t *n_exact)
 {
     static const bool force_exact = getenv("SF_MATCH_EXACT") && getenv("SF_MATCH_EXACT")[0] == '1';
-    const double work = (double)m1 * (double)m2 * (double)d;
     const bool huge = !(8.0 * (double)d * entry_max * entry_max < 1e300);
-    if (force_exact || work < 5e8 || m2 < 256 || huge) {
+    if (force_exact || sf_match_small(m1, m2, d) || huge) {
         *n_exact = m1;
         return top2_exact(ctx, da, m1, db, m2, d, didx, ddist, "k8_top2_tile");
     }
