@@ -176,6 +176,28 @@ int sf_normals_radius(sf_ctx *ctx, sf_cloud *cloud, const double *queries, int64
                       const double *pre, double *out /* m x 3 */, int flags);
 int sf_normals(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, const double *pre, double *out /* m x 3 */,
                int flags);
+
+/* ---- ISS keypoints (Intrinsic Shape Signatures, Zhong 2009), K10: a detector the reference does not have ----
+ * saliency[i] = the smallest eigenvalue e3 of the covariance of the ball of salient_radius around point i (the very numbers
+ * compute_normals(radius=) decomposes; eigenvalues e1 >= e2 >= e3), or -1.0 unless the ball holds at least min_neighbors points
+ * (i included), e2 / e1 < gamma_21, e3 / e2 < gamma_32, e1 > 0, e2 > 0 and e3 > 1e-12 e1 (a fixed floor: an exactly flat ball
+ * must not become salient through the rounding of a sum).  Rows in the CALLER's point order, n of them; count (nullable):
+ * the ball sizes.  gammas in (0, 1], min_neighbors >= 1.  The pass runs on the grid sf_cloud_build_grid makes for
+ * salient_radius (rebuilt if the cloud carries another one), so its bits do not depend on earlier searches.
+ * flags: SF_OUT_DEVICE = saliency / count are device pointers. */
+int sf_iss_saliency(sf_ctx *ctx, sf_cloud *cloud, double salient_radius, double gamma_21, double gamma_32, int min_neighbors,
+                    double *saliency /* n */, int32_t *count /* nullable, n */, int flags);
+/* Non-maximum suppression of ANY per-point score (caller order, n values): point i is selected <=> score[i] > 0, the ball of
+ * non_max_radius around it holds at least min_neighbors points, and none of them has a strictly larger score (exact float64
+ * comparisons: points that tie are all kept).  selected (room for n): the int64 indices in ascending caller order;
+ * *n_selected (host): how many.  flags: SF_IN_DEVICE = score is a device pointer, SF_OUT_DEVICE = selected is one. */
+int sf_iss_select(sf_ctx *ctx, sf_cloud *cloud, const double *saliency /* n */, double non_max_radius, int min_neighbors,
+                  int64_t *selected /* n */, int64_t *n_selected, int flags);
+/* sf_iss_saliency followed by sf_iss_select without the saliency leaving the device; bit-identical to the two calls.
+ * saliency (nullable, n): receives the scores; flags: SF_OUT_DEVICE = saliency and selected are device pointers. */
+int sf_iss_keypoints(sf_ctx *ctx, sf_cloud *cloud, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
+                     int min_neighbors, double *saliency /* nullable, n */, int64_t *selected /* n */, int64_t *n_selected,
+                     int flags);
 /* Local PCA of every query's neighbourhood, same kernel (K3) with the full decomposition as output: replaces
  * the per-point loops of compute_sphericity / compute_pca_based_basic_features (pca_based_descriptors.py:60-73,
  * 150-187, via pca() :15-26) and compute_local_pca_with_moments (:75-146).  eigenvalues: ascending, m x 3.

@@ -28,8 +28,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("scan"), p.add_argument("ref")
     p.add_argument("--normals-k", type=int, default=30, help="neighbours for the PCA normals (reference default 30)")
     p.add_argument("--keep-stored-normals", action="store_true", help="use the file's normals instead of recomputing them")
-    p.add_argument("--keypoints", default="subsampling", choices=["random", "iterative", "subsampling", "subsampling_with_density"])
-    p.add_argument("--keypoint-size", type=float, default=None, help="sphere / voxel size of the keypoint selection")
+    p.add_argument("--keypoints", default="subsampling", choices=["random", "iterative", "subsampling", "subsampling_with_density", "iss"])
+    p.add_argument("--keypoint-size", type=float, default=None,
+                   help="sphere / voxel size of the keypoint selection (iss: the salient radius, default 6 x the cloud's resolution)")
+    p.add_argument("--iss-non-max-radius", type=float, default=None, help="iss: suppression radius (default 4 x the cloud's resolution)")
+    p.add_argument("--iss-gamma21", type=float, default=0.975), p.add_argument("--iss-gamma32", type=float, default=0.975)
     p.add_argument("--min-n-neighbors", type=int, default=None)
     p.add_argument("--proportion", type=float, default=0.5, help="share of points kept by --keypoints random")
     p.add_argument("--descriptor", default="shot_single_scale", choices=["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale"])
@@ -60,7 +63,8 @@ def main(argv=None) -> int:
     ref, ref_normals = get_data(args.ref, **load)
     pipe = RegistrationPipeline(scan=scan, scan_normals=scan_normals, ref=ref, ref_normals=ref_normals)
     pipe.select_keypoints(args.keypoints, neighborhood_size=args.keypoint_size, min_n_neighbors=args.min_n_neighbors,
-                          proportion_picked=args.proportion)
+                          proportion_picked=args.proportion, iss_non_max_radius=args.iss_non_max_radius,
+                          iss_gamma_21=args.iss_gamma21, iss_gamma_32=args.iss_gamma32)
     pipe.compute_descriptors(radius=args.radius, descriptor_choice=args.descriptor, fpfh_n_bins=args.fpfh_bins, phi=args.phi,
                              rho=args.rho, n_scales=args.n_scales, subsample_support=not args.no_support_subsampling,
                              min_neighborhood_size=args.min_neighborhood_size, disable_progress_bars=True, verbose=False)

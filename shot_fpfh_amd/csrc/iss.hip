@@ -1,0 +1,326 @@
+// iss.hip -- K10: ISS keypoints (Intrinsic Shape Signatures, Zhong 2009; the rule PCL's and Open3D's detectors are documented
+// with), the one stage of the pipeline the reference has no counterpart of.
+//
+//   saliency[i] = e3 of the covariance of the ball B(i, r_s) (eigenvalues e1 >= e2 >= e3), or -1 when the ball has fewer than
+//                 min_neighbors points, e2 / e1 >= gamma_21, e3 / e2 >= gamma_32, e1 <= 0, e2 <= 0 or e3 <= 1e-12 e1;
+//   keypoint i  <=> saliency[i] > 0, |B(i, r_n)| >= min_neighbors, and no j in B(i, r_n) has saliency[j] > saliency[i].
+//
+// Mapping: the covariances are K2 + K3's fused sweep (search.hip::k_radius_cov, unchanged, with its count output switched on);
+// k_iss_saliency is one eigen-solve per lane on top (eigh3.h; K4's note on one-thread solves applies, the stage is small);
+// k_iss_nms is K2's candidate sweep -- four queries per wave, run tables per 16-lane row, candidate pairs, the conservative
+// x window -- that reads the candidates' saliency next to their coordinates (a fourth coalesced 16-byte load: the array sits
+// in the cell-sorted order of xs / ys / zs) and keeps two wave-wide facts per query, the hit count and "some hit is strictly
+// larger".  No lists, no LDS ring: one int32 flag per point leaves the kernel.
+// What bounds it: the saliency pass is k_radius_cov (issue-bound sweep) + 1M eigen-solves; the suppression is the sweep of
+// K2's count pass with one more load per step and an early exit at the first larger hit.
+//
+// Orders.  Between the two passes the saliency lives in the CALLER's point order: a grid is kept or rebuilt per radius
+// (cell in [r, 2 r]) and a rebuild changes the cell-sorted order, so each pass maps through the perm of the grid it runs on.
+// The saliency pass always runs on the grid sf_cloud_build_grid makes for r_s itself -- the order of a covariance's sums
+// follows the cell-sorted order, and points with equal neighbour sets differ by that rounding alone, so the keypoints of a
+// cloud must not depend on which radius it happened to be searched with before.  The suppression compares stored values and
+// tests exact ball membership: it gives the same flags on any valid grid and takes whichever is there.
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+
+#include <cmath>
+
+#include "eigh3.h"
+#include "search_util.h"
+
+namespace {
+
+#define SF_ISS_FLOOR 1e-12 // e3 > SF_ISS_FLOOR * e1: a float64 covariance of k <= 1e4 points carries ~k 2^-53 e1 of rounding
+
+// One lane per cell-sorted position: eigenvalues of the covariance k_radius_cov left (c11 c21 c31 c22 c32 c33), the rule
+// above, the result scattered to the caller's numbering.
+__global__ __launch_bounds__(64) void k_iss_saliency(const double *__restrict__ cov, const int32_t *__restrict__ cnt,
+                                                     const int32_t *__restrict__ perm, int64_t n, double gamma_21, double gamma_32,
+                                                     int min_neighbors, double *__restrict__ saliency, int32_t *__restrict__ count)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *c = cov + 6 * i;
+    const sf_eig::eig3 e = sf_eig::eigh3_lower(c[0], c[1], c[2], c[3], c[4], c[5]);
+    const double e1 = e.w3, e2 = e.w2, e3 = e.w1;
+    const int k = cnt[i];
+    const bool salient = k >= min_neighbors && e1 > 0.0 && e2 > 0.0 && e2 / e1 < gamma_21 && e3 / e2 < gamma_32 && e3 > SF_ISS_FLOOR * e1;
+    const int64_t o = perm[i];
+    saliency[o] = salient ? e3 : -1.0;
+    if (count) count[o] = k;
+}
+
+// caller order -> the cell-sorted order of the current grid (+ the two elements the pair loads may touch past the end)
+__global__ void k_iss_gather(const double *__restrict__ score, const int32_t *__restrict__ perm, int64_t n, double *__restrict__ sorted)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) sorted[i] = score[perm[i]];
+    else if (i < n + 2) sorted[i] = 0.0;
+}
+
+#ifndef SF_ISS_WPB
+#define SF_ISS_WPB 8 // waves per workgroup, four queries each (K2's shape)
+#endif
+
+// Non-maximum suppression of `sal` (cell-sorted order) over the ball of squared radius r2 around every cloud point.
+// flag[perm[q]] = 1 <=> sal[q] > 0, at least min_neighbors points in the ball (q included), none of them with a larger value.
+__global__ __launch_bounds__(64 * SF_ISS_WPB) void k_iss_nms(sf_grid_desc g, const int32_t *__restrict__ cell_start,
+                                                             const double *__restrict__ xs, const double *__restrict__ ys,
+                                                             const double *__restrict__ zs, const double *__restrict__ sal,
+                                                             const int32_t *__restrict__ perm, int64_t m, double r2,
+                                                             int min_neighbors, int32_t *__restrict__ flag)
+{
+    const int lane = threadIdx.x & 63, sl = lane & 15, rw = lane >> 4;
+    const int64_t q0 = sf_uniform64((sf_xcd_block() * SF_ISS_WPB + (threadIdx.x >> 6)) * 4);
+    if (q0 >= m) return;
+    const int nq = (int)(m - q0 < 4 ? m - q0 : 4);
+    const int64_t qm = q0 + (rw < nq ? rw : 0);
+    const double pxv = xs[qm], pyv = ys[qm], pzv = zs[qm], sv = sal[qm]; // this row's query
+    int y0, y1, z0, z1;
+    stencil_bounds(pyv, g.lo[1], g.inv_cell, g.dim[1], y0, y1);
+    stencil_bounds(pzv, g.lo[2], g.inv_cell, g.dim[2], z0, z1);
+    __shared__ int4 runs[SF_ISS_WPB][4][12];
+    int4(*const tabs)[12] = runs[threadIdx.x >> 6];
+    int first_slot = 0;
+    { // (the run tables of the four queries, all of them whatever their saliency: see search.hip::k_radius)
+        const int r = sl < 9 ? sl : 8;
+        const int cz = z0 + r / 3, cy = y0 + r % 3;
+        bool ok = sl < 9 && rw < nq && cz <= z1 && cy <= y1;
+        const int64_t row = ((int64_t)(ok ? cz : z0) * g.dim[1] + (ok ? cy : y0)) * g.dim[0];
+        const double pxr = pxv - g.lo[0], pyr = pyv - g.lo[1], pzr = pzv - g.lo[2];
+        const double by0 = (double)cy * g.cell, bz0 = (double)cz * g.cell;
+        const double slack_y = 1e-9 * g.cell + 1e-15 * (fabs(pyr) + by0 + g.cell);
+        const double slack_z = 1e-9 * g.cell + 1e-15 * (fabs(pzr) + bz0 + g.cell);
+        const double dy = fmax(fmax(by0 - pyr, pyr - (by0 + g.cell)) - slack_y, 0.0);
+        const double dz = fmax(fmax(bz0 - pzr, pzr - (bz0 + g.cell)) - slack_z, 0.0);
+        const double w2 = (r2 * (1.0 + 1e-9) - dy * dy) - dz * dz;
+        ok = ok && w2 >= 0.0;
+        const double w = sf_sqrt_fast(fmax(w2, 0.0)) * (1.0 + 1e-9) + 1e-9 * g.cell +
+                         1e-15 * (fabs(pxr) + (double)g.dim[0] * (g.cell / (double)g.xsub));
+        int s = 0, e = 0;
+        if (sl < 9) {
+            s = cell_start[row + sf_cell_coord(pxr - w, 0.0, g.inv_cell_x, g.dim[0])];
+            e = cell_start[row + sf_cell_coord(pxr + w, 0.0, g.inv_cell_x, g.dim[0]) + 1];
+        }
+        if (!ok) { s = 0; e = 0; }
+        const int base = s & ~1;
+        const int npairs = (e - base + 1) >> 1;
+        int inc = npairs;
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false); // row_shr:1
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false); // row_shr:2
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, false); // row_shr:4
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, false); // row_shr:8
+        first_slot = inc - npairs;
+        if (sl < 12) tabs[rw][sl] = make_int4(base - 2 * first_slot, s, e, first_slot);
+    }
+    __builtin_amdgcn_wave_barrier(); // the tables are written and read by this wave only
+    for (int qi = 0; qi < nq; ++qi) {
+        const int64_t q = q0 + qi;
+        // the query's own value as a scalar: a point that is not salient is no keypoint whatever surrounds it, and the whole
+        // wave skips its sweep together (no lane reads a run table under a divergent mask)
+        const double sq = sf_read_lane(sv, 16 * qi);
+        int keep = 0;
+        if (sq > 0.0) {
+            const int4 *const tab = tabs[qi];
+            const double px = sf_read_lane(pxv, 16 * qi), py = sf_read_lane(pyv, 16 * qi), pz = sf_read_lane(pzv, 16 * qi);
+            const int b4 = __shfl(first_slot, 16 * qi + 4), b8 = __shfl(first_slot, 16 * qi + 8);
+            const int nslots = sf_uniform(__shfl(first_slot, 16 * qi + 9));
+            int total = 0;
+            bool larger = false;
+            for (int f0 = 0; f0 < nslots; f0 += 64) {
+                const int f = f0 + lane;
+                int r = f >= b4 ? 4 : 0;
+                r += f >= tab[r + 2].w ? 2 : 0;
+                r += f >= tab[r + 1].w ? 1 : 0;
+                r = f >= b8 ? 8 : r;
+                const int4 t = tab[r];
+                const bool live = f < nslots;
+                const int j = live ? t.x + 2 * f : 0; // idle lanes of the last step load pair 0 (always there)
+                const bool in0 = live & (j >= t.y), in1 = live & (j + 1 < t.z);
+                const double2 X = *reinterpret_cast<const double2 *>(xs + j);
+                const double2 Y = *reinterpret_cast<const double2 *>(ys + j);
+                const double2 Z = *reinterpret_cast<const double2 *>(zs + j);
+                const double2 S = *reinterpret_cast<const double2 *>(sal + j);
+                const double dxa = X.x - px, dya = Y.x - py, dza = Z.x - pz;
+                const double dxb = X.y - px, dyb = Y.y - py, dzb = Z.y - pz;
+                const double d2a = (dxa * dxa + dya * dya) + dza * dza, d2b = (dxb * dxb + dyb * dyb) + dzb * dzb;
+                const bool hit0 = in0 & (d2a <= r2);
+                const bool hit1 = in1 & (d2b <= r2);
+                total += __popcll(__ballot(hit0)) + __popcll(__ballot(hit1));
+                if (__ballot((hit0 & (S.x > sq)) | (hit1 & (S.y > sq)))) { larger = true; break; } // (wave-uniform)
+            }
+            keep = !larger && total >= min_neighbors;
+        }
+        if (lane == 0) flag[perm[q]] = keep;
+    }
+}
+
+struct flag_set {
+    const int32_t *flag;
+    __host__ __device__ bool operator()(int64_t i) const { return flag[i] != 0; }
+};
+
+int check_radius(const char *who, const char *what, double r)
+{
+    if (r > 0.0 && std::isfinite(r)) return SF_OK;
+    sf_set_error("%s: %s must be positive and finite (got %g)", who, what, r);
+    return SF_ERR_ARG;
+}
+
+int check_rule(const char *who, double gamma_21, double gamma_32, int min_neighbors)
+{
+    if (!(gamma_21 > 0.0 && gamma_21 <= 1.0) || !(gamma_32 > 0.0 && gamma_32 <= 1.0)) {
+        sf_set_error("%s: gamma_21 and gamma_32 must lie in (0, 1] (got %g, %g)", who, gamma_21, gamma_32);
+        return SF_ERR_ARG;
+    }
+    if (min_neighbors < 1) { sf_set_error("%s: min_neighbors must be at least 1 (got %d)", who, min_neighbors); return SF_ERR_ARG; }
+    return SF_OK;
+}
+
+// the grid sf_cloud_build_grid makes for this radius, whatever grid the cloud carries (see "Orders" above)
+int saliency_grid(sf_ctx *ctx, sf_cloud *c, double radius)
+{
+    const bool whole = c->cell_start && c->pop_begin == 0 && c->pop_end == c->n;
+    if (whole && c->cell == radius * (1.0 + 9.5367431640625e-07)) return SF_OK; // (grid.hip: edge = cell (1 + 2^-20))
+    return sf_cloud_build_grid(ctx, c, radius);
+}
+
+// saliency (and counts, nullable) of every point in the caller's order, device pointers
+int saliency_dev(sf_ctx *ctx, sf_cloud *c, double radius, double gamma_21, double gamma_32, int min_neighbors, double *saliency,
+                 int32_t *count)
+{
+    const int64_t n = c->n;
+    if (!n) return SF_OK;
+    SF_CHECK(saliency_grid(ctx, c, radius));
+    sf_pool_guard tmp(ctx);
+    double *cov = nullptr;
+    int32_t *cnt = nullptr;
+    SF_CHECK(tmp.alloc(&cov, (size_t)n * 6));
+    SF_CHECK(tmp.alloc(&cnt, (size_t)n));
+    SF_CHECK(sf_k2_radius_cov_self(ctx, c, radius, "k10_iss_cov", cov, cnt));
+    SF_LAUNCH(ctx, "k10_iss_saliency", k_iss_saliency, dim3((unsigned)sf_div_up(n, 64)), dim3(64), (const double *)cov,
+              (const int32_t *)cnt, (const int32_t *)c->perm, n, gamma_21, gamma_32, min_neighbors, saliency, count);
+    return SF_OK;
+}
+
+// the selected points of a score in the caller's order (device), ascending, and their number (device word *dnum)
+int select_dev(sf_ctx *ctx, sf_cloud *c, const double *score, double radius, int min_neighbors, int64_t *selected, size_t *dnum)
+{
+    const int64_t n = c->n;
+    SF_CHECK(sf_k2_ensure_grid(ctx, c, radius));
+    sf_pool_guard tmp(ctx);
+    double *sorted = nullptr;
+    int32_t *flag = nullptr;
+    SF_CHECK(tmp.alloc(&sorted, (size_t)n + 2));
+    SF_CHECK(tmp.alloc(&flag, (size_t)n));
+    SF_LAUNCH(ctx, "k10_iss_gather", k_iss_gather, dim3((unsigned)sf_div_up(n + 2, 256)), dim3(256), score, (const int32_t *)c->perm, n, sorted);
+    const sf_grid_desc g = sf_make_grid_desc(c);
+    SF_LAUNCH(ctx, "k10_iss_nms", k_iss_nms, dim3(sf_xcd_grid(sf_div_up(n, 4 * SF_ISS_WPB))), dim3(64 * SF_ISS_WPB), g,
+              (const int32_t *)c->cell_start, (const double *)c->xs, (const double *)c->ys, (const double *)c->zs, (const double *)sorted,
+              (const int32_t *)c->perm, n, radius * radius, min_neighbors, flag);
+    rocprim::counting_iterator<int64_t> first(0);
+    const flag_set pred{flag};
+    size_t tb = 0;
+    SF_HIP(rocprim::select(nullptr, tb, first, selected, dnum, (size_t)n, pred, ctx->stream));
+    char *scratch = nullptr;
+    SF_CHECK(tmp.alloc(&scratch, tb ? tb : 8));
+    {
+        sf_launch_timer t_(ctx, "k10_iss_compact");
+        SF_HIP(rocprim::select(scratch, tb, first, selected, dnum, (size_t)n, pred, ctx->stream));
+    }
+    return SF_OK;
+}
+
+// the tail of both selecting entry points: the count to the host (one read-back), then the indices if the host wants them
+int finish_selection(sf_ctx *ctx, const size_t *dnum, const int64_t *dsel, int64_t *selected, int64_t *n_selected, int flags)
+{
+    void *pin = nullptr;
+    SF_CHECK(sf_ctx_pinned(ctx, &pin));
+    SF_HIP(hipMemcpyAsync(pin, dnum, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t k = *(const size_t *)pin;
+    *n_selected = (int64_t)k;
+    if (!(flags & SF_OUT_DEVICE) && k) {
+        SF_HIP(hipMemcpyAsync(selected, dsel, k * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        SF_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return SF_OK;
+}
+
+} // namespace
+
+extern "C" int sf_iss_saliency(sf_ctx *ctx, sf_cloud *c, double salient_radius, double gamma_21, double gamma_32, int min_neighbors,
+                               double *saliency, int32_t *count, int flags)
+{
+    if (!ctx || !c || !saliency) { sf_set_error("sf_iss_saliency: null argument"); return SF_ERR_ARG; }
+    SF_CHECK(check_radius("sf_iss_saliency", "salient_radius", salient_radius));
+    SF_CHECK(check_rule("sf_iss_saliency", gamma_21, gamma_32, min_neighbors));
+    SF_HIP(hipSetDevice(ctx->device));
+    const int64_t n = c->n;
+    if (!n) return SF_OK;
+    sf_pool_guard tmp(ctx);
+    double *dsal = saliency;
+    int32_t *dcnt = count;
+    if (!(flags & SF_OUT_DEVICE)) {
+        SF_CHECK(tmp.alloc(&dsal, (size_t)n));
+        if (count) SF_CHECK(tmp.alloc(&dcnt, (size_t)n));
+    }
+    SF_CHECK(saliency_dev(ctx, c, salient_radius, gamma_21, gamma_32, min_neighbors, dsal, dcnt));
+    if (!(flags & SF_OUT_DEVICE)) {
+        SF_HIP(hipMemcpyAsync(saliency, dsal, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (count) SF_HIP(hipMemcpyAsync(count, dcnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        SF_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return SF_OK;
+}
+
+extern "C" int sf_iss_select(sf_ctx *ctx, sf_cloud *c, const double *saliency, double non_max_radius, int min_neighbors,
+                             int64_t *selected, int64_t *n_selected, int flags)
+{
+    if (!ctx || !c || !saliency || !selected || !n_selected) { sf_set_error("sf_iss_select: null argument"); return SF_ERR_ARG; }
+    SF_CHECK(check_radius("sf_iss_select", "non_max_radius", non_max_radius));
+    SF_CHECK(check_rule("sf_iss_select", 1.0, 1.0, min_neighbors));
+    SF_HIP(hipSetDevice(ctx->device));
+    const int64_t n = c->n;
+    *n_selected = 0;
+    if (!n) return SF_OK;
+    sf_pool_guard tmp(ctx);
+    const double *dsal = saliency;
+    if (!(flags & SF_IN_DEVICE)) {
+        double *p = nullptr;
+        SF_CHECK(tmp.alloc(&p, (size_t)n));
+        SF_HIP(hipMemcpyAsync(p, saliency, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        dsal = p;
+    }
+    int64_t *dsel = selected;
+    size_t *dnum = nullptr;
+    if (!(flags & SF_OUT_DEVICE)) SF_CHECK(tmp.alloc(&dsel, (size_t)n));
+    SF_CHECK(tmp.alloc(&dnum, 1));
+    SF_CHECK(select_dev(ctx, c, dsal, non_max_radius, min_neighbors, dsel, dnum));
+    return finish_selection(ctx, dnum, dsel, selected, n_selected, flags);
+}
+
+extern "C" int sf_iss_keypoints(sf_ctx *ctx, sf_cloud *c, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
+                                int min_neighbors, double *saliency, int64_t *selected, int64_t *n_selected, int flags)
+{
+    if (!ctx || !c || !selected || !n_selected) { sf_set_error("sf_iss_keypoints: null argument"); return SF_ERR_ARG; }
+    SF_CHECK(check_radius("sf_iss_keypoints", "salient_radius", salient_radius));
+    SF_CHECK(check_radius("sf_iss_keypoints", "non_max_radius", non_max_radius));
+    SF_CHECK(check_rule("sf_iss_keypoints", gamma_21, gamma_32, min_neighbors));
+    SF_HIP(hipSetDevice(ctx->device));
+    const int64_t n = c->n;
+    *n_selected = 0;
+    if (!n) return SF_OK;
+    sf_pool_guard tmp(ctx);
+    const bool dev_out = (flags & SF_OUT_DEVICE) != 0;
+    double *dsal = saliency;
+    int64_t *dsel = selected;
+    size_t *dnum = nullptr;
+    if (!dev_out || !saliency) SF_CHECK(tmp.alloc(&dsal, (size_t)n));
+    if (!dev_out) SF_CHECK(tmp.alloc(&dsel, (size_t)n));
+    SF_CHECK(tmp.alloc(&dnum, 1));
+    SF_CHECK(saliency_dev(ctx, c, salient_radius, gamma_21, gamma_32, min_neighbors, dsal, nullptr));
+    SF_CHECK(select_dev(ctx, c, dsal, non_max_radius, min_neighbors, dsel, dnum));
+    if (!dev_out && saliency) SF_HIP(hipMemcpyAsync(saliency, dsal, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    return finish_selection(ctx, dnum, dsel, selected, n_selected, flags);
+}

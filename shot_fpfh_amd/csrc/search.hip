@@ -1058,6 +1058,21 @@ extern "C" int sf_normals_radius(sf_ctx *ctx, sf_cloud *c, const double *queries
     if ((flags & (SF_IN_DEVICE | SF_OUT_DEVICE)) != (SF_IN_DEVICE | SF_OUT_DEVICE)) SF_HIP(hipStreamSynchronize(ctx->stream));
     return SF_OK;
 }
+
+// (for iss.hip) the grid rule of every search, and the fused sweep over the cloud's own points -- all of them, on the grid the
+// cloud carries, which the caller has made sure serves `radius` -- with the counts kept: cov 6 n and count n, by cell-sorted
+// position, under the timer name `prof`.
+int sf_k2_ensure_grid(sf_ctx *ctx, sf_cloud *c, double radius) { return ensure_grid(ctx, c, radius); }
+
+int sf_k2_radius_cov_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, double *cov, int32_t *count)
+{
+    const int64_t m = c->n;
+    if (!m) return SF_OK;
+    const sf_grid_desc g = sf_make_grid_desc(c);
+    SF_LAUNCH(ctx, prof, k_radius_cov, dim3(sf_xcd_grid(sf_div_up(m, 4 * SF_K2C_WPB))), dim3(64 * SF_K2C_WPB), g, c->cell_start, c->xs,
+              c->ys, c->zs, c->xs, c->ys, c->zs, m, radius * radius, cov, (double *)nullptr, count);
+    return SF_OK;
+}
 // ---- caller-supplied neighbourhoods ------------------------------------------------------------------------------------------
 // ShotMultiprocessor.compute_local_rf / compute_descriptor take the lists the caller hands them -- support[neighborhoods[i]],
 // shot_parallelization.py:46-84, 86-133 -- whatever produced them: KDTree.query_radius of another radius, KDTree.query (k-NN),

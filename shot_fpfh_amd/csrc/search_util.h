@@ -68,4 +68,7 @@ struct __attribute__((aligned(8))) sf_dbl2 {
 // search.hip, for knn.hip: queries into processing order, and the lists of a strided sample of them counted at a radius
 int sf_k2_prepare_queries(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const double *queries, int flags);
 int sf_k2_count_sample(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double r2, int32_t *sel_dev, int32_t *cnt_dev);
+// search.hip, for iss.hip: keep or rebuild the grid for a radius, and k_radius_cov over the whole cloud with its counts
+int sf_k2_ensure_grid(sf_ctx *ctx, sf_cloud *c, double radius);
+int sf_k2_radius_cov_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, double *cov, int32_t *count);
 

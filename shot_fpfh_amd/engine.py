@@ -725,6 +725,49 @@ class Cloud:
                                                     SF_IN_DEVICE | SF_OUT_DEVICE), "sf_normals_radius")
         return out
 
+    # ---- ISS keypoints (K10) ----------------------------------------------------------------------------
+    def resolution(self, points) -> float:
+        """Mean distance from a point to its nearest OTHER point: the second column of the k = 2 self query (an exact
+        duplicate contributes 0).  `points` are the cloud's own, in the caller's order."""
+        if self.n < 2:
+            raise ValueError("the resolution of a cloud needs at least two points")
+        off, _, dist = self.knn_search(points, 2).export(return_distance=True)
+        return float(dist.reshape(-1, 2).max(axis=1).mean())  # (export orders a list by index: the farther of the two)
+
+    def iss_saliency(self, salient_radius: float, gamma_21: float = 0.975, gamma_32: float = 0.975, min_neighbors: int = 5,
+                     return_counts: bool = False):
+        """sf_iss_saliency: the smallest covariance eigenvalue of every point's ball, -1.0 where the ISS rule rejects the
+        point; caller order [, the ball sizes]."""
+        sal = np.zeros(self.n, dtype=np.float64)
+        cnt = np.zeros(self.n, dtype=np.int32) if return_counts else None
+        _ffi.check(self.engine.lib.sf_iss_saliency(self.engine.h, self.h, float(salient_radius), float(gamma_21), float(gamma_32),
+                                                  int(min_neighbors), _ptr(sal), _ptr(cnt), SF_HOST), "sf_iss_saliency")
+        return (sal, cnt) if return_counts else sal
+
+    def iss_select(self, saliency, non_max_radius: float, min_neighbors: int = 5) -> np.ndarray:
+        """sf_iss_select: non-maximum suppression of any per-point score (caller order) over the balls of non_max_radius;
+        the selected indices, int64, ascending."""
+        score = np.ascontiguousarray(saliency, dtype=np.float64)
+        if score.shape != (self.n,):
+            raise ValueError(f"one score per cloud point expected, got shape {score.shape}")
+        sel = np.zeros(max(self.n, 1), dtype=np.int64)
+        k = C.c_int64(0)
+        _ffi.check(self.engine.lib.sf_iss_select(self.engine.h, self.h, _ptr(score), float(non_max_radius), int(min_neighbors),
+                                                _ptr(sel), C.byref(k), SF_HOST), "sf_iss_select")
+        return sel[: k.value].copy()
+
+    def iss_keypoints(self, salient_radius: float, non_max_radius: float, gamma_21: float = 0.975, gamma_32: float = 0.975,
+                      min_neighbors: int = 5, return_saliency: bool = False):
+        """sf_iss_keypoints: both passes, the saliency staying on the device in between."""
+        sal = np.zeros(self.n, dtype=np.float64) if return_saliency else None
+        sel = np.zeros(max(self.n, 1), dtype=np.int64)
+        k = C.c_int64(0)
+        _ffi.check(self.engine.lib.sf_iss_keypoints(self.engine.h, self.h, float(salient_radius), float(non_max_radius),
+                                                   float(gamma_21), float(gamma_32), int(min_neighbors), _ptr(sal), _ptr(sel),
+                                                   C.byref(k), SF_HOST), "sf_iss_keypoints")
+        idx = sel[: k.value].copy()
+        return (idx, sal) if return_saliency else idx
+
     def radius_search_self(self, radius: float, begin: int = 0, end: Optional[int] = None) -> "Neighbors":
         end = self.n if end is None else end
         h = _ffi.check_handle(

@@ -3,6 +3,9 @@
 Same names, arguments and results as the reference.  Wherever the reference builds a KDTree and calls
 query_radius, the lists come from the uniform-grid radius search on the MI355X (kernels K1 + K2); the
 remaining logic is index bookkeeping and stays on the host.
+
+`select_keypoints_iss` (with `cloud_resolution` and `iss_saliency`) has no counterpart in the reference: the ISS
+detector (Zhong 2009, the rule of PCL's and Open3D's detectors), which looks at the geometry -- kernels K10.
 """
 from __future__ import annotations
 
@@ -20,6 +23,9 @@ __all__ = [
     "select_keypoints_randomly",
     "select_query_indices_randomly",
     "select_keypoints_with_density_threshold",
+    "cloud_resolution",
+    "iss_saliency",
+    "select_keypoints_iss",
 ]
 
 # module-level generator with the reference's seed (keypoint_selection.py:8); its state persists across calls
@@ -89,3 +95,105 @@ def select_keypoints_with_density_threshold(
     finally:
         cloud.free()
     return picked[density > density_threshold_value]
+
+
+# ---- ISS (Intrinsic Shape Signatures): saliency + non-maximum suppression on the device (K10) ------------------------
+def _iss_points(points) -> npt.NDArray[np.float64]:
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"expected an (N, 3) array, got shape {points.shape}")
+    return points
+
+
+def _iss_radius(name: str, value) -> float:
+    value = float(value)
+    if not (np.isfinite(value) and value > 0.0):
+        raise ValueError(f"{name} must be positive and finite (got {value})")
+    return value
+
+
+def _iss_rule(gamma_21: float, gamma_32: float, min_neighbors: int) -> None:
+    for name, g in (("gamma_21", gamma_21), ("gamma_32", gamma_32)):
+        if not 0.0 < float(g) <= 1.0:
+            raise ValueError(f"{name} must lie in (0, 1] (got {g})")
+    if int(min_neighbors) < 1:
+        raise ValueError(f"min_neighbors must be at least 1 (got {min_neighbors})")
+
+
+def cloud_resolution(points: npt.NDArray[np.float64], *, engine=None) -> float:
+    """Mean over all points of the distance to the nearest OTHER point (the k = 2 self query, second column: exact
+    duplicates contribute 0)."""
+    points = _iss_points(points)
+    if points.shape[0] < 2:
+        raise ValueError("the resolution of a cloud needs at least two points")
+    cloud = (engine or default_engine()).cloud(points)
+    try:
+        return cloud.resolution(points)
+    finally:
+        cloud.free()
+
+
+def iss_saliency(
+    points: npt.NDArray[np.float64],
+    salient_radius: float,
+    gamma_21: float = 0.975,
+    gamma_32: float = 0.975,
+    min_neighbors: int = 5,
+    *,
+    engine=None,
+) -> npt.NDArray[np.float64]:
+    """ISS saliency of every point: with e1 >= e2 >= e3 the eigenvalues of the covariance of the ball of `salient_radius`
+    around it (the point included; mean-centred, divided by the ball's size), e3 if the ball holds at least
+    `min_neighbors` points, e2 / e1 < gamma_21, e3 / e2 < gamma_32, e1 > 0, e2 > 0 and e3 > 1e-12 e1 -- else -1.0."""
+    points = _iss_points(points)
+    salient_radius = _iss_radius("salient_radius", salient_radius)
+    _iss_rule(gamma_21, gamma_32, min_neighbors)
+    if points.shape[0] == 0:
+        return np.zeros(0, dtype=np.float64)
+    cloud = (engine or default_engine()).cloud(points)
+    try:
+        return cloud.iss_saliency(salient_radius, gamma_21, gamma_32, min_neighbors)
+    finally:
+        cloud.free()
+
+
+def select_keypoints_iss(
+    points: npt.NDArray[np.float64],
+    salient_radius: Optional[float] = None,
+    non_max_radius: Optional[float] = None,
+    gamma_21: float = 0.975,
+    gamma_32: float = 0.975,
+    min_neighbors: int = 5,
+    *,
+    return_saliency: bool = False,
+    engine=None,
+):
+    """ISS keypoints: the points whose saliency (iss_saliency) is positive, that have at least `min_neighbors` points
+    within `non_max_radius` (themselves included) and none among them with a strictly larger saliency -- exact ties are all
+    kept.  int64 indices into `points`, ascending [, the saliency of every point].  A radius left None is 6 (salient) resp.
+    4 (non-maximum) times the cloud's resolution (cloud_resolution); a resolution of 0 or fewer than two points then
+    raise ValueError."""
+    points = _iss_points(points)
+    if salient_radius is not None:
+        salient_radius = _iss_radius("salient_radius", salient_radius)
+    if non_max_radius is not None:
+        non_max_radius = _iss_radius("non_max_radius", non_max_radius)
+    _iss_rule(gamma_21, gamma_32, min_neighbors)
+    n = points.shape[0]
+    if n == 0:
+        empty = np.zeros(0, dtype=np.int64)
+        return (empty, np.zeros(0, dtype=np.float64)) if return_saliency else empty
+    automatic = salient_radius is None or non_max_radius is None
+    if automatic and n < 2:
+        raise ValueError("automatic ISS radii need at least two points")
+    cloud = (engine or default_engine()).cloud(points)
+    try:
+        if automatic:
+            rho = cloud.resolution(points)
+            if not rho > 0.0:
+                raise ValueError("automatic ISS radii need a cloud resolution above 0 (every point has an exact duplicate)")
+            salient_radius = 6.0 * rho if salient_radius is None else salient_radius
+            non_max_radius = 4.0 * rho if non_max_radius is None else non_max_radius
+        return cloud.iss_keypoints(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, return_saliency)
+    finally:
+        cloud.free()

@@ -60,13 +60,18 @@ class RegistrationPipeline:
     # ---- stage 1: keypoints (pipeline.py:53-130) ---------------------------------------------------------
     def select_keypoints(
         self,
-        selection_algorithm: Literal["random", "iterative", "subsampling", "subsampling_with_density"],
+        selection_algorithm: Literal["random", "iterative", "subsampling", "subsampling_with_density", "iss"],
         *,
         neighborhood_size: float | None = None,
         min_n_neighbors: int | None = None,
         proportion_picked: float = 0.5,
         force_recompute: bool = False,
+        iss_non_max_radius: float | None = None,
+        iss_gamma_21: float = 0.975,
+        iss_gamma_32: float = 0.975,
     ) -> None:
+        """"iss" (not in the reference): `neighborhood_size` is the salient radius, `iss_non_max_radius` the suppression
+        radius (None: 6 resp. 4 times the cloud's resolution), `min_n_neighbors` the smallest ball when given (else 5)."""
         if selection_algorithm == "random":
             assert 0 <= proportion_picked <= 1, "Incorrect proportion passed."
         pick = {
@@ -74,6 +79,8 @@ class RegistrationPipeline:
             "iterative": lambda p: _ks.select_keypoints_iteratively(p, neighborhood_size),
             "subsampling": lambda p: _ks.select_keypoints_subsampling(p, neighborhood_size),
             "subsampling_with_density": lambda p: _ks.select_keypoints_with_density_threshold(p, neighborhood_size, min_n_neighbors),
+            "iss": lambda p: _ks.select_keypoints_iss(p, neighborhood_size, iss_non_max_radius, iss_gamma_21, iss_gamma_32,
+                                                      5 if min_n_neighbors is None else min_n_neighbors),
         }.get(selection_algorithm)
         if pick is None:
             raise ValueError("Incorrect keypoint selection algorithm.")
