@@ -383,6 +383,36 @@ int sf_rows_abs_max(sf_ctx *ctx, const double *rows_dev, int64_t m, int64_t d, d
 int sf_ransac_score(sf_ctx *ctx, const double *a, const double *b, int64_t m, const double *Rt, int64_t n_draws,
                     double thr, int64_t *inliers, int flags);
 
+/* ---- RANSAC with pre-rejection, device-side Kabsch and a refit over the inliers: K11 (no counterpart in the reference) ----
+ * a_dev, b_dev: m x 3 matched points; draws_dev: n_draws x draw_size int64 indices into them (3 <= draw_size <= 8).  All data
+ * pointers are DEVICE memory except where a parameter says "host".
+ * sf_ransac_hypotheses: per draw one status byte and one row [R row-major (9), t (3)] (zeros unless the status is 0):
+ *     0  a transform: R = argmax tr(R H) over SO(3) for the sample's centred cross-covariance H, t = bbar - R abar
+ *     1  rejected: some pair i < j of the sample has edge lengths ea = |a_i - a_j|, eb = |b_i - b_j| with
+ *        ea < edge_similarity * eb or eb < edge_similarity * ea            (edge_similarity in [0, 1); 0 passes everything)
+ *     2  degenerate: s2 + sign(det H) s3 <= 1e-6 s1 for H's singular values s1 >= s2 >= s3 (H = 0 and non-finite input included)
+ *     3  an index outside [0, m): never dereferenced, the draw is left out
+ *   Asynchronous on the context's stream.
+ * sf_ransac_refit_sums: the sums of one Kabsch fit over ALL inliers ||a R^T + t - b|| <= thr (K9's rule, bit for bit) of the
+ *   transform Rt (12 host doubles), centroids first, then the centred cross-covariance; block partials are folded in a fixed
+ *   order, so a call repeats bit for bit.  sums[24] (host): [0] inlier count, [1..3] abar, [4..6] bbar over the inliers,
+ *   [7..15] sum (a - abar)(b - bbar)^T row-major, [16] sum of squared residuals, [17..19] sum a, [20..22] sum b, [23] 0.
+ * sf_ransac_prerejective: sf_ransac_hypotheses, the status-0 rows compacted in draw order, sf_ransac_score over them and the
+ *   FIRST maximum.  Optional device outputs (NULL: not wanted): status_dev (n_draws), Rt_dev (n_draws x 12: the first n_scored
+ *   rows are the compacted transforms), map_dev (n_draws: slot -> draw number, strictly increasing), counts_dev (n_draws: K9's
+ *   counts per slot).  result[8] (host): [0] rejected, [1] degenerate, [2] scored draws, [3] the winning draw (-1: nothing was
+ *   scored), [4] its inlier count, [5] its slot, [6] draws of status 3 (then the call returns SF_ERR_ARG), [7] 0;
+ *   best_Rt[12] (host): the winner's transform. */
+#define SF_RANSAC_MIN_DRAW_SIZE 3
+#define SF_RANSAC_MAX_DRAW_SIZE 8
+int sf_ransac_hypotheses(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const int64_t *draws_dev,
+                         int64_t n_draws, int draw_size, double edge_similarity, unsigned char *status_dev, double *Rt_dev);
+int sf_ransac_refit_sums(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const double *Rt /* 12 */, double thr,
+                         double *sums /* 24 */);
+int sf_ransac_prerejective(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const int64_t *draws_dev,
+                           int64_t n_draws, int draw_size, double edge_similarity, double thr, unsigned char *status_dev,
+                           double *Rt_dev, int64_t *map_dev, int64_t *counts_dev, int64_t *result /* 8 */, double *best_Rt /* 12 */);
+
 /* ---- voxel subsampling: grid_subsampling (core/subsampling.py:5-39) and the voxel loop of
  * select_keypoints_with_density_threshold (keypoint_selection.py:80-101) ---------------------------------
  * sf_voxels_build: keys ((p - min p) // voxel).astype(int) with NumPy's floor_divide, voxels ranked in np.unique's

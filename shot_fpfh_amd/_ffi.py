@@ -109,6 +109,9 @@ SIGNATURES = {
     "sf_match_stream_abort": (None, [_vp, _vp]),
     "sf_rows_abs_max": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "sf_ransac_score": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _f64, _vp, _int]),
+    "sf_ransac_hypotheses": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _f64, _vp, _vp]),
+    "sf_ransac_refit_sums": (_int, [_vp, _vp, _vp, _i64, _vp, _f64, _vp]),
+    "sf_ransac_prerejective": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_voxels_build": (_vp, [_vp, _vp, _i64, _f64, _int]),
     "sf_voxels_count": (_i64, [_vp]),
     "sf_voxels_inverse": (_int, [_vp, _vp, _vp]),

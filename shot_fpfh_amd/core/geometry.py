@@ -70,6 +70,19 @@ def solver_point_to_point(scan: npt.NDArray[np.float64], ref: npt.NDArray[np.flo
     return RigidTransform(rot, ref_center - rot.dot(scan_center))
 
 
+def kabsch_from_covariance(cross_cov: npt.NDArray[np.float64], scan_center: npt.NDArray[np.float64],
+                           ref_center: npt.NDArray[np.float64]) -> RigidTransform:
+    """`solver_point_to_point` from its sums -- centred cross-covariance sum (p - pbar)(q - qbar)^T and the two centroids, as
+    the device reductions return them (ICP's pair sums, the RANSAC refit): same SVD, same reflection rule."""
+    u, _, vt = np.linalg.svd(cross_cov)
+    rot = vt.T @ u.T
+    if np.linalg.det(rot) < 0:
+        ut = u.T.copy()
+        ut[-1] *= -1
+        rot = vt.T @ ut
+    return RigidTransform(rot, ref_center - rot.dot(scan_center))
+
+
 def solver_point_to_point_batched(scan: npt.NDArray[np.float64], ref: npt.NDArray[np.float64], return_reflected: bool = False):
     """`solver_point_to_point` for a stack of draws: scan, ref of shape (n, k, 3) -> rotations (n, 3, 3),
     translations (n, 3).

@@ -3,6 +3,7 @@
 // Not part of include/shotfpfh.h.  (The main loops of the float64 kernels: match_mainloop.h.)
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <functional>
 
@@ -44,6 +45,20 @@ int sf_match_rescue(sf_ctx *ctx, const double *da, int64_t m1, int64_t d, const 
 int sf_match_max(sf_ctx *ctx, const char *name, const double *v, int64_t n, double *part, double *out);
 
 // The size rule of the float64 paths: below it the fixed costs of the matrix-core path dominate and the exact tile kernel runs
+// K9's inlier rule sqrt(s) <= thr without the square root: certain for s <= lo = thr^2 rounded down, impossible for s >= hi =
+// (next double)^2 rounded up (sqrt is monotone and correctly rounded); a negative or NaN threshold admits nothing.  Shared by
+// K9 (match.hip) and the refit sums of K11 (ransac.hip), which must take the very same pairs.
+static inline void sf_ransac_band(double thr, double *lo, double *hi)
+{
+    *lo = *hi = -1.0;
+    if (thr >= 0.0) {
+        const double up = std::nextafter(thr, INFINITY);
+        *lo = std::nextafter(thr * thr, -INFINITY);
+        *hi = std::isinf(up) ? INFINITY : std::nextafter(up * up, INFINITY);
+        if (std::isinf(thr)) *lo = *hi = INFINITY; // everything finite is an inlier; s = inf: sqrt path
+    }
+}
+
 static inline bool sf_match_small(int64_t m1, int64_t m2, int64_t d)
 {
     return (double)m1 * (double)m2 * (double)d < 5e8 || m2 < 256;

@@ -464,15 +464,8 @@ extern "C" int sf_ransac_score(sf_ctx *ctx, const double *a, const double *b, in
     if (n_draws) {
         SF_HIP(hipMemsetAsync(dinl, 0, (size_t)n_draws * sizeof(int64_t), ctx->stream));
         if (m) {
-            // sqrt(s) <= thr is certain for s <= lo = thr^2 rounded down, impossible for s >= hi = (next double)^2
-            // rounded up (sqrt is monotone and correctly rounded); a negative or NaN threshold admits nothing
-            double lo = -1.0, hi = -1.0;
-            if (thr >= 0.0) {
-                const double up = std::nextafter(thr, INFINITY);
-                lo = std::nextafter(thr * thr, -INFINITY);
-                hi = std::isinf(up) ? INFINITY : std::nextafter(up * up, INFINITY);
-                if (std::isinf(thr)) lo = hi = INFINITY; // everything finite is an inlier; s = inf: sqrt path
-            }
+            double lo, hi;
+            sf_ransac_band(thr, &lo, &hi);
             const int64_t tiles = sf_div_up(m, K9_TILE);
             int64_t splits = sf_div_up(n_draws, K9_MAX_DRAWS);
             if (tiles * splits < 1024) splits = std::min<int64_t>(n_draws, sf_div_up(1024, tiles));

@@ -1,0 +1,380 @@
+// ransac.hip -- K11: RANSAC with pre-rejection, the Kabsch fits on the device and the sums of a refit over the inliers.
+//
+// No counterpart in the reference, whose ransac_on_matches (ransac.py:17-82) scores every draw and keeps the first best minimal
+// sample.  Here, per draw (k11_hypotheses, one thread each):
+//   1. the edge-length test of Open3D's CorrespondenceCheckerBasedOnEdgeLength / PCL's SampleConsensusPrerejective: a rigid motion
+//      keeps distances, so a sample whose scan-side and reference-side edges disagree (ea < sim eb or eb < sim ea for a pair) holds a
+//      wrong match and is dropped before anybody scores it                                                     -> status 1
+//   2. the Kabsch fit of the sample: centroids, centred cross-covariance H, R = argmax tr(R H) by Horn's quaternion form (horn4.h),
+//      t = bbar - R abar.  gap = s2 + sign(det H) s3 <= 1e-6 s1 (H = 0, collinear samples, non-finite input) -> status 2
+// The surviving transforms are compacted IN DRAW ORDER (count per block, scan of the block counts, scatter: no atomics decide a
+// position), scored by K9 (sf_ransac_score, match.hip -- reused as it is) and reduced to the first maximum.
+// k11_pair_sums are the two passes of a Kabsch fit over ALL inliers of one transform -- K9's inlier rule, centroids first, then the
+// centred cross-covariance, block partials folded in a fixed order as icp.hip does for nearest-neighbour pairs -- whose 3x3 problem
+// the caller solves on the host.
+#include "common.h"
+#include "device_util.h"
+#include "horn4.h"
+#include "match.h"
+
+extern "C" int sf_ransac_score(sf_ctx *ctx, const double *a, const double *b, int64_t m, const double *Rt, int64_t n_draws,
+                               double thr, int64_t *inliers, int flags);
+
+namespace {
+
+constexpr int K11_MAX_DRAW = SF_RANSAC_MAX_DRAW_SIZE;
+constexpr int K11_BLOCK = 256;       // draws per block of the compaction kernels
+constexpr int K11_SUM_BLOCKS = 256;  // blocks of the pair sums (fixed: the fold order does not depend on m)
+constexpr int K11_NV = 10;           // values per partial row (pass 0: 7, pass 1: 10)
+constexpr int64_t K11_MAX_DRAWS = (int64_t)65535 * 8192; // K9's limit (match.hip)
+
+__global__ __launch_bounds__(64) void k11_hypotheses(const double *__restrict__ a, const double *__restrict__ b, int64_t m,
+                                                     const int64_t *__restrict__ draws, int64_t n_draws, int size, double sim,
+                                                     unsigned char *__restrict__ status, double *__restrict__ Rt)
+{
+    const int64_t d = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (d >= n_draws) return;
+    // the sample: arrays indexed by unrolled loop counters only (registers)
+    double ax[K11_MAX_DRAW], ay[K11_MAX_DRAW], az[K11_MAX_DRAW], bx[K11_MAX_DRAW], by[K11_MAX_DRAW], bz[K11_MAX_DRAW];
+    bool bad = false;
+#pragma unroll
+    for (int s = 0; s < K11_MAX_DRAW; ++s) {
+        ax[s] = ay[s] = az[s] = bx[s] = by[s] = bz[s] = 0.0;
+        if (s < size) {
+            int64_t i = draws[d * size + s];
+            if (i < 0 || i >= m) { bad = true; i = 0; } // never dereferenced out of range (m >= 1 here)
+            ax[s] = a[3 * i]; ay[s] = a[3 * i + 1]; az[s] = a[3 * i + 2];
+            bx[s] = b[3 * i]; by[s] = b[3 * i + 1]; bz[s] = b[3 * i + 2];
+        }
+    }
+    bool pass = true;
+#pragma unroll
+    for (int i = 0; i < K11_MAX_DRAW; ++i)
+#pragma unroll
+        for (int j = i + 1; j < K11_MAX_DRAW; ++j)
+            if (j < size) {
+                const double ux = ax[i] - ax[j], uy = ay[i] - ay[j], uz = az[i] - az[j];
+                const double vx = bx[i] - bx[j], vy = by[i] - by[j], vz = bz[i] - bz[j];
+                const double ea = sqrt((ux * ux + uy * uy) + uz * uz), eb = sqrt((vx * vx + vy * vy) + vz * vz);
+                pass &= (ea >= sim * eb) & (eb >= sim * ea);
+            }
+    unsigned char st = bad ? 3 : (pass ? 0 : 1);
+    double o[12];
+#pragma unroll
+    for (int v = 0; v < 12; ++v) o[v] = 0.0;
+    if (st == 0) {
+        double ma0 = 0, ma1 = 0, ma2 = 0, mb0 = 0, mb1 = 0, mb2 = 0;
+#pragma unroll
+        for (int s = 0; s < K11_MAX_DRAW; ++s)
+            if (s < size) { ma0 += ax[s]; ma1 += ay[s]; ma2 += az[s]; mb0 += bx[s]; mb1 += by[s]; mb2 += bz[s]; }
+        const double n = (double)size;
+        ma0 /= n; ma1 /= n; ma2 /= n; mb0 /= n; mb1 /= n; mb2 /= n;
+        double h00 = 0, h01 = 0, h02 = 0, h10 = 0, h11 = 0, h12 = 0, h20 = 0, h21 = 0, h22 = 0;
+#pragma unroll
+        for (int s = 0; s < K11_MAX_DRAW; ++s)
+            if (s < size) {
+                const double px = ax[s] - ma0, py = ay[s] - ma1, pz = az[s] - ma2;
+                const double qx = bx[s] - mb0, qy = by[s] - mb1, qz = bz[s] - mb2;
+                h00 += px * qx; h01 += px * qy; h02 += px * qz;
+                h10 += py * qx; h11 += py * qy; h12 += py * qz;
+                h20 += pz * qx; h21 += pz * qy; h22 += pz * qz;
+            }
+        const sf_horn::rot3 R = sf_horn::kabsch_rotation(h00, h01, h02, h10, h11, h12, h20, h21, h22);
+        const double t0 = mb0 - ((R.r0 * ma0 + R.r1 * ma1) + R.r2 * ma2);
+        const double t1 = mb1 - ((R.r3 * ma0 + R.r4 * ma1) + R.r5 * ma2);
+        const double t2 = mb2 - ((R.r6 * ma0 + R.r7 * ma1) + R.r8 * ma2);
+        // (the sum of magnitudes is finite iff all twelve are: no NaN and no infinity ever reaches the scoring)
+        const double mag = (((fabs(R.r0) + fabs(R.r1)) + (fabs(R.r2) + fabs(R.r3))) + ((fabs(R.r4) + fabs(R.r5)) + (fabs(R.r6) + fabs(R.r7)))) +
+                           ((fabs(R.r8) + fabs(t0)) + (fabs(t1) + fabs(t2)));
+        if (R.gap > 1e-6 * R.s1 && mag <= 1.7976931348623157e308) {
+            o[0] = R.r0; o[1] = R.r1; o[2] = R.r2; o[3] = R.r3; o[4] = R.r4; o[5] = R.r5; o[6] = R.r6; o[7] = R.r7; o[8] = R.r8;
+            o[9] = t0; o[10] = t1; o[11] = t2;
+        } else {
+            st = 2;
+        }
+    }
+    status[d] = st;
+#pragma unroll
+    for (int v = 0; v < 12; ++v) Rt[12 * d + v] = o[v];
+}
+
+// survivors (status 0) per block of K11_BLOCK draws; tallies[1..3]: draws of status 1, 2, 3
+__global__ __launch_bounds__(K11_BLOCK) void k11_count(const unsigned char *__restrict__ status, int64_t n_draws,
+                                                       int *__restrict__ block_count, unsigned long long *__restrict__ tallies)
+{
+    __shared__ int c[4];
+    if (threadIdx.x < 4) c[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t d = (int64_t)blockIdx.x * K11_BLOCK + threadIdx.x;
+    const int st = d < n_draws ? (int)status[d] : -1;
+    for (int v = 0; v < 4; ++v) {
+        const int n = __popcll(__ballot(st == v));
+        if ((threadIdx.x & 63) == 0 && n) atomicAdd(&c[v], n);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) block_count[blockIdx.x] = c[0];
+    if (threadIdx.x >= 1 && threadIdx.x < 4 && c[threadIdx.x]) atomicAdd(&tallies[threadIdx.x], (unsigned long long)c[threadIdx.x]);
+}
+
+// exclusive scan of the block counts by ONE block (a chunk of 256 per step, carried); tallies[0] = number of survivors
+__global__ __launch_bounds__(256) void k11_scan(const int *__restrict__ block_count, int64_t nblocks, int64_t *__restrict__ block_off,
+                                                unsigned long long *__restrict__ tallies)
+{
+    __shared__ int64_t sh[256];
+    int64_t carry = 0;
+    for (int64_t base = 0; base < nblocks; base += 256) {
+        const int64_t i = base + threadIdx.x;
+        const int64_t mine = i < nblocks ? block_count[i] : 0;
+        sh[threadIdx.x] = mine;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const int64_t add = threadIdx.x >= off ? sh[threadIdx.x - off] : 0;
+            __syncthreads();
+            sh[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (i < nblocks) block_off[i] = carry + sh[threadIdx.x] - mine;
+        carry += sh[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tallies[0] = (unsigned long long)carry;
+}
+
+// survivors to their slot, draw order kept: slot = block offset + survivors before this one in the block
+__global__ __launch_bounds__(K11_BLOCK) void k11_scatter(const unsigned char *__restrict__ status, const double *__restrict__ Rt_all,
+                                                         int64_t n_draws, const int64_t *__restrict__ block_off,
+                                                         double *__restrict__ Rt_out, int64_t *__restrict__ map)
+{
+    __shared__ int wave_n[K11_BLOCK / 64];
+    const int64_t d = (int64_t)blockIdx.x * K11_BLOCK + threadIdx.x;
+    const bool keep = d < n_draws && status[d] == 0;
+    const unsigned long long mask = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_n[wave] = __popcll(mask);
+    __syncthreads();
+    if (!keep) return;
+    int before = __popcll(mask & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) before += wave_n[w];
+    const int64_t slot = block_off[blockIdx.x] + before;
+    map[slot] = d;
+#pragma unroll
+    for (int v = 0; v < 12; ++v) Rt_out[12 * slot + v] = Rt_all[12 * d + v];
+}
+
+// first maximum of counts[0..n): out = {slot, draw, count}, best_rt = that slot's transform.  One block.
+__global__ __launch_bounds__(1024) void k11_argmax(const int64_t *__restrict__ counts, int64_t n, const int64_t *__restrict__ map,
+                                                   const double *__restrict__ Rt, int64_t *__restrict__ out, double *__restrict__ best_rt)
+{
+    __shared__ int64_t sc[16], si[16];
+    int64_t best = -1, bi = INT64_MAX;
+    for (int64_t i = threadIdx.x; i < n; i += 1024) { // ascending per thread: strict > keeps its first maximum
+        const int64_t c = counts[i];
+        if (c > best) { best = c; bi = i; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const int64_t c2 = __shfl_xor(best, off), i2 = __shfl_xor(bi, off);
+        if (c2 > best || (c2 == best && i2 < bi)) { best = c2; bi = i2; }
+    }
+    if ((threadIdx.x & 63) == 0) { sc[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        best = threadIdx.x < 16 ? sc[threadIdx.x] : -1;
+        bi = threadIdx.x < 16 ? si[threadIdx.x] : INT64_MAX;
+        for (int off = 8; off > 0; off >>= 1) {
+            const int64_t c2 = __shfl_xor(best, off), i2 = __shfl_xor(bi, off);
+            if (c2 > best || (c2 == best && i2 < bi)) { best = c2; bi = i2; }
+        }
+        best = __shfl(best, 0); bi = __shfl(bi, 0);
+        const bool any = best >= 0;
+        if (threadIdx.x == 0) { out[0] = any ? bi : -1; out[1] = any ? map[bi] : -1; out[2] = any ? best : 0; }
+        if (threadIdx.x < 12) best_rt[threadIdx.x] = any ? Rt[12 * bi + threadIdx.x] : 0.0;
+    }
+}
+
+// pass 0: inlier count, sum of inlier a, sum of inlier b.  pass 1: centred H = sum (a - abar)(b - bbar)^T (9), sum of squared residuals.
+// The inliers are K9's: ((a R^T) + t) - b formed left to right, sqrt(s) <= thr decided through the band (sf_ransac_band).
+template <int PASS>
+__global__ __launch_bounds__(256) void k11_pair_sums(const double *__restrict__ a, const double *__restrict__ b, int64_t m,
+                                                     const double *__restrict__ R, double thr, double lo, double hi,
+                                                     const double *__restrict__ mean /* 6, pass 1 */, double *__restrict__ partial)
+{
+    constexpr int NV = PASS == 0 ? 7 : 10;
+    __shared__ double sh[4][K11_NV];
+    double acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+    const double r0 = R[0], r1 = R[1], r2 = R[2], r3 = R[3], r4 = R[4], r5 = R[5], r6 = R[6], r7 = R[7], r8 = R[8];
+    const double t0 = R[9], t1 = R[10], t2 = R[11];
+    double pm0 = 0, pm1 = 0, pm2 = 0, qm0 = 0, qm1 = 0, qm2 = 0;
+    if (PASS == 1) { pm0 = mean[0]; pm1 = mean[1]; pm2 = mean[2]; qm0 = mean[3]; qm1 = mean[4]; qm2 = mean[5]; }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const double px = a[3 * i], py = a[3 * i + 1], pz = a[3 * i + 2];
+        const double qx = b[3 * i], qy = b[3 * i + 1], qz = b[3 * i + 2];
+        const double e0 = ((px * r0 + py * r1) + pz * r2) + t0 - qx;
+        const double e1 = ((px * r3 + py * r4) + pz * r5) + t1 - qy;
+        const double e2 = ((px * r6 + py * r7) + pz * r8) + t2 - qz;
+        const double s = (e0 * e0 + e1 * e1) + e2 * e2;
+        if (!(s <= lo || (s < hi && sqrt(s) <= thr))) continue;
+        if (PASS == 0) {
+            acc[0] += 1.0;
+            acc[1] += px; acc[2] += py; acc[3] += pz;
+            acc[4] += qx; acc[5] += qy; acc[6] += qz;
+        } else {
+            const double ux = px - pm0, uy = py - pm1, uz = pz - pm2;
+            const double vx = qx - qm0, vy = qy - qm1, vz = qz - qm2;
+            acc[0] += ux * vx; acc[1] += ux * vy; acc[2] += ux * vz;
+            acc[3] += uy * vx; acc[4] += uy * vy; acc[5] += uy * vz;
+            acc[6] += uz * vx; acc[7] += uz * vy; acc[8] += uz * vz;
+            acc[NV - 1] += s;
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        double x = acc[v];
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+        if (lane == 0) sh[wave][v] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < NV)
+        partial[(size_t)blockIdx.x * K11_NV + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+
+// the block partials folded in block order into sums[24] (layout: sf_ransac_refit_sums); pass 0 also leaves the centroids
+__global__ __launch_bounds__(64) void k11_sums_final(const double *__restrict__ partial, int nblocks, int pass, double *__restrict__ sums)
+{
+    const int v = threadIdx.x, nv = pass == 0 ? 7 : 10;
+    double x = 0.0;
+    if (v < nv)
+        for (int blk = 0; blk < nblocks; ++blk) x += partial[(size_t)blk * K11_NV + v];
+    const double cnt = __shfl(x, 0);
+    if (pass == 0) {
+        if (v == 0) { sums[0] = x; sums[23] = 0.0; }
+        if (v >= 1 && v < 7) { sums[16 + v] = x; sums[v] = cnt > 0.0 ? x / cnt : 0.0; }
+    } else if (v < 10) {
+        sums[7 + v] = x;
+    }
+}
+
+int launch_hypotheses(sf_ctx *ctx, const char *who, const double *a, const double *b, int64_t m, const int64_t *draws,
+                      int64_t n_draws, int draw_size, double sim, unsigned char *status, double *Rt)
+{
+    if (draw_size < SF_RANSAC_MIN_DRAW_SIZE || draw_size > SF_RANSAC_MAX_DRAW_SIZE) {
+        sf_set_error("%s: draw_size %d outside %d .. %d", who, draw_size, SF_RANSAC_MIN_DRAW_SIZE, SF_RANSAC_MAX_DRAW_SIZE);
+        return SF_ERR_UNSUPPORTED;
+    }
+    if (!(sim >= 0.0 && sim < 1.0)) { sf_set_error("%s: edge_similarity %g outside [0, 1)", who, sim); return SF_ERR_ARG; }
+    if (n_draws > K11_MAX_DRAWS) { sf_set_error("%s: more than 65535 x 8192 draws", who); return SF_ERR_UNSUPPORTED; }
+    if (n_draws && m < draw_size) { sf_set_error("%s: %lld matches, fewer than the draw size %d", who, (long long)m, draw_size); return SF_ERR_ARG; }
+    if (!n_draws) return SF_OK;
+    SF_LAUNCH(ctx, "k11_hypotheses", k11_hypotheses, dim3((unsigned)sf_div_up(n_draws, 64)), dim3(64), a, b, m, draws, n_draws,
+              draw_size, sim, status, Rt);
+    return SF_OK;
+}
+
+} // namespace
+
+extern "C" int sf_ransac_hypotheses(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const int64_t *draws_dev,
+                                    int64_t n_draws, int draw_size, double edge_similarity, unsigned char *status_dev,
+                                    double *Rt_dev)
+{
+    if (!ctx || !a_dev || !b_dev || !draws_dev || !status_dev || !Rt_dev || m < 0 || n_draws < 0) {
+        sf_set_error("sf_ransac_hypotheses: bad argument");
+        return SF_ERR_ARG;
+    }
+    SF_HIP(hipSetDevice(ctx->device));
+    return launch_hypotheses(ctx, "sf_ransac_hypotheses", a_dev, b_dev, m, draws_dev, n_draws, draw_size, edge_similarity,
+                             status_dev, Rt_dev);
+}
+
+extern "C" int sf_ransac_refit_sums(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const double *Rt, double thr,
+                                    double *sums)
+{
+    if (!ctx || !a_dev || !b_dev || !Rt || !sums || m < 0) { sf_set_error("sf_ransac_refit_sums: bad argument"); return SF_ERR_ARG; }
+    SF_HIP(hipSetDevice(ctx->device));
+    for (int i = 0; i < 24; ++i) sums[i] = 0.0;
+    if (!m) return SF_OK;
+    sf_pool_guard tmp(ctx);
+    double *dRt = nullptr, *partial = nullptr, *dsums = nullptr;
+    SF_CHECK(tmp.alloc(&dRt, 12));
+    SF_CHECK(tmp.alloc(&partial, (size_t)K11_SUM_BLOCKS * K11_NV));
+    SF_CHECK(tmp.alloc(&dsums, 24));
+    SF_HIP(hipMemcpyAsync(dRt, Rt, 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    double lo, hi;
+    sf_ransac_band(thr, &lo, &hi);
+    const dim3 grid(K11_SUM_BLOCKS), block(256);
+    SF_LAUNCH(ctx, "k11_pair_sums", k11_pair_sums<0>, grid, block, a_dev, b_dev, m, (const double *)dRt, thr, lo, hi,
+              (const double *)nullptr, partial);
+    SF_LAUNCH(ctx, "k11_sums_final", k11_sums_final, dim3(1), dim3(64), (const double *)partial, K11_SUM_BLOCKS, 0, dsums);
+    SF_LAUNCH(ctx, "k11_pair_sums", k11_pair_sums<1>, grid, block, a_dev, b_dev, m, (const double *)dRt, thr, lo, hi,
+              (const double *)(dsums + 1), partial);
+    SF_LAUNCH(ctx, "k11_sums_final", k11_sums_final, dim3(1), dim3(64), (const double *)partial, K11_SUM_BLOCKS, 1, dsums);
+    SF_HIP(hipMemcpyAsync(sums, dsums, 24 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream)); // Rt and sums are host buffers
+    return SF_OK;
+}
+
+extern "C" int sf_ransac_prerejective(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const int64_t *draws_dev,
+                                      int64_t n_draws, int draw_size, double edge_similarity, double thr,
+                                      unsigned char *status_dev, double *Rt_dev, int64_t *map_dev, int64_t *counts_dev,
+                                      int64_t *result, double *best_Rt)
+{
+    if (!ctx || !a_dev || !b_dev || !draws_dev || !result || !best_Rt || m < 0 || n_draws < 0) {
+        sf_set_error("sf_ransac_prerejective: bad argument");
+        return SF_ERR_ARG;
+    }
+    SF_HIP(hipSetDevice(ctx->device));
+    for (int i = 0; i < 8; ++i) result[i] = 0;
+    result[3] = result[5] = -1;
+    for (int i = 0; i < 12; ++i) best_Rt[i] = 0.0;
+    sf_pool_guard tmp(ctx);
+    const size_t nd = (size_t)std::max<int64_t>(n_draws, 1);
+    const int64_t nblocks = sf_div_up(n_draws, K11_BLOCK);
+    double *Rt_all = nullptr, *dbest = nullptr;
+    int *block_count = nullptr;
+    int64_t *block_off = nullptr, *dwin = nullptr;
+    unsigned long long *tallies = nullptr;
+    if (!status_dev) SF_CHECK(tmp.alloc(&status_dev, nd));
+    if (!Rt_dev) SF_CHECK(tmp.alloc(&Rt_dev, nd * 12));
+    if (!map_dev) SF_CHECK(tmp.alloc(&map_dev, nd));
+    if (!counts_dev) SF_CHECK(tmp.alloc(&counts_dev, nd));
+    SF_CHECK(tmp.alloc(&Rt_all, nd * 12));
+    SF_CHECK(tmp.alloc(&block_count, (size_t)std::max<int64_t>(nblocks, 1)));
+    SF_CHECK(tmp.alloc(&block_off, (size_t)std::max<int64_t>(nblocks, 1)));
+    SF_CHECK(tmp.alloc(&tallies, 4));
+    SF_CHECK(tmp.alloc(&dwin, 4));
+    SF_CHECK(tmp.alloc(&dbest, 12));
+    SF_CHECK(launch_hypotheses(ctx, "sf_ransac_prerejective", a_dev, b_dev, m, draws_dev, n_draws, draw_size, edge_similarity,
+                               status_dev, Rt_all));
+    if (!n_draws) return SF_OK;
+    SF_HIP(hipMemsetAsync(tallies, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    SF_LAUNCH(ctx, "k11_count", k11_count, dim3((unsigned)nblocks), dim3(K11_BLOCK), (const unsigned char *)status_dev, n_draws,
+              block_count, tallies);
+    SF_LAUNCH(ctx, "k11_scan", k11_scan, dim3(1), dim3(256), (const int *)block_count, nblocks, block_off, tallies);
+    SF_LAUNCH(ctx, "k11_scatter", k11_scatter, dim3((unsigned)nblocks), dim3(K11_BLOCK), (const unsigned char *)status_dev,
+              (const double *)Rt_all, n_draws, (const int64_t *)block_off, Rt_dev, map_dev);
+    // the number of survivors sizes K9's launch: the one read-back between the two halves
+    void *pin = nullptr;
+    SF_CHECK(sf_ctx_pinned(ctx, &pin));
+    unsigned long long *ht = (unsigned long long *)pin;
+    SF_HIP(hipMemcpyAsync(ht, tallies, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    const int64_t n_scored = (int64_t)ht[0], n_rej = (int64_t)ht[1], n_deg = (int64_t)ht[2], n_bad = (int64_t)ht[3];
+    result[0] = n_rej; result[1] = n_deg; result[2] = n_scored; result[6] = n_bad;
+    if (n_bad) {
+        sf_set_error("sf_ransac_prerejective: %lld draws name a match outside [0, %lld)", (long long)n_bad, (long long)m);
+        return SF_ERR_ARG;
+    }
+    if (!n_scored) return SF_OK;
+    SF_CHECK(sf_ransac_score(ctx, a_dev, b_dev, m, Rt_dev, n_scored, thr, counts_dev, SF_IN_DEVICE | SF_OUT_DEVICE));
+    SF_LAUNCH(ctx, "k11_argmax", k11_argmax, dim3(1), dim3(1024), (const int64_t *)counts_dev, n_scored, (const int64_t *)map_dev,
+              (const double *)Rt_dev, dwin, dbest);
+    int64_t *hw = (int64_t *)pin;
+    double *hb = (double *)((char *)pin + 64);
+    SF_HIP(hipMemcpyAsync(hw, dwin, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipMemcpyAsync(hb, dbest, 12 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    result[5] = hw[0]; result[3] = hw[1]; result[4] = hw[2];
+    memcpy(best_Rt, hb, 12 * sizeof(double));
+    return SF_OK;
+}

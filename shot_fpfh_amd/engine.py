@@ -476,6 +476,47 @@ class Engine:
                                             SF_IN_DEVICE | SF_OUT_DEVICE), "sf_ransac_score")
         return out
 
+    # ---- RANSAC with pre-rejection (K11) ------------------------------------------------------------
+    def ransac_hypotheses_device(self, a: DeviceArray, b: DeviceArray, m: int, draws: DeviceArray, n_draws: int, draw_size: int,
+                                 edge_similarity: float, status: DeviceArray, rt: DeviceArray) -> None:
+        """sf_ransac_hypotheses on resident operands, asynchronous: draws (n_draws, draw_size) int64 -> status (n_draws,) uint8
+        (0 transform, 1 rejected by the edge test, 2 degenerate, 3 index out of range) and rt (n_draws, 12)."""
+        if (draws.dtype != np.int64 or draws.nbytes < n_draws * draw_size * 8 or status.dtype != np.uint8 or status.nbytes < n_draws
+                or rt.dtype != np.float64 or rt.nbytes < n_draws * 96 or a.shape[0] < m or b.shape[0] < m):
+            raise ValueError("ransac_hypotheses_device: operands smaller than the counts given")
+        _ffi.check(self.lib.sf_ransac_hypotheses(self.h, a.ptr, b.ptr, int(m), draws.ptr, int(n_draws), int(draw_size),
+                                                 float(edge_similarity), status.ptr, rt.ptr), "sf_ransac_hypotheses")
+
+    def ransac_refit_sums(self, a: DeviceArray, b: DeviceArray, m: int, rt, thr: float) -> np.ndarray:
+        """sf_ransac_refit_sums: the 24 sums of a Kabsch fit over the inliers of the transform `rt` (12 doubles, host):
+        [0] count, [1:4] abar, [4:7] bbar, [7:16] centred cross-covariance, [16] sum of squared residuals, [17:20] sum a, [20:23] sum b."""
+        rt = np.ascontiguousarray(rt, dtype=np.float64).reshape(12)
+        if a.shape[0] < m or b.shape[0] < m:
+            raise ValueError("ransac_refit_sums: operands smaller than the count given")
+        sums = np.zeros(24, dtype=np.float64)
+        _ffi.check(self.lib.sf_ransac_refit_sums(self.h, a.ptr, b.ptr, int(m), _ptr(rt), float(thr), _ptr(sums)), "sf_ransac_refit_sums")
+        return sums
+
+    def ransac_prerejective_device(self, a: DeviceArray, b: DeviceArray, m: int, draws: DeviceArray, n_draws: int, draw_size: int,
+                                   edge_similarity: float, thr: float, *, status: Optional[DeviceArray] = None,
+                                   rt: Optional[DeviceArray] = None, slot_draw: Optional[DeviceArray] = None,
+                                   counts: Optional[DeviceArray] = None) -> tuple[np.ndarray, np.ndarray]:
+        """sf_ransac_prerejective: hypotheses, order-preserving compaction, K9 and the first maximum in one call.  Returns
+        (result, best_rt): result = [rejected, degenerate, scored, winning draw or -1, its inlier count, its slot, 0, 0] (int64) and
+        the winner's 12 doubles.  The optional resident outputs receive the status bytes, the compacted transforms, the slot -> draw
+        map and K9's counts per slot (each sized for n_draws rows)."""
+        if draws.dtype != np.int64 or draws.nbytes < n_draws * draw_size * 8 or a.shape[0] < m or b.shape[0] < m:
+            raise ValueError("ransac_prerejective_device: operands smaller than the counts given")
+        for arr, dt, row in ((status, np.uint8, 1), (rt, np.float64, 96), (slot_draw, np.int64, 8), (counts, np.int64, 8)):
+            if arr is not None and (arr.dtype != dt or arr.nbytes < n_draws * row):
+                raise ValueError("ransac_prerejective_device: an output array of the wrong type or smaller than n_draws rows")
+        result, best = np.zeros(8, dtype=np.int64), np.zeros(12, dtype=np.float64)
+        opt = [None if x is None else x.ptr for x in (status, rt, slot_draw, counts)]
+        _ffi.check(self.lib.sf_ransac_prerejective(self.h, a.ptr, b.ptr, int(m), draws.ptr, int(n_draws), int(draw_size),
+                                                   float(edge_similarity), float(thr), *opt, _ptr(result), _ptr(best)),
+                   "sf_ransac_prerejective")
+        return result, best
+
     # ---- multi-GPU (RCCL) -------------------------------------------------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)

@@ -28,6 +28,7 @@ from scipy.spatial.transform import Rotation
 
 from . import _ffi
 from .core import RigidTransform, grid_subsampling
+from .core.geometry import kabsch_from_covariance
 from .engine import Cloud, DeviceArray, Engine, default_engine
 
 __all__ = [
@@ -66,13 +67,7 @@ class _PairSums:
 def _rigid_fit(s: _PairSums) -> RigidTransform:
     """Kabsch from the centred cross-covariance (core/solvers.py:9-30: same SVD, same reflection rule)."""
     s.require_pairs()
-    u, _, vt = np.linalg.svd(s.cross_cov)
-    rot = vt.T @ u.T
-    if np.linalg.det(rot) < 0:
-        ut = u.T.copy()
-        ut[-1] *= -1
-        rot = vt.T @ ut
-    return RigidTransform(rot, s.sum_q / s.count - rot.dot(s.sum_p / s.count))
+    return kabsch_from_covariance(s.cross_cov, s.sum_p / s.count, s.sum_q / s.count)
 
 
 def _plane_fit(s: _PairSums) -> RigidTransform:

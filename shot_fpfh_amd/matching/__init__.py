@@ -1,7 +1,7 @@
 """GPU drop-ins for shot_fpfh.matching (reference matching/__init__.py:1-19)."""
 from .filters import FilterFunction, left_median_filter, quantile_filter, threshold_filter
 from .match import basic_matching, double_matching_with_rejects, match_descriptors, match_two_nearest, ratio_test_matching
-from .ransac import ransac_on_matches
+from .ransac import RansacRecord, ransac_on_matches, ransac_prerejective
 
 __all__ = [
     "FilterFunction",
@@ -14,4 +14,6 @@ __all__ = [
     "match_two_nearest",
     "ratio_test_matching",
     "ransac_on_matches",
+    "ransac_prerejective",
+    "RansacRecord",
 ]

@@ -7,20 +7,25 @@ output, `draw_stream`) and one Kabsch fit per draw -- solved in stacks through t
 routines (bit-identical transforms, checked against the per-draw solver on a sample of every stack).
 Device: the gather keypoints[indices] of all matches and (K9) the O(n_draws x n_matches) inlier count of
 every candidate transform, a chunk of draws per launch while the host fits the next chunk.
+
+`ransac_prerejective` is a second coarse registration beside it, not in the reference: the draws of a generator of its own go to
+the device, which drops the samples whose edge lengths disagree, fits the others (K11, csrc/ransac.hip), scores the survivors
+with K9 and returns the first best; the winner is then refitted over all its inliers.
 """
 from __future__ import annotations
 
 import logging
+from dataclasses import dataclass, field
 from typing import Optional
 
 import numpy as np
 import numpy.typing as npt
 
 from ..core import RigidTransform, solver_point_to_point
-from ..core.geometry import solver_point_to_point_batched
+from ..core.geometry import kabsch_from_covariance, solver_point_to_point_batched
 from ..engine import Engine, default_engine
 
-__all__ = ["ransac_on_matches", "rng"]
+__all__ = ["ransac_on_matches", "ransac_prerejective", "RansacRecord", "draw_stream", "rng"]
 
 # same seed and same persistence across calls as the reference module's generator
 rng = np.random.default_rng(seed=72)
@@ -193,6 +198,7 @@ def ransac_on_matches(
     # (2 x 24 MB + 2 x 8 MB at the link's rate) and the gather keypoints[indices] runs on the device -- on the host it is two
     # scattered passes over 10^6 rows, 40-300 ms.  The host needs the 4 matched pairs of each DRAW only.
     matched = _matched_points_on_device(eng, scan_kp, scan_idx, ref_kp, ref_idx)
+    pending: list = []
     try:
         scan_d = np.ascontiguousarray(scan_kp[scan_idx[draws]], dtype=np.float64)
         ref_d = np.ascontiguousarray(ref_kp[ref_idx[draws]], dtype=np.float64)
@@ -200,7 +206,6 @@ def ransac_on_matches(
         inliers = np.empty(n_draws, dtype=np.int64)
         # chunks of draws: the Kabsch fits of chunk c + 1 (host: LAPACK, ~2.5 us per draw) run while K9 scores chunk c
         chunk = max(1024, -(-n_draws // 4))
-        pending = []
         for c0 in range(0, n_draws, chunk):
             c1 = min(c0 + chunk, n_draws)
             _solve_chunk(scan_d[c0:c1], ref_d[c0:c1], records[c0:c1])
@@ -208,6 +213,8 @@ def ransac_on_matches(
         for (c0, job) in zip(range(0, n_draws, chunk), pending):
             inliers[c0:c0 + job.n] = job.result()
     finally:
+        for job in pending:  # (an error between two chunks: the jobs nobody asked for their result hold two buffers each)
+            job.free()
         matched.free()
     best = int(np.argmax(inliers))  # first maximum == reference's strict-greater update rule
     if verbose:
@@ -215,6 +222,108 @@ def ransac_on_matches(
     best_transform = RigidTransform(records[best, :9].reshape(3, 3).copy(), records[best, 9:].copy())
     best_transform.normalize_rotation()
     return inliers[best] / n_matches, best_transform
+
+
+@dataclass
+class RansacRecord:
+    """What `ransac_prerejective` did: how the draws fell, who won, and the inlier count the winner started with and had after
+    each refit that was kept."""
+
+    n_draws: int = 0
+    n_rejected: int = 0    # by the edge-length test
+    n_degenerate: int = 0  # no unique rotation (collinear or coincident sample)
+    n_scored: int = 0
+    winner_draw: int = -1
+    winner_inliers: int = 0
+    refit_inliers: list = field(default_factory=list)
+
+
+def ransac_prerejective(
+    scan_descriptors_indices: npt.NDArray[np.integer],
+    ref_descriptors_indices: npt.NDArray[np.integer],
+    scan_keypoints: npt.NDArray[np.float64],
+    ref_keypoints: npt.NDArray[np.float64],
+    n_draws: int = 10000,
+    draw_size: int = 3,
+    distance_threshold: float = 1,
+    edge_similarity: float = 0.9,
+    refit_iterations: int = 2,
+    seed: int = 72,
+    verbose: bool = False,
+    *,
+    engine: Optional[Engine] = None,
+) -> tuple[float, RigidTransform, RansacRecord]:
+    """RANSAC with pre-rejection and a refit: (inlier ratio, RigidTransform with a re-normalised rotation, RansacRecord).
+
+    With a = scan_keypoints[scan_indices], b = ref_keypoints[ref_indices]:
+      1. n_draws samples of draw_size matches from a fresh np.random.default_rng(seed) (a call repeats on its own);
+      2. a sample is rejected unless every pair of it has edge lengths ea = |a_i - a_j|, eb = |b_i - b_j| with
+         ea >= edge_similarity * eb and eb >= edge_similarity * ea (a rigid motion keeps distances);
+      3. the others get their Kabsch fit on the device; samples without a unique rotation are left out;
+      4. the survivors are scored, in draw order, by the inlier count |a R^T + t - b| <= distance_threshold; the first
+         maximum wins;
+      5. refit_iterations times: Kabsch over ALL inliers of the current transform, kept while the inlier count does not drop,
+         stopped when it no longer changes (or fewer than 3 inliers are left).
+    Raises ValueError when there are fewer matches than draw_size, no draws, or no draw survives steps 2 and 3.
+    """
+    scan_idx, ref_idx = np.asarray(scan_descriptors_indices), np.asarray(ref_descriptors_indices)
+    n_matches = int(scan_idx.shape[0])
+    n_draws, draw_size, refit_iterations = int(n_draws), int(draw_size), int(refit_iterations)
+    if not 3 <= draw_size <= 8:
+        raise ValueError(f"draw_size must be 3 .. 8, got {draw_size}")
+    if not 0.0 <= edge_similarity < 1.0:
+        raise ValueError(f"edge_similarity must lie in [0, 1), got {edge_similarity}")
+    if refit_iterations < 0:
+        raise ValueError(f"refit_iterations must not be negative, got {refit_iterations}")
+    if n_draws <= 0:
+        raise ValueError(f"n_draws must be positive, got {n_draws}")
+    if ref_idx.shape[0] != n_matches:
+        raise ValueError(f"{n_matches} scan indices for {ref_idx.shape[0]} reference indices")
+    if n_matches < draw_size:
+        raise ValueError(f"{n_matches} matches are fewer than the draw size {draw_size}")
+    eng = engine or default_engine()
+    draws = draw_stream(np.random.default_rng(seed), n_matches, draw_size, n_draws)
+    thr = float(distance_threshold)
+    held = []
+    matched = _matched_points_on_device(eng, np.asarray(scan_keypoints), scan_idx, np.asarray(ref_keypoints), ref_idx)
+    try:
+        ddraws = eng.empty((n_draws, draw_size), np.int64)
+        held.append(ddraws)
+        ddraws.from_host(draws)
+        result, best = eng.ransac_prerejective_device(matched.a, matched.b, n_matches, ddraws, n_draws, draw_size,
+                                                      float(edge_similarity), thr)
+        record = RansacRecord(n_draws=n_draws, n_rejected=int(result[0]), n_degenerate=int(result[1]), n_scored=int(result[2]),
+                              winner_draw=int(result[3]), winner_inliers=int(result[4]))
+        if record.n_scored == 0:
+            raise ValueError(f"no draw survived: {record.n_rejected} of {n_draws} rejected by the edge test at similarity "
+                             f"{edge_similarity}, {record.n_degenerate} degenerate")
+        current, count = np.array(best, dtype=np.float64), record.winner_inliers
+        sums = eng.ransac_refit_sums(matched.a, matched.b, n_matches, current, thr) if refit_iterations else None
+        for _ in range(refit_iterations):
+            if int(sums[0]) < 3:
+                break
+            fit = kabsch_from_covariance(sums[7:16].reshape(3, 3), sums[1:4], sums[4:7]).as_row12()
+            if not np.isfinite(fit).all():
+                break
+            new_sums = eng.ransac_refit_sums(matched.a, matched.b, n_matches, fit, thr)
+            new_count = int(new_sums[0])
+            if new_count < count:
+                break
+            unchanged = new_count == count
+            current, count, sums = fit, new_count, new_sums
+            record.refit_inliers.append(new_count)
+            if unchanged:
+                break
+    finally:
+        for h in held:
+            h.free()
+        matched.free()
+    if verbose:
+        logging.info(f"Draw {record.winner_draw} of {record.n_scored} scored ({record.n_rejected} rejected): "
+                     f"{record.winner_inliers} inliers, after refits {record.refit_inliers}, out of {n_matches}")
+    transform = RigidTransform(current[:9].reshape(3, 3).copy(), current[9:].copy())
+    transform.normalize_rotation()
+    return count / n_matches, transform, record
 
 
 def _solve_chunk(scan_d: np.ndarray, ref_d: np.ndarray, records: np.ndarray) -> None:
@@ -242,8 +351,11 @@ class _ScoreJob:
         try:
             return self.out_dev.to_host()[: self.n]
         finally:
-            self.rt_dev.free()
-            self.out_dev.free()
+            self.free()
+
+    def free(self) -> None:
+        self.rt_dev.free()
+        self.out_dev.free()
 
 
 class _matched_points_on_device:
@@ -287,11 +399,20 @@ class _matched_points_on_device:
     def score_async(self, records: np.ndarray, thr: float) -> _ScoreJob:
         n = records.shape[0]
         rt = self.eng.empty((max(n, 1), 12))
-        out = self.eng.empty((max(n, 1),), np.int64)
-        if n:
-            rt.from_host(np.ascontiguousarray(records))
-            self.eng.ransac_score_device(self.a, self.b, self.m, rt, n, thr, out)
-        return _ScoreJob(self.eng, rt, out, n)
+        try:
+            out = self.eng.empty((max(n, 1),), np.int64)
+        except Exception:
+            rt.free()
+            raise
+        job = _ScoreJob(self.eng, rt, out, n)
+        try:
+            if n:
+                rt.from_host(np.ascontiguousarray(records))
+                self.eng.ransac_score_device(self.a, self.b, self.m, rt, n, thr, out)
+        except Exception:
+            job.free()
+            raise
+        return job
 
     def free(self) -> None:
         for h in self._held:

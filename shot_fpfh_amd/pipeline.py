@@ -25,6 +25,7 @@ from .matching import (
     double_matching_with_rejects,
     match_descriptors,
     ransac_on_matches,
+    ransac_prerejective,
     ratio_test_matching,
     threshold_filter,
 )
@@ -187,11 +188,25 @@ class RegistrationPipeline:
     # ---- stage 4: coarse registration (pipeline.py:445-486) ----------------------------------------------------
     def run_ransac(self, *, n_draws: int = 10000, draw_size: int = 4, max_inliers_distance: float = 2,
                    exact_transformation: RigidTransform | None = None,
-                   disable_progress_bar: bool = False) -> tuple[RigidTransform, float]:
+                   disable_progress_bar: bool = False, method: Literal["reference", "prerejective"] = "reference",
+                   edge_similarity: float = 0.9, refit_iterations: int = 2) -> tuple[RigidTransform, float]:
+        """method="reference": the reference's RANSAC.  method="prerejective": draws that fail the edge-length test at
+        `edge_similarity` are dropped unscored and the winner is refitted over its inliers `refit_iterations` times (three
+        points determine the fit: pass draw_size=3 there, the default of `ransac_prerejective` itself)."""
         logging.info(" -- Aligning the point clouds by RANSAC-ing the matches --")
-        inliers_ratio, transformation = ransac_on_matches(
-            *self.matches, self.scan[self.scan_keypoints], self.ref[self.ref_keypoints], n_draws=n_draws,
-            draw_size=draw_size, distance_threshold=max_inliers_distance, disable_progress_bar=disable_progress_bar)
+        if method == "reference":
+            inliers_ratio, transformation = ransac_on_matches(
+                *self.matches, self.scan[self.scan_keypoints], self.ref[self.ref_keypoints], n_draws=n_draws,
+                draw_size=draw_size, distance_threshold=max_inliers_distance,
+                disable_progress_bar=disable_progress_bar)
+        elif method == "prerejective":
+            inliers_ratio, transformation, record = ransac_prerejective(
+                *self.matches, self.scan[self.scan_keypoints], self.ref[self.ref_keypoints], n_draws=n_draws,
+                draw_size=draw_size, distance_threshold=max_inliers_distance,
+                edge_similarity=edge_similarity, refit_iterations=refit_iterations)
+            logging.info(f"{record.n_scored} of {record.n_draws} draws scored, inliers {record.winner_inliers} -> {record.refit_inliers}")
+        else:
+            raise ValueError("Incorrect RANSAC method selected.")
         if exact_transformation is not None:
             cosine = (np.trace(exact_transformation.rotation @ transformation.rotation.T) - 1) / 2
             logging.info(f"Norm of the angle between the two rotations: {abs(np.arccos(cosine)):.2f}\n"
