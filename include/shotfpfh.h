@@ -413,6 +413,32 @@ int sf_ransac_prerejective(sf_ctx *ctx, const double *a_dev, const double *b_dev
                            int64_t n_draws, int draw_size, double edge_similarity, double thr, unsigned char *status_dev,
                            double *Rt_dev, int64_t *map_dev, int64_t *counts_dev, int64_t *result /* 8 */, double *best_Rt /* 12 */);
 
+/* ---- fast global registration over given matches: K12 (no counterpart in the reference) --------------------------------------
+ * Zhou, Park, Koltun (ECCV 2016): a scaled Geman-McClure cost over the matched pairs, minimised by graduated non-convexity -- a
+ * fixed number of weighted Gauss-Newton steps on SE(3), no draws.  a_dev, b_dev: m x 3 matched points (DEVICE); sel_dev: NULL (the
+ * rows are matches 0 .. k-1, k <= m) or k int64 match ids (DEVICE, duplicates allowed; an id outside [0, m) is never dereferenced
+ * and makes the call return SF_ERR_ARG); k >= 3.  With ca, cb the means of the rows, s = max(max |a - ca|, max |b - cb|),
+ * x = (a - ca) / s, y = (b - cb) / s and the state R = I, t = 0, mu = 1, `iterations` times:
+ *     p = R x + t, r = p - y, l = mu / (mu + r.r), w = l^2, J = [-[p]x | I]:  A = sum w J^T J, g = sum w J^T r,
+ *     E = sum (w r.r + mu (l - 1)^2), W = sum w;  A xi = -g by LDL^T;  R <- exp([xi_0..2]x) R, t <- exp([xi_0..2]x) t + xi_3..5;
+ *     after every decrease_every-th iteration mu <- max(mu / division_factor, (distance_threshold / s)^2).
+ *   The sums are block partials folded in a fixed order (no atomics): a call repeats bit for bit.  All launches are queued on the
+ *   context's stream without a host wait in between; the call waits once, for the result.
+ * sf_fgr_sums: ONE pass at the state given (host, 20: ca (3), cb (3), s, R row-major (9), t (3), mu).  sums[32] (host): [0..20] A's
+ *   upper triangle row by row, [21..26] g, [27] E, [28] W, [29] the row count, [30], [31] 0.
+ * sf_fgr: the whole optimisation.  Rt[12] (host): R row-major and the denormalised t = s t + cb - R ca.  info[8] (host):
+ *   [0] status (0 done; 1 degenerate: a pivot d_j of A's LDL^T was not positive up to rounding, d_j <= 1e-12 A_jj -- the weighted
+ *   points do not determine a motion: all on one line, or within about 1e-6 of their extent of one -- and the transform of the
+ *   previous iteration is returned; 2 the rows have no extent or are not finite: no transform), [1] iterations
+ *   run, [2] final mu, [3] s, [4] E and [5] W of the last pass, [6], [7] 0.  trace (host, nullable): iterations x 4 rows
+ *   [mu, E, W, |xi|] of the iterations run, zeros after them.
+ *   SF_ERR_ARG: k < 3, iterations < 1, decrease_every < 1, division_factor <= 1, a threshold that is not finite. */
+int sf_fgr_sums(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const int64_t *sel_dev /* nullable */, int64_t k,
+                const double *state /* 20 */, double *sums /* 32 */);
+int sf_fgr(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const int64_t *sel_dev /* nullable */, int64_t k,
+           double distance_threshold, int iterations, int decrease_every, double division_factor, double *Rt /* 12 */,
+           double *info /* 8 */, double *trace /* nullable, iterations x 4 */);
+
 /* ---- voxel subsampling: grid_subsampling (core/subsampling.py:5-39) and the voxel loop of
  * select_keypoints_with_density_threshold (keypoint_selection.py:80-101) ---------------------------------
  * sf_voxels_build: keys ((p - min p) // voxel).astype(int) with NumPy's floor_divide, voxels ranked in np.unique's

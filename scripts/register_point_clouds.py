@@ -46,10 +46,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--reject-threshold", type=float, default=0.8), p.add_argument("--threshold-multiplier", type=float, default=10)
     p.add_argument("--ransac-draws", type=int, default=10000), p.add_argument("--ransac-draw-size", type=int, default=None,
                                                                             help="default 4 (reference), 3 (prerejective)")
-    p.add_argument("--ransac", default="reference", choices=["reference", "prerejective"],
-                   help="prerejective: drop draws whose edge lengths disagree before scoring, refit the winner over its inliers")
+    p.add_argument("--ransac", default="reference", choices=["reference", "prerejective", "fgr"],
+                   help="prerejective: drop draws whose edge lengths disagree before scoring, refit the winner over its inliers; "
+                        "fgr: fast global registration, no draws (--ransac-draws and --ransac-draw-size are ignored)")
     p.add_argument("--ransac-edge-similarity", type=float, default=0.9), p.add_argument("--ransac-refit", type=int, default=2)
     p.add_argument("--ransac-threshold", type=float, default=1.0)
+    p.add_argument("--fgr-iterations", type=int, default=64), p.add_argument("--fgr-tuples", type=int, default=0)
     p.add_argument("--icp", default="point_to_plane", choices=["point_to_point", "point_to_plane", "none"])
     p.add_argument("--icp-dmax", type=float, default=0.5), p.add_argument("--icp-voxel", type=float, default=0.2)
     p.add_argument("--icp-max-iter", type=int, default=50), p.add_argument("--icp-rms", type=float, default=1e-3)
@@ -79,7 +81,8 @@ def main(argv=None) -> int:
     transformation, inliers_ratio = pipe.run_ransac(n_draws=args.ransac_draws, draw_size=draw_size,
                                                     max_inliers_distance=args.ransac_threshold, disable_progress_bar=True,
                                                     method=args.ransac, edge_similarity=args.ransac_edge_similarity,
-                                                    refit_iterations=args.ransac_refit)
+                                                    refit_iterations=args.ransac_refit, fgr_iterations=args.fgr_iterations,
+                                                    fgr_tuple_count=args.fgr_tuples)
     logging.info(f"RANSAC inlier ratio {inliers_ratio:.3f}\n{transformation}")
     outputs = [(f"{args.write}_ransac.ply", transformation)] if args.write else []
     if args.icp != "none":

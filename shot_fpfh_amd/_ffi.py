@@ -112,6 +112,8 @@ SIGNATURES = {
     "sf_ransac_hypotheses": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _f64, _vp, _vp]),
     "sf_ransac_refit_sums": (_int, [_vp, _vp, _vp, _i64, _vp, _f64, _vp]),
     "sf_ransac_prerejective": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_fgr_sums": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "sf_fgr": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _f64, _int, _int, _f64, _vp, _vp, _vp]),
     "sf_voxels_build": (_vp, [_vp, _vp, _i64, _f64, _int]),
     "sf_voxels_count": (_i64, [_vp]),
     "sf_voxels_inverse": (_int, [_vp, _vp, _vp]),

@@ -517,6 +517,38 @@ class Engine:
                    "sf_ransac_prerejective")
         return result, best
 
+    # ---- fast global registration (K12) ---------------------------------------------------------------
+    @staticmethod
+    def _fgr_rows(who: str, a: DeviceArray, b: DeviceArray, m: int, sel: Optional[DeviceArray], k: Optional[int]) -> int:
+        k = int(m if sel is None and k is None else (sel.shape[0] if k is None else k))
+        if a.shape[0] < m or b.shape[0] < m or (sel is not None and (sel.dtype != np.int64 or sel.nbytes < 8 * k)):
+            raise ValueError(f"{who}: operands smaller than the counts given, or a selection that is not int64")
+        return k
+
+    def fgr_sums(self, a: DeviceArray, b: DeviceArray, m: int, state, sel: Optional[DeviceArray] = None,
+                 k: Optional[int] = None) -> np.ndarray:
+        """sf_fgr_sums: one pass of K12 over rows 0 .. k-1 (or the k match ids of `sel`) at the state given (20 host doubles:
+        ca, cb, s, R row-major, t, mu).  Returns 32 doubles: A's upper triangle (21), g (6), E, W, the row count, 0, 0."""
+        k = self._fgr_rows("fgr_sums", a, b, m, sel, k)
+        state = np.ascontiguousarray(state, dtype=np.float64).reshape(20)
+        sums = np.zeros(32, dtype=np.float64)
+        _ffi.check(self.lib.sf_fgr_sums(self.h, a.ptr, b.ptr, int(m), None if sel is None else sel.ptr, k, _ptr(state), _ptr(sums)),
+                   "sf_fgr_sums")
+        return sums
+
+    def fgr_device(self, a: DeviceArray, b: DeviceArray, m: int, distance_threshold: float, iterations: int = 64,
+                   decrease_every: int = 4, division_factor: float = 1.4, sel: Optional[DeviceArray] = None,
+                   k: Optional[int] = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """sf_fgr: the whole optimisation on resident matched points, one host wait.  Returns (Rt: 12 doubles, denormalised;
+        info: [status, iterations run, final mu, s, E, W, 0, 0]; trace: (iterations, 4) rows [mu, E, W, |xi|])."""
+        k = self._fgr_rows("fgr_device", a, b, m, sel, k)
+        rt, info = np.zeros(12, dtype=np.float64), np.zeros(8, dtype=np.float64)
+        trace = np.zeros((max(int(iterations), 1), 4), dtype=np.float64)
+        _ffi.check(self.lib.sf_fgr(self.h, a.ptr, b.ptr, int(m), None if sel is None else sel.ptr, k, float(distance_threshold),
+                                   int(iterations), int(decrease_every), float(division_factor), _ptr(rt), _ptr(info), _ptr(trace)),
+                   "sf_fgr")
+        return rt, info, trace
+
     # ---- multi-GPU (RCCL) -------------------------------------------------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)

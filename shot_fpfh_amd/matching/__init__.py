@@ -1,5 +1,6 @@
 """GPU drop-ins for shot_fpfh.matching (reference matching/__init__.py:1-19)."""
 from .filters import FilterFunction, left_median_filter, quantile_filter, threshold_filter
+from .fgr import FgrRecord, fast_global_registration
 from .match import basic_matching, double_matching_with_rejects, match_descriptors, match_two_nearest, ratio_test_matching
 from .ransac import RansacRecord, ransac_on_matches, ransac_prerejective
 
@@ -16,4 +17,6 @@ __all__ = [
     "ransac_on_matches",
     "ransac_prerejective",
     "RansacRecord",
+    "fast_global_registration",
+    "FgrRecord",
 ]

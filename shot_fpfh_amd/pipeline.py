@@ -24,6 +24,7 @@ from .matching import (
     basic_matching,
     double_matching_with_rejects,
     match_descriptors,
+    fast_global_registration,
     ransac_on_matches,
     ransac_prerejective,
     ratio_test_matching,
@@ -188,11 +189,14 @@ class RegistrationPipeline:
     # ---- stage 4: coarse registration (pipeline.py:445-486) ----------------------------------------------------
     def run_ransac(self, *, n_draws: int = 10000, draw_size: int = 4, max_inliers_distance: float = 2,
                    exact_transformation: RigidTransform | None = None,
-                   disable_progress_bar: bool = False, method: Literal["reference", "prerejective"] = "reference",
-                   edge_similarity: float = 0.9, refit_iterations: int = 2) -> tuple[RigidTransform, float]:
+                   disable_progress_bar: bool = False, method: Literal["reference", "prerejective", "fgr"] = "reference",
+                   edge_similarity: float = 0.9, refit_iterations: int = 2, fgr_iterations: int = 64,
+                   fgr_tuple_count: int = 0) -> tuple[RigidTransform, float]:
         """method="reference": the reference's RANSAC.  method="prerejective": draws that fail the edge-length test at
         `edge_similarity` are dropped unscored and the winner is refitted over its inliers `refit_iterations` times (three
-        points determine the fit: pass draw_size=3 there, the default of `ransac_prerejective` itself)."""
+        points determine the fit: pass draw_size=3 there, the default of `ransac_prerejective` itself).  method="fgr": fast global
+        registration, which draws nothing -- `max_inliers_distance` is its threshold, `n_draws` and `draw_size` are ignored,
+        `fgr_iterations` Gauss-Newton steps are taken over all matches (or over `fgr_tuple_count` tuples of them)."""
         logging.info(" -- Aligning the point clouds by RANSAC-ing the matches --")
         if method == "reference":
             inliers_ratio, transformation = ransac_on_matches(
@@ -205,6 +209,11 @@ class RegistrationPipeline:
                 draw_size=draw_size, distance_threshold=max_inliers_distance,
                 edge_similarity=edge_similarity, refit_iterations=refit_iterations)
             logging.info(f"{record.n_scored} of {record.n_draws} draws scored, inliers {record.winner_inliers} -> {record.refit_inliers}")
+        elif method == "fgr":
+            inliers_ratio, transformation, fgr_record = fast_global_registration(
+                *self.matches, self.scan[self.scan_keypoints], self.ref[self.ref_keypoints],
+                distance_threshold=max_inliers_distance, iterations=fgr_iterations, tuple_count=fgr_tuple_count)
+            logging.info(f"{fgr_record.iterations} iterations over {fgr_record.rows} rows, {fgr_record.inliers} inliers")
         else:
             raise ValueError("Incorrect RANSAC method selected.")
         if exact_transformation is not None:
