@@ -439,6 +439,29 @@ int sf_fgr(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, con
            double distance_threshold, int iterations, int decrease_every, double division_factor, double *Rt /* 12 */,
            double *info /* 8 */, double *trace /* nullable, iterations x 4 */);
 
+/* ---- geometric-consistency filter of a set of matches: K13 (no counterpart in the reference) ----------------------------------
+ * A rigid motion keeps lengths: matches i and j can both be true only if |a_i - a_j| and |b_i - b_j| agree within the noise.
+ * a_dev, b_dev: m x 3 matched points (DEVICE), m <= 2^31 - 1.  In unfused float64, in this order:
+ *     dp(i,j) = sqrt(((ax_i - ax_j)^2 + (ay_i - ay_j)^2) + (az_i - az_j)^2),  dq(i,j) the same on b;
+ *     compat(i,j) = i != j and |dp - dq| <= distance_threshold and min(dp, dq) >= min_edge     (any comparison with a NaN is
+ *     false: a row that is not finite is compatible with nothing);
+ *     degree[i] = #{ j : member[j] and compat(i,j) }.
+ *   Every result is an integer decided in float64 and summed with integer adds: exact, and the same on every call.
+ * sf_consistency_degree: degree_out_dev (m uint32) over the columns j with member_dev[j] != 0 (m bytes; NULL: all columns).
+ *   Asynchronous on the context's stream.
+ * sf_consistency_group: degree_dev <- the degree over all columns; seed = the LOWEST index among its maxima; member_dev[j] <-
+ *   compat(seed, j), member_dev[seed] <- 1; g = sum member; group_degree_dev <- the degree over the member columns.  Five
+ *   launches queued without a host wait in between; the call waits once, for info (host, 4 int64): [0] seed, [1] its degree,
+ *   [2] g, [3] status (0: a group; 1: no compatible pair -- then seed = -1, g = 0, member and group_degree are all zero).
+ *   SF_ERR_ARG: a NULL pointer (but member_dev of sf_consistency_degree), m < 0, m > 2^31 - 1, a distance_threshold or min_edge that
+ *   is negative or not finite.  m = 0: SF_OK, nothing is written. */
+int sf_consistency_degree(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m,
+                          const unsigned char *member_dev /* nullable */, double distance_threshold, double min_edge,
+                          unsigned *degree_out_dev);
+int sf_consistency_group(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, double distance_threshold,
+                         double min_edge, unsigned *degree_dev, unsigned char *member_dev, unsigned *group_degree_dev,
+                         int64_t *info /* 4 */);
+
 /* ---- voxel subsampling: grid_subsampling (core/subsampling.py:5-39) and the voxel loop of
  * select_keypoints_with_density_threshold (keypoint_selection.py:80-101) ---------------------------------
  * sf_voxels_build: keys ((p - min p) // voxel).astype(int) with NumPy's floor_divide, voxels ranked in np.unique's

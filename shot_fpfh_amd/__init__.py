@@ -10,7 +10,14 @@ from ._ffi import ShotFpfhError
 from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor, compute_normals
 from .engine import Cloud, DeviceArray, Engine, Neighbors, Spfh, default_engine
 from .helpers import get_data, read_ply, write_ply
-from .matching import basic_matching, fast_global_registration, match_descriptors, ransac_on_matches, ransac_prerejective
+from .matching import (
+    basic_matching,
+    fast_global_registration,
+    geometric_consistency_filter,
+    match_descriptors,
+    ransac_on_matches,
+    ransac_prerejective,
+)
 from .pipeline import RegistrationPipeline
 
 __all__ = [
@@ -29,6 +36,7 @@ __all__ = [
     "ransac_on_matches",
     "ransac_prerejective",
     "fast_global_registration",
+    "geometric_consistency_filter",
     "RegistrationPipeline",
     "read_ply",
     "write_ply",

@@ -114,6 +114,8 @@ SIGNATURES = {
     "sf_ransac_prerejective": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _int, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_fgr_sums": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sf_fgr": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _f64, _int, _int, _f64, _vp, _vp, _vp]),
+    "sf_consistency_degree": (_int, [_vp, _vp, _vp, _i64, _vp, _f64, _f64, _vp]),
+    "sf_consistency_group": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "sf_voxels_build": (_vp, [_vp, _vp, _i64, _f64, _int]),
     "sf_voxels_count": (_i64, [_vp]),
     "sf_voxels_inverse": (_int, [_vp, _vp, _vp]),

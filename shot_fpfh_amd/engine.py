@@ -549,6 +549,41 @@ class Engine:
                    "sf_fgr")
         return rt, info, trace
 
+    # ---- geometric-consistency filter (K13) -------------------------------------------------------------
+    @staticmethod
+    def _consistency_sizes(who: str, a: DeviceArray, b: DeviceArray, m: int, u32=(), u8=()) -> None:
+        if (a.shape[0] < m or b.shape[0] < m or any(x.dtype != np.uint32 or x.nbytes < 4 * m for x in u32)
+                or any(x.dtype != np.uint8 or x.nbytes < m for x in u8)):
+            raise ValueError(f"{who}: operands smaller than the count given, or a degree / member array of the wrong type")
+
+    def consistency_degree(self, a: DeviceArray, b: DeviceArray, m: int, distance_threshold: float, min_edge: float,
+                           member: Optional[DeviceArray] = None) -> np.ndarray:
+        """sf_consistency_degree on resident matched points: per match the number of columns j (of those with member[j] != 0,
+        uint8; None: all) whose lengths |a_i - a_j| and |b_i - b_j| agree within distance_threshold and are both at least
+        min_edge.  Returns m uint32."""
+        m = int(m)
+        self._consistency_sizes("consistency_degree", a, b, m, u8=() if member is None else (member,))
+        out = self.empty((max(m, 1),), np.uint32)
+        try:
+            _ffi.check(self.lib.sf_consistency_degree(self.h, a.ptr, b.ptr, m, None if member is None else member.ptr,
+                                                      float(distance_threshold), float(min_edge), out.ptr), "sf_consistency_degree")
+            return out.to_host()[:m]
+        finally:
+            out.free()
+
+    def consistency_group_device(self, a: DeviceArray, b: DeviceArray, m: int, distance_threshold: float, min_edge: float,
+                                 degree: DeviceArray, member: DeviceArray, group_degree: DeviceArray
+                                 ) -> tuple[DeviceArray, DeviceArray, DeviceArray, np.ndarray]:
+        """sf_consistency_group: degree, first maximum, the seed's row, its count and the degree inside the group, queued back to
+        back with one host wait.  `degree`, `group_degree` (m uint32) and `member` (m uint8) are resident outputs, handed back
+        with info = [seed, its degree, group size, status (1: no compatible pair, seed -1)] (int64)."""
+        m = int(m)
+        self._consistency_sizes("consistency_group_device", a, b, m, u32=(degree, group_degree), u8=(member,))
+        info = np.array([-1, 0, 0, 1], dtype=np.int64)  # (what stays for m = 0, where the library writes nothing)
+        _ffi.check(self.lib.sf_consistency_group(self.h, a.ptr, b.ptr, m, float(distance_threshold), float(min_edge), degree.ptr,
+                                                 member.ptr, group_degree.ptr, _ptr(info)), "sf_consistency_group")
+        return degree, member, group_degree, info
+
     # ---- multi-GPU (RCCL) -------------------------------------------------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)

@@ -1,4 +1,5 @@
 """GPU drop-ins for shot_fpfh.matching (reference matching/__init__.py:1-19)."""
+from .consistency import ConsistencyRecord, geometric_consistency_filter
 from .filters import FilterFunction, left_median_filter, quantile_filter, threshold_filter
 from .fgr import FgrRecord, fast_global_registration
 from .match import basic_matching, double_matching_with_rejects, match_descriptors, match_two_nearest, ratio_test_matching
@@ -19,4 +20,6 @@ __all__ = [
     "RansacRecord",
     "fast_global_registration",
     "FgrRecord",
+    "geometric_consistency_filter",
+    "ConsistencyRecord",
 ]

@@ -25,6 +25,7 @@ from .matching import (
     double_matching_with_rejects,
     match_descriptors,
     fast_global_registration,
+    geometric_consistency_filter,
     ransac_on_matches,
     ransac_prerejective,
     ratio_test_matching,
@@ -185,6 +186,18 @@ class RegistrationPipeline:
         if debug_mode:
             gap = np.linalg.norm(self.scan_descriptors[self.matches[0]] - self.ref_descriptors[self.matches[1]], axis=0)
             logging.info(f"Maximum distance between the descriptors matched: {gap.max(initial=0):.2f}")
+
+    def filter_matches_by_consistency(self, distance_threshold: float, min_edge: float | None = None,
+                                      group_share: float = 0.4) -> None:
+        """Keeps the matches that agree with each other on lengths within `distance_threshold` (`geometric_consistency_filter`,
+        not in the reference): `self.matches` is replaced by the kept ones, in their order."""
+        logging.info("-- Filtering the matches by geometric consistency --")
+        total = self.matches[0].shape[0]
+        scan_kept, ref_kept, record = geometric_consistency_filter(
+            *self.matches, self.scan[self.scan_keypoints], self.ref[self.ref_keypoints], distance_threshold=distance_threshold,
+            min_edge=min_edge, group_share=group_share)
+        self.matches = (scan_kept, ref_kept)
+        logging.info(f"{scan_kept.shape[0]} matches kept out of {total} ({record.status}, group of {record.group_size})")
 
     # ---- stage 4: coarse registration (pipeline.py:445-486) ----------------------------------------------------
     def run_ransac(self, *, n_draws: int = 10000, draw_size: int = 4, max_inliers_distance: float = 2,
