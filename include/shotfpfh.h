@@ -462,6 +462,33 @@ int sf_consistency_group(sf_ctx *ctx, const double *a_dev, const double *b_dev, 
                          double min_edge, unsigned *degree_dev, unsigned char *member_dev, unsigned *group_degree_dev,
                          int64_t *info /* 4 */);
 
+/* ---- second-order consistency of a set of matches (SC2; Chen, Sun, Yang, Tao, CVPR 2022): K14 ---------------------------------
+ * With compat(i,j) exactly as above:  C[i][j] = 1 if compat(i,j) else 0 (symmetric, zero diagonal);
+ *     s2[i] = sum_j C[i][j] sum_k C[i][k] C[j][k]       -- the pairs (j, k) compatible with i AND with each other, twice the
+ *     triangles through i in the compatibility graph.  True matches form a clique, accidental ones do not.
+ * The matrix is bytes, 16-byte aligned, m_pad x m_pad row-major with m_pad = SF_SC2_PAD(m) and every byte of the padding zero; m <=
+ * SF_SC2_MAX_MATCHES (a 1 GiB matrix, s2 < 2^30).  The m^3 sum is an integer GEMM on the int8 matrix cores: exact.
+ * sf_consistency_matrix: cmat_dev (m_pad x m_pad bytes, padding included) <- C.  Asynchronous.
+ * sf_consistency_sc2: s2_dev (m uint32) <- s2 of ANY matrix of 0 / 1 bytes in that layout, symmetric or not, with the formula
+ *   above (row i against row j, weighted by C[i][j]); other byte values, or a padding that is not zero, are unspecified.
+ *   Asynchronous.
+ * sf_consistency_sc2_group: the matrix (from the context's pool) and s2_dev; seed = the LOWEST index among the maxima of s2;
+ *   member_dev[j] <- compat(seed, j), member_dev[seed] <- 1; g = sum member; group_degree_dev <- the degree over the member
+ *   columns, as sf_consistency_group (for a member j other than the seed it is C[seed][j] N[seed][j] + 1).  Queued without a
+ *   host wait in between; the call waits once, for info (host, 4 int64): [0] seed, [1] s2[seed], [2] g, [3] status (0: a group;
+ *   1: no consistent triple -- then seed = -1, g = 0, member and group_degree are all zero).
+ *   SF_ERR_ARG: a NULL pointer, m < 0, m > SF_SC2_MAX_MATCHES (refused before anything is allocated), a distance_threshold or
+ *   min_edge that is negative or not finite.  m = 0: SF_OK, nothing is written. */
+#define SF_SC2_MAX_MATCHES 32768
+#define SF_SC2_TILE 256
+#define SF_SC2_PAD(m) (((m) + SF_SC2_TILE - 1) / SF_SC2_TILE * SF_SC2_TILE)
+int sf_consistency_matrix(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, double distance_threshold,
+                          double min_edge, unsigned char *cmat_dev);
+int sf_consistency_sc2(sf_ctx *ctx, const unsigned char *cmat_dev, int64_t m, unsigned *s2_dev);
+int sf_consistency_sc2_group(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, double distance_threshold,
+                             double min_edge, unsigned *s2_dev, unsigned char *member_dev, unsigned *group_degree_dev,
+                             int64_t *info /* 4 */);
+
 /* ---- voxel subsampling: grid_subsampling (core/subsampling.py:5-39) and the voxel loop of
  * select_keypoints_with_density_threshold (keypoint_selection.py:80-101) ---------------------------------
  * sf_voxels_build: keys ((p - min p) // voxel).astype(int) with NumPy's floor_divide, voxels ranked in np.unique's

@@ -44,8 +44,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--min-neighborhood-size", type=int, default=100)
     p.add_argument("--matching", default="simple", choices=["simple", "double", "threshold", "ratio"])
     p.add_argument("--reject-threshold", type=float, default=0.8), p.add_argument("--threshold-multiplier", type=float, default=10)
-    p.add_argument("--consistency", type=float, default=None, metavar="EPS",
-                   help="keep only the matches whose pairwise lengths agree within EPS on both sides before the registration (default: off)")
+    consistency = p.add_mutually_exclusive_group()
+    consistency.add_argument("--consistency", type=float, default=None, metavar="EPS",
+                             help="keep only the matches whose pairwise lengths agree within EPS on both sides before the registration (default: off)")
+    consistency.add_argument("--consistency-sc2", type=float, default=None, metavar="EPS",
+                             help="the same test, the group chosen by second-order consistency (triangles of the compatibility graph): "
+                                  "for sets with a few per cent of true matches, at most 32768 of them (default: off)")
     p.add_argument("--ransac-draws", type=int, default=10000), p.add_argument("--ransac-draw-size", type=int, default=None,
                                                                             help="default 4 (reference), 3 (prerejective)")
     p.add_argument("--ransac", default="reference", choices=["reference", "prerejective", "fgr"],
@@ -81,6 +85,8 @@ def main(argv=None) -> int:
     logging.info(f"{pipe.matches[0].shape[0]} matches")
     if args.consistency is not None:
         pipe.filter_matches_by_consistency(args.consistency)
+    if args.consistency_sc2 is not None:
+        pipe.filter_matches_by_second_order_consistency(args.consistency_sc2)
     draw_size = args.ransac_draw_size or (3 if args.ransac == "prerejective" else 4)
     transformation, inliers_ratio = pipe.run_ransac(n_draws=args.ransac_draws, draw_size=draw_size,
                                                     max_inliers_distance=args.ransac_threshold, disable_progress_bar=True,

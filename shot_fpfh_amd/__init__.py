@@ -17,6 +17,8 @@ from .matching import (
     match_descriptors,
     ransac_on_matches,
     ransac_prerejective,
+    second_order_consistency_filter,
+    SecondOrderRecord,
 )
 from .pipeline import RegistrationPipeline
 
@@ -37,6 +39,8 @@ __all__ = [
     "ransac_prerejective",
     "fast_global_registration",
     "geometric_consistency_filter",
+    "second_order_consistency_filter",
+    "SecondOrderRecord",
     "RegistrationPipeline",
     "read_ply",
     "write_ply",

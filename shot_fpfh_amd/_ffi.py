@@ -116,6 +116,9 @@ SIGNATURES = {
     "sf_fgr": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _f64, _int, _int, _f64, _vp, _vp, _vp]),
     "sf_consistency_degree": (_int, [_vp, _vp, _vp, _i64, _vp, _f64, _f64, _vp]),
     "sf_consistency_group": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "sf_consistency_matrix": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _vp]),
+    "sf_consistency_sc2": (_int, [_vp, _vp, _i64, _vp]),
+    "sf_consistency_sc2_group": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "sf_voxels_build": (_vp, [_vp, _vp, _i64, _f64, _int]),
     "sf_voxels_count": (_i64, [_vp]),
     "sf_voxels_inverse": (_int, [_vp, _vp, _vp]),

@@ -156,6 +156,209 @@ int k13_launch_degree(sf_ctx *ctx, const double *a, const double *b, int64_t m, 
     return SF_OK;
 }
 
+
+// ---- K14: second-order consistency (SC2, Chen et al. 2022) on the int8 matrix cores ----------------------------------------------
+// C[i][j] = compat(i, j) as a byte matrix, m_pad x m_pad with m_pad = m rounded up to K14_T and the padding zero;
+//   s2[i] = sum_j C[i][j] N[i][j],   N[i][j] = sum_k C[i][k] C[j][k]   (N = C C^T: both operands are ROWS of one matrix),
+// twice the triangles through i in the compatibility graph -- the definition of tests/sc2_numpy.py.  Integers throughout.
+//
+// k14_matrix is k13_degree's loop with a store in place of the count: compat is symmetric bit for bit (the squares of negated
+// differences are equal), so the thread that owns row i writes [c][i] and a wave's store is 64 consecutive bytes.
+//
+// k14_sc2 is the m^3 part, a K-loop GEMM on v_mfma_i32_32x32x32_i8.  A workgroup of 8 waves owns 256 x 256 outputs, a wave 64 x 128
+// (2 x 4 accumulators of 32 x 32: 128 registers).  Per step the 64-byte K-chunk of the tile's 256 + 256 rows (32 KB) goes from
+// global memory into one of two LDS buffers by LDS-DMA, four 1 KB instructions a wave.  The LDS image is lane-linear, row-major
+// with 64-byte rows; slot p of row r holds the 16-byte chunk p ^ ((r >> 2) & 3) -- the permutation is applied to the SOURCE
+// address of the DMA and to the fragment read alike -- so the 16 lanes of a fragment read (16 consecutive rows, one chunk) touch
+// 16 different 16-byte bank groups: rows r and r + 4 would share theirs otherwise.  Operand layout as k_i8_min (match_i8.hip):
+// lane (r31, h) holds bytes [16 h, 16 h + 16) of row r31 of the 32-deep step; accumulator register r is row (r & 3) + 8 (r >> 2) +
+// 4 h, column r31.  Epilogue: acc x C[row][col], summed over the wave's four column blocks in registers and over the 32 lanes of
+// a half by DPP, one integer atomicAdd per row and wave into s2 (zeroed in front).  Every s2 is below 2^30 at the cap.
+// Only the tiles J >= I are computed: N is symmetric for ANY C, so tile (I, J) with J > I also adds, per column j, the sum over
+// its rows of C[j][i] N[i][j] -- what tile (J, I) would have added to s2[j] -- from the same accumulators.
+typedef int k14_i4 __attribute__((ext_vector_type(4)));
+typedef int k14_i16 __attribute__((ext_vector_type(16)));
+constexpr int K14_T = SF_SC2_TILE;          // outputs of a workgroup along either axis; m_pad is a multiple of it
+constexpr int K14_KC = 64;                  // bytes of K per step and row
+constexpr int K14_BUF = 2 * K14_T * K14_KC; // one LDS buffer: the row tile's 256 rows, then the column tile's
+static_assert(K14_T == 256 && K14_T % K13_TILE == 0 && K14_T == K13_BLOCK, "the tile shapes below are written out for 256");
+
+// grid: (m_pad / K13_BLOCK row blocks, column slices); every byte of the m_pad x m_pad matrix is written, the padding as zero
+// (a row or column past m is NaN and compatible with nothing).
+__global__ __launch_bounds__(K13_BLOCK) void k14_matrix(const double *__restrict__ a, const double *__restrict__ b, int64_t m,
+                                                        int64_t m_pad, double thr, double min_edge, int tiles_per_slice,
+                                                        unsigned char *__restrict__ cmat)
+{
+    __shared__ __attribute__((aligned(16))) double col[K13_TILE * 6];
+    const double nan = __builtin_nan("");
+    const int64_t i = (int64_t)blockIdx.x * K13_BLOCK + threadIdx.x; // < m_pad
+    double ax = nan, ay = nan, az = nan, bx = nan, by = nan, bz = nan;
+    if (i < m) {
+        ax = a[3 * i]; ay = a[3 * i + 1]; az = a[3 * i + 2];
+        bx = b[3 * i]; by = b[3 * i + 1]; bz = b[3 * i + 2];
+    }
+    const int64_t tile0 = (int64_t)blockIdx.y * tiles_per_slice;
+    for (int t = 0; t < tiles_per_slice; ++t) {
+        const int64_t j0 = (tile0 + t) * K13_TILE;
+        if (j0 >= m_pad) break; // (the same for the whole block)
+        __syncthreads();
+        for (int e = threadIdx.x; e < 6 * K13_TILE; e += K13_BLOCK) {
+            const int side = e >= 3 * K13_TILE ? 1 : 0;
+            const int r = e - side * 3 * K13_TILE, c = r / 3;
+            double v = nan;
+            if (j0 + c < m) v = (side ? b : a)[3 * j0 + r];
+            col[6 * c + 3 * side + (r - 3 * c)] = v;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int c = 0; c < K13_TILE; ++c) { // (whole tiles: m_pad is a multiple of K13_TILE)
+            const double *q = col + 6 * c;
+            const bool ok = k13_compat(ax, ay, az, bx, by, bz, q[0], q[1], q[2], q[3], q[4], q[5], thr, min_edge);
+            cmat[(j0 + c) * m_pad + i] = (ok && j0 + c != i) ? 1 : 0;
+        }
+    }
+}
+
+#define K14_DMA16(GPTR, LDS_DST)                                                                                    \
+    {                                                                                                               \
+        unsigned keep_;                                                                                             \
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"       \
+                     "s_mov_b32 m0, %0"                                                                             \
+                     : "=&s"(keep_)                                                                                 \
+                     : "v"(GPTR), "s"(LDS_DST)                                                                      \
+                     : "memory");                                                                                   \
+    }
+// the K-chunk [K0, K0 + K14_KC) of the 512 rows into buffer BUF: instruction u of wave w fills rows 16 (w + 8 u) .. + 15
+#define K14_DMA(K0, BUF)                                                                                            \
+    {                                                                                                               \
+        const unsigned dst_ = lds_base + (unsigned)(BUF) * K14_BUF + 1024u * wave_u;                                \
+        _Pragma("unroll") for (int u = 0; u < 4; ++u) K14_DMA16(src[u] + (K0), dst_ + 8192u * u)                    \
+    }
+#define K14_FRAG(ROW0, KS) (*reinterpret_cast<const k14_i4 *>(bp + (ROW0) * K14_KC + roff[KS]))
+
+// grid: (row tiles, column tiles) of K14_T.  cmat: m_pad x m_pad bytes of 0 / 1 with zero padding; s2 (m uint32) is added to.
+__global__ __launch_bounds__(512, 1) void k14_sc2(const unsigned char *__restrict__ cmat, int64_t m, int64_t m_pad,
+                                                   unsigned *__restrict__ s2)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char Ls[2 * K14_BUF];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r31 = lane & 31, h = lane >> 5;
+    const int wr = wave >> 1, wc = wave & 1; // the wave's 64 rows x 128 columns of the tile
+    if (blockIdx.y < blockIdx.x) return; // N = C C^T is symmetric whatever C is: tile (J, I) is served by tile (I, J)'s columns
+    const bool mirror = blockIdx.y > blockIdx.x;
+    const int64_t row_tile = (int64_t)blockIdx.x * K14_T, col_tile = (int64_t)blockIdx.y * K14_T;
+    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)Ls;
+    const unsigned wave_u = (unsigned)__builtin_amdgcn_readfirstlane(wave);
+    const unsigned char *src[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int P = 64 * (wave + 8 * u) + lane, row = P >> 2, c = (P & 3) ^ ((row >> 2) & 3);
+        const int64_t grow = row < K14_T ? row_tile + row : col_tile + (row - K14_T);
+        src[u] = cmat + grow * m_pad + 16 * c;
+    }
+    unsigned roff[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) roff[ks] = (unsigned)(r31 * K14_KC + (((2 * ks + h) ^ ((r31 >> 2) & 3)) * 16));
+    k14_i16 acc[2][4];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 4; ++bj)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[bi][bj][r] = 0;
+    const int64_t nk = m_pad / K14_KC;
+    K14_DMA(0, 0)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int64_t kc = 0; kc < nk; ++kc) {
+        const int buf = (int)(kc & 1);
+        if (kc + 1 < nk) K14_DMA((kc + 1) * K14_KC, buf ^ 1)
+        const unsigned char *bp = Ls + buf * K14_BUF;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            k14_i4 fa[2], fb[4];
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi) fa[bi] = K14_FRAG(64 * wr + 32 * bi, ks);
+#pragma unroll
+            for (int bj = 0; bj < 4; ++bj) fb[bj] = K14_FRAG(K14_T + 128 * wc + 32 * bj, ks);
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int bj = 0; bj < 4; ++bj)
+                    acc[bi][bj] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[bi], fb[bj], acc[bi][bj], 0, 0, 0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's DMA pieces of the next chunk have landed
+        __syncthreads();
+    }
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t row = row_tile + 64 * wr + 32 * bi + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const unsigned char *crow = cmat + row * m_pad + col_tile + 128 * wc + r31;
+            int v = 0;
+#pragma unroll
+            for (int bj = 0; bj < 4; ++bj) v += acc[bi][bj][r] * (int)crow[32 * bj];
+            v = sf_row16_sum(v);
+            v += __shfl_xor(v, 16); // the two DPP rows of this 32-lane half
+            if (r31 == 0 && row < m && v) atomicAdd(&s2[row], (unsigned)v);
+        }
+    if (!mirror) return; // (the same for the whole block)
+    // the mirrored tile: s2[col] += sum_row C[col][row] N[row][col].  A lane owns a column; its rows of one accumulator are four
+    // runs of four consecutive bytes of C's row `col`.  Summed over registers, then over the two lane halves.
+#pragma unroll
+    for (int bj = 0; bj < 4; ++bj) {
+        const int64_t col = col_tile + 128 * wc + 32 * bj + r31;
+        const unsigned char *ccol = cmat + col * m_pad + row_tile + 64 * wr + 4 * h;
+        int v = 0;
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned w = *reinterpret_cast<const unsigned *>(ccol + 32 * bi + 8 * q); // rows 8 q + 4 h + (0 .. 3)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v += acc[bi][bj][4 * q + e] * (int)((w >> (8 * e)) & 0xffu);
+            }
+        v += __shfl_xor(v, 32);
+        if (h == 0 && col < m && v) atomicAdd(&s2[col], (unsigned)v);
+    }
+}
+#undef K14_DMA
+#undef K14_DMA16
+#undef K14_FRAG
+
+int k14_check_count(const char *who, bool pointers, int64_t m)
+{
+    if (!pointers || m < 0) { sf_set_error("%s: bad argument", who); return SF_ERR_ARG; }
+    if (m > SF_SC2_MAX_MATCHES) {
+        sf_set_error("%s: %lld matches, at most %d (the byte matrix is m^2)", who, (long long)m, SF_SC2_MAX_MATCHES);
+        return SF_ERR_ARG;
+    }
+    return SF_OK;
+}
+
+int64_t k14_pad(int64_t m) { return sf_div_up(m, K14_T) * K14_T; }
+
+int k14_launch_matrix(sf_ctx *ctx, const double *a, const double *b, int64_t m, double thr, double min_edge, unsigned char *cmat)
+{
+    const int64_t m_pad = k14_pad(m), row_blocks = m_pad / K13_BLOCK, tiles = m_pad / K13_TILE;
+    const int64_t want = std::min<int64_t>(tiles, std::max<int64_t>(1, sf_div_up(K13_TARGET_BLOCKS, row_blocks)));
+    const int tiles_per_slice = (int)sf_div_up(tiles, want);
+    const int64_t slices = sf_div_up(tiles, tiles_per_slice);
+    SF_LAUNCH(ctx, "k14_matrix", k14_matrix, dim3((unsigned)row_blocks, (unsigned)slices), dim3(K13_BLOCK), a, b, m, m_pad, thr, min_edge,
+              tiles_per_slice, cmat);
+    return SF_OK;
+}
+
+// s2_dev <- 0, then one launch: the tiles add into it.
+int k14_launch_sc2(sf_ctx *ctx, const unsigned char *cmat, int64_t m, unsigned *s2_dev)
+{
+    const int64_t m_pad = k14_pad(m), tiles = m_pad / K14_T; // <= 128
+    SF_HIP(hipMemsetAsync(s2_dev, 0, (size_t)m * sizeof(unsigned), ctx->stream));
+    SF_LAUNCH(ctx, "k14_sc2", k14_sc2, dim3((unsigned)tiles, (unsigned)tiles), dim3(512), cmat, m, m_pad, s2_dev);
+    return SF_OK;
+}
+
 } // namespace
 
 extern "C" int sf_consistency_degree(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m,
@@ -194,5 +397,58 @@ extern "C" int sf_consistency_group(sf_ctx *ctx, const double *a_dev, const doub
     SF_HIP(hipStreamSynchronize(ctx->stream)); // the one wait of the call
     for (int v = 0; v < IN_SIZE; ++v) info[v] = hi[v];
     if (info[IN_STATUS] != 0) info[IN_SEED] = -1; // no compatible pair: no seed, no group
+    return SF_OK;
+}
+
+extern "C" int sf_consistency_matrix(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, double distance_threshold,
+                                     double min_edge, unsigned char *cmat_dev)
+{
+    SF_CHECK(k13_check("sf_consistency_matrix", ctx && a_dev && b_dev && cmat_dev, m, distance_threshold, min_edge));
+    SF_CHECK(k14_check_count("sf_consistency_matrix", true, m));
+    if (m == 0) return SF_OK;
+    SF_HIP(hipSetDevice(ctx->device));
+    return k14_launch_matrix(ctx, a_dev, b_dev, m, distance_threshold, min_edge, cmat_dev);
+}
+
+extern "C" int sf_consistency_sc2(sf_ctx *ctx, const unsigned char *cmat_dev, int64_t m, unsigned *s2_dev)
+{
+    SF_CHECK(k14_check_count("sf_consistency_sc2", ctx && cmat_dev && s2_dev, m));
+    if (m == 0) return SF_OK;
+    SF_HIP(hipSetDevice(ctx->device));
+    return k14_launch_sc2(ctx, cmat_dev, m, s2_dev);
+}
+
+extern "C" int sf_consistency_sc2_group(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, double distance_threshold,
+                                        double min_edge, unsigned *s2_dev, unsigned char *member_dev, unsigned *group_degree_dev,
+                                        int64_t *info)
+{
+    SF_CHECK(k13_check("sf_consistency_sc2_group", ctx && a_dev && b_dev && s2_dev && member_dev && group_degree_dev && info, m,
+                       distance_threshold, min_edge));
+    SF_CHECK(k14_check_count("sf_consistency_sc2_group", true, m)); // (before anything is allocated)
+    if (m == 0) return SF_OK;
+    SF_HIP(hipSetDevice(ctx->device));
+    sf_pool_guard tmp(ctx);
+    int64_t *dinfo = nullptr;
+    unsigned char *cmat = nullptr;
+    const int64_t m_pad = k14_pad(m);
+    SF_CHECK(tmp.alloc(&dinfo, IN_SIZE));
+    SF_CHECK(tmp.alloc(&cmat, (size_t)m_pad * (size_t)m_pad));
+    const dim3 one(1), fold(K13_FOLD);
+    // queued back to back: nothing below waits for the device.  The first maximum of s2 is K13's arg-max on another array; the
+    // seed's row, its count and the degree inside the group are K13's own kernels, so they agree with the matrix bit for bit.
+    SF_CHECK(k14_launch_matrix(ctx, a_dev, b_dev, m, distance_threshold, min_edge, cmat));
+    SF_CHECK(k14_launch_sc2(ctx, cmat, m, s2_dev));
+    SF_LAUNCH(ctx, "k13_argmax", k13_argmax, one, fold, (const unsigned *)s2_dev, m, dinfo);
+    SF_LAUNCH(ctx, "k13_mark", k13_mark, dim3((unsigned)sf_div_up(m, K13_BLOCK)), dim3(K13_BLOCK), a_dev, b_dev, m, distance_threshold,
+              min_edge, (const int64_t *)dinfo, member_dev);
+    SF_LAUNCH(ctx, "k13_count", k13_count, one, fold, (const unsigned char *)member_dev, m, dinfo);
+    SF_CHECK(k13_launch_degree(ctx, a_dev, b_dev, m, member_dev, distance_threshold, min_edge, group_degree_dev));
+    void *pin = nullptr;
+    SF_CHECK(sf_ctx_pinned(ctx, &pin));
+    int64_t *hi = (int64_t *)pin;
+    SF_HIP(hipMemcpyAsync(hi, dinfo, IN_SIZE * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream)); // the one wait of the call
+    for (int v = 0; v < IN_SIZE; ++v) info[v] = hi[v];
+    if (info[IN_STATUS] != 0) info[IN_SEED] = -1; // no consistent triple: no seed, no group
     return SF_OK;
 }

@@ -584,6 +584,68 @@ class Engine:
                                                  member.ptr, group_degree.ptr, _ptr(info)), "sf_consistency_group")
         return degree, member, group_degree, info
 
+    # ---- second-order consistency (K14) -------------------------------------------------------------------
+    SC2_MAX_MATCHES = 32768  # SF_SC2_MAX_MATCHES: a 1 GiB byte matrix
+    SC2_TILE = 256           # SF_SC2_TILE
+
+    @classmethod
+    def sc2_padded(cls, m: int) -> int:
+        """SF_SC2_PAD: the edge of the byte matrix of m matches."""
+        return (int(m) + cls.SC2_TILE - 1) // cls.SC2_TILE * cls.SC2_TILE
+
+    def _sc2_matrix(self, who: str, cmat: DeviceArray, m: int) -> None:
+        if not 0 <= m <= self.SC2_MAX_MATCHES:
+            raise ValueError(f"{who}: {m} matches, at most {self.SC2_MAX_MATCHES}")
+        if cmat.dtype != np.uint8 or cmat.nbytes < self.sc2_padded(m) ** 2:
+            raise ValueError(f"{who}: the matrix must hold {self.sc2_padded(m)}^2 bytes (uint8)")
+
+    def consistency_matrix(self, a: DeviceArray, b: DeviceArray, m: int, distance_threshold: float, min_edge: float,
+                           out: Optional[DeviceArray] = None) -> DeviceArray:
+        """sf_consistency_matrix on resident matched points: the 0/1 compatibility matrix as bytes, resident, sc2_padded(m) on
+        either edge with the padding zero.  Asynchronous; `out` (uint8, at least that many bytes) is reused when given."""
+        m = int(m)
+        self._consistency_sizes("consistency_matrix", a, b, m)
+        if not 0 <= m <= self.SC2_MAX_MATCHES:
+            raise ValueError(f"consistency_matrix: {m} matches, at most {self.SC2_MAX_MATCHES}")
+        pad = self.sc2_padded(m)
+        mine = out is None
+        if mine:
+            out = self.empty((max(pad, 1), max(pad, 1)), np.uint8)
+        try:
+            self._sc2_matrix("consistency_matrix", out, m)
+            _ffi.check(self.lib.sf_consistency_matrix(self.h, a.ptr, b.ptr, m, float(distance_threshold), float(min_edge), out.ptr),
+                       "sf_consistency_matrix")
+        except Exception:
+            if mine:
+                out.free()
+            raise
+        return out
+
+    def consistency_sc2(self, cmat: DeviceArray, m: int) -> np.ndarray:
+        """sf_consistency_sc2 of a resident 0/1 byte matrix (sc2_padded(m) on either edge, zero padding; symmetric or not):
+        s2[i] = sum_j C[i,j] sum_k C[i,k] C[j,k] on the int8 matrix cores.  Returns m uint32."""
+        m = int(m)
+        self._sc2_matrix("consistency_sc2", cmat, m)
+        out = self.empty((max(m, 1),), np.uint32)
+        try:
+            _ffi.check(self.lib.sf_consistency_sc2(self.h, cmat.ptr, m, out.ptr), "sf_consistency_sc2")
+            return out.to_host()[:m]
+        finally:
+            out.free()
+
+    def consistency_sc2_group_device(self, a: DeviceArray, b: DeviceArray, m: int, distance_threshold: float, min_edge: float,
+                                     s2: DeviceArray, member: DeviceArray, group_degree: DeviceArray
+                                     ) -> tuple[DeviceArray, DeviceArray, DeviceArray, np.ndarray]:
+        """sf_consistency_sc2_group: the matrix, s2, its first maximum, the seed's row, its count and the degree inside the group,
+        queued back to back with one host wait.  `s2`, `group_degree` (m uint32) and `member` (m uint8) are resident outputs,
+        handed back with info = [seed, s2[seed], group size, status (1: no consistent triple, seed -1)] (int64)."""
+        m = int(m)
+        self._consistency_sizes("consistency_sc2_group_device", a, b, m, u32=(s2, group_degree), u8=(member,))
+        info = np.array([-1, 0, 0, 1], dtype=np.int64)  # (what stays for m = 0, where the library writes nothing)
+        _ffi.check(self.lib.sf_consistency_sc2_group(self.h, a.ptr, b.ptr, m, float(distance_threshold), float(min_edge), s2.ptr,
+                                                     member.ptr, group_degree.ptr, _ptr(info)), "sf_consistency_sc2_group")
+        return s2, member, group_degree, info
+
     # ---- multi-GPU (RCCL) -------------------------------------------------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)

@@ -4,6 +4,7 @@ from .filters import FilterFunction, left_median_filter, quantile_filter, thresh
 from .fgr import FgrRecord, fast_global_registration
 from .match import basic_matching, double_matching_with_rejects, match_descriptors, match_two_nearest, ratio_test_matching
 from .ransac import RansacRecord, ransac_on_matches, ransac_prerejective
+from .sc2 import SecondOrderRecord, second_order_consistency_filter
 
 __all__ = [
     "FilterFunction",
@@ -22,4 +23,6 @@ __all__ = [
     "FgrRecord",
     "geometric_consistency_filter",
     "ConsistencyRecord",
+    "second_order_consistency_filter",
+    "SecondOrderRecord",
 ]

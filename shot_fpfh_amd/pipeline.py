@@ -29,6 +29,7 @@ from .matching import (
     ransac_on_matches,
     ransac_prerejective,
     ratio_test_matching,
+    second_order_consistency_filter,
     threshold_filter,
 )
 
@@ -194,6 +195,19 @@ class RegistrationPipeline:
         logging.info("-- Filtering the matches by geometric consistency --")
         total = self.matches[0].shape[0]
         scan_kept, ref_kept, record = geometric_consistency_filter(
+            *self.matches, self.scan[self.scan_keypoints], self.ref[self.ref_keypoints], distance_threshold=distance_threshold,
+            min_edge=min_edge, group_share=group_share)
+        self.matches = (scan_kept, ref_kept)
+        logging.info(f"{scan_kept.shape[0]} matches kept out of {total} ({record.status}, group of {record.group_size})")
+
+    def filter_matches_by_second_order_consistency(self, distance_threshold: float, min_edge: float | None = None,
+                                                   group_share: float = 0.5) -> None:
+        """Keeps the matches that `second_order_consistency_filter` (not in the reference) selects -- the group around the match
+        that lies in the most triangles of the compatibility graph, which still finds the true matches where they are a per
+        cent of the set: `self.matches` is replaced by the kept ones, in their order."""
+        logging.info("-- Filtering the matches by second-order consistency --")
+        total = self.matches[0].shape[0]
+        scan_kept, ref_kept, record = second_order_consistency_filter(
             *self.matches, self.scan[self.scan_keypoints], self.ref[self.ref_keypoints], distance_threshold=distance_threshold,
             min_edge=min_edge, group_share=group_share)
         self.matches = (scan_kept, ref_kept)
