@@ -489,6 +489,46 @@ int sf_consistency_sc2_group(sf_ctx *ctx, const double *a_dev, const double *b_d
                              double min_edge, unsigned *s2_dev, unsigned char *member_dev, unsigned *group_degree_dev,
                              int64_t *info /* 4 */);
 
+/* ---- SC2 registration: one fit per second-order seed, ranked by inliers over all matches: K15 (the other half of SC2-PCR) -----
+ * With C, s2 and the matrix layout of K14 above; all data pointers are DEVICE memory except result and best_Rt.
+ * sf_sc2_seeds: seeds_dev (n_seeds int32) <- the matches of the n_seeds largest s2, s2 descending and position ascending, those
+ *   with s2 > 0 only; the slots after the last one hold -1.  Exact (a rank count).  Asynchronous.
+ * sf_sc2_seed_rows: rows_dev (n_seeds x m_pad uint32, every entry written) <- row_s[j] = C[seed_s][j] sum_k C[seed_s][k] C[j][k]
+ *   for ANY matrix of 0 / 1 bytes in K14's layout, symmetric or not -- an integer GEMM on the int8 matrix cores over tiles of
+ *   SF_SC2_SEED_TILE seeds x SF_SC2_TILE columns.  Seeds may repeat and come in any order; a seed of -1, or outside [0, m),
+ *   gives a zero row; the padding columns are zero.  sum_j row_s[j] = s2[seed_s].  Asynchronous.
+ * sf_sc2_seed_fits: per seed, top = max_j row_s[j]; member j iff j = seed_s or (row_s[j] >= 1 and (double)row_s[j] >=
+ *   group_share * (double)top) -- the rule of second_order_consistency_filter; size_dev (n_seeds int32) <- the member count;
+ *   the Kabsch fit over the members (centroids first, then the centred cross-covariance; partial sums folded in a fixed order:
+ *   a call repeats bit for bit) with the rules and constants of sf_ransac_hypotheses.  status_dev (n_seeds bytes): 0 a transform,
+ *   1 fewer than three members, 2 degenerate (no unique rotation, or not finite), 3 no seed in the slot.  Rt_dev (n_seeds x 12:
+ *   R row-major, t; zeros unless the status is 0).  Optional (NULL: not wanted): sums_dev (n_seeds x 24, the layout of
+ *   sf_ransac_refit_sums over the members, [16] = 0), member_dev (n_seeds x m bytes).  Asynchronous.
+ * sf_sc2_registration: sf_consistency_matrix, sf_consistency_sc2, the three calls above, the status-0 transforms compacted in
+ *   seed order, sf_ransac_score over them at distance_threshold and the FIRST maximum, queued without a host wait in between; the
+ *   call waits once, for the result.  The matrix and the rows (n_seeds x m_pad x 4 bytes) come from the context's pool.  Optional
+ *   device outputs (NULL: not wanted): s2_dev (m uint32), seeds_dev, status_dev, size_dev (n_seeds each, as above), Rt_dev
+ *   (n_seeds x 12: the first `scored` rows are the compacted transforms, the others zero), map_dev (n_seeds int64: slot -> position
+ *   among the seeds, strictly increasing, then -1), counts_dev (n_seeds int64: the inlier count per slot, then -1).
+ *   result[8] (host): [0] seeds found, [1] seeds with fewer than three members, [2] degenerate, [3] scored, [4] the winning
+ *   seed's match (-1: nothing was scored), [5] its inlier count, [6] its position among the seeds (-1), [7] its consensus size;
+ *   best_Rt[12] (host): its transform (zeros when nothing was scored).
+ *   SF_ERR_ARG: a NULL pointer that is not optional, m < 0, m > SF_SC2_MAX_MATCHES, n_seeds outside 1 .. SF_SC2_MAX_SEEDS, a
+ *   group_share outside (0, 1], a distance_threshold or min_edge that is negative or not finite -- all refused before anything is
+ *   allocated.  m = 0: SF_OK, nothing is written. */
+#define SF_SC2_MAX_SEEDS 1024
+#define SF_SC2_SEED_TILE 64
+int sf_sc2_seeds(sf_ctx *ctx, const unsigned *s2_dev, int64_t m, int64_t n_seeds, int *seeds_dev);
+int sf_sc2_seed_rows(sf_ctx *ctx, const unsigned char *cmat_dev, int64_t m, const int *seeds_dev, int64_t n_seeds,
+                     unsigned *rows_dev);
+int sf_sc2_seed_fits(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const int *seeds_dev,
+                     const unsigned *rows_dev, int64_t n_seeds, double group_share, unsigned char *status_dev, int *size_dev,
+                     double *Rt_dev, double *sums_dev /* nullable */, unsigned char *member_dev /* nullable */);
+int sf_sc2_registration(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, double distance_threshold,
+                        double min_edge, int64_t n_seeds, double group_share, unsigned *s2_dev, int *seeds_dev,
+                        unsigned char *status_dev, int *size_dev, double *Rt_dev, int64_t *map_dev, int64_t *counts_dev,
+                        int64_t *result /* 8 */, double *best_Rt /* 12 */);
+
 /* ---- voxel subsampling: grid_subsampling (core/subsampling.py:5-39) and the voxel loop of
  * select_keypoints_with_density_threshold (keypoint_selection.py:80-101) ---------------------------------
  * sf_voxels_build: keys ((p - min p) // voxel).astype(int) with NumPy's floor_divide, voxels ranked in np.unique's

@@ -52,9 +52,12 @@ def parse_args(argv=None) -> argparse.Namespace:
                                   "for sets with a few per cent of true matches, at most 32768 of them (default: off)")
     p.add_argument("--ransac-draws", type=int, default=10000), p.add_argument("--ransac-draw-size", type=int, default=None,
                                                                             help="default 4 (reference), 3 (prerejective)")
-    p.add_argument("--ransac", default="reference", choices=["reference", "prerejective", "fgr"],
+    p.add_argument("--ransac", default="reference", choices=["reference", "prerejective", "fgr", "sc2"],
                    help="prerejective: drop draws whose edge lengths disagree before scoring, refit the winner over its inliers; "
-                        "fgr: fast global registration, no draws (--ransac-draws and --ransac-draw-size are ignored)")
+                        "fgr: fast global registration, no draws (--ransac-draws and --ransac-draw-size are ignored); "
+                        "sc2: one fit per second-order seed, ranked by inliers, at most 32768 matches (no draws either; may be "
+                        "combined with --consistency or --consistency-sc2, which then thin the matches first)")
+    p.add_argument("--sc2-seeds", type=int, default=256, metavar="N", help="--ransac sc2: the number of seeds, 1 .. 1024")
     p.add_argument("--ransac-edge-similarity", type=float, default=0.9), p.add_argument("--ransac-refit", type=int, default=2)
     p.add_argument("--ransac-threshold", type=float, default=1.0)
     p.add_argument("--fgr-iterations", type=int, default=64), p.add_argument("--fgr-tuples", type=int, default=0)
@@ -92,7 +95,7 @@ def main(argv=None) -> int:
                                                     max_inliers_distance=args.ransac_threshold, disable_progress_bar=True,
                                                     method=args.ransac, edge_similarity=args.ransac_edge_similarity,
                                                     refit_iterations=args.ransac_refit, fgr_iterations=args.fgr_iterations,
-                                                    fgr_tuple_count=args.fgr_tuples)
+                                                    fgr_tuple_count=args.fgr_tuples, sc2_seeds=args.sc2_seeds)
     logging.info(f"RANSAC inlier ratio {inliers_ratio:.3f}\n{transformation}")
     outputs = [(f"{args.write}_ransac.ply", transformation)] if args.write else []
     if args.icp != "none":

@@ -17,6 +17,8 @@ from .matching import (
     match_descriptors,
     ransac_on_matches,
     ransac_prerejective,
+    sc2_registration,
+    Sc2RegistrationRecord,
     second_order_consistency_filter,
     SecondOrderRecord,
 )
@@ -41,6 +43,8 @@ __all__ = [
     "geometric_consistency_filter",
     "second_order_consistency_filter",
     "SecondOrderRecord",
+    "sc2_registration",
+    "Sc2RegistrationRecord",
     "RegistrationPipeline",
     "read_ply",
     "write_ply",

@@ -119,6 +119,10 @@ SIGNATURES = {
     "sf_consistency_matrix": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _vp]),
     "sf_consistency_sc2": (_int, [_vp, _vp, _i64, _vp]),
     "sf_consistency_sc2_group": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "sf_sc2_seeds": (_int, [_vp, _vp, _i64, _i64, _vp]),
+    "sf_sc2_seed_rows": (_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "sf_sc2_seed_fits": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "sf_sc2_registration": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sf_voxels_build": (_vp, [_vp, _vp, _i64, _f64, _int]),
     "sf_voxels_count": (_i64, [_vp]),
     "sf_voxels_inverse": (_int, [_vp, _vp, _vp]),

@@ -17,6 +17,15 @@
 // The chain of sf_consistency_group (degree, arg-max, mark, count, masked degree) is queued on the stream; the host waits once.
 #include "common.h"
 #include "device_util.h"
+#include "horn4.h"
+
+// K9 (match.hip) and the back half of K11 (ransac.hip): what K15 ranks its fits with
+extern "C" int sf_ransac_score(sf_ctx *ctx, const double *a, const double *b, int64_t m, const double *Rt, int64_t n_draws,
+                               double thr, int64_t *inliers, int flags);
+int64_t sf_k11_blocks(int64_t n);
+int sf_k11_compact(sf_ctx *ctx, const unsigned char *status, const double *Rt_all, int64_t n, double *Rt_out, int64_t *map,
+                   int *block_count, int64_t *block_off, unsigned long long *tallies);
+int sf_k11_first_max(sf_ctx *ctx, const int64_t *counts, int64_t n, const int64_t *map, const double *Rt, int64_t *win, double *best_rt);
 
 namespace {
 
@@ -324,7 +333,6 @@ __global__ __launch_bounds__(512, 1) void k14_sc2(const unsigned char *__restric
     }
 }
 #undef K14_DMA
-#undef K14_DMA16
 #undef K14_FRAG
 
 int k14_check_count(const char *who, bool pointers, int64_t m)
@@ -359,6 +367,304 @@ int k14_launch_sc2(sf_ctx *ctx, const unsigned char *cmat, int64_t m, unsigned *
     return SF_OK;
 }
 
+
+// ---- K15: SC2 registration -- one Kabsch fit per second-order seed, ranked by inliers over all matches ----------------------------
+// The other half of SC2-PCR on the matrix K14 builds (the definition: tests/sc2_registration_numpy.py):
+//   seeds   the n_seeds matches of the largest s2 > 0, s2 descending, position ascending (k15_seeds: an exact rank count, every
+//           thread writes the one slot its rank names -- no atomic decides a position);
+//   rows    row_s[j] = C[seed_s][j] sum_k C[seed_s][k] C[j][k] (k15_seed_rows: the thin integer GEMM below);
+//   fits    consensus of a seed = the filter's rule on its row, Kabsch over the members (k15_fit, one workgroup a seed);
+//   ranking K11's compaction, K9 and K11's first maximum (ransac.hip, match.hip), as they are.
+//
+// k15_seed_rows is k14_sc2 with a gathered, short row operand and a store in place of the sum.  A workgroup of 8 waves owns
+// K15_TS = 64 seeds x 256 columns; wave w owns the 64 x 32 block of columns 32 w .. 32 w + 31 (2 accumulators).  Per step the
+// 64-byte K-chunk of the 64 seed rows (source row = cmat row of the seed: the gather is in the DMA's source address and nowhere
+// else) and of the tile's 256 column rows goes into one of two 20 KB LDS buffers by LDS-DMA, 20 instructions of 1 KB: waves
+// 0 .. 3 issue three, the others two.  LDS image, bank permutation and operand layout are k14_sc2's.  N has no symmetry to use
+// here (the row operand is a subset), and the grid is (seed tiles, column tiles) with the seed tile the fast axis: the seed
+// tiles of one column tile are resident together and stream the same 256 rows of C.  A seed of -1 (or outside [0, m)) reads
+// row 0 and multiplies by 0.
+constexpr int K15_TS = SF_SC2_SEED_TILE;     // seeds of a workgroup
+constexpr int K15_ROWS = K15_TS + K14_T;     // LDS rows of a buffer: the seed rows, then the column tile's
+constexpr int K15_BUF = K15_ROWS * K14_KC;   // 20 KB
+constexpr int K15_SEL = 1024;                // keys staged at a time by k15_seeds
+constexpr int K15_FIT = 256;                 // threads of k15_fit
+static_assert(K15_TS == 64 && K15_ROWS % 16 == 0 && K15_ROWS / 16 <= 24, "the DMA split below is written out for 64 + 256 rows");
+
+// grid: blocks of 256 matches.  rank(i) = #{ j : (s2[j], -j) > (s2[i], -i) } as one 64-bit compare; seeds_dev was filled with -1.
+__global__ __launch_bounds__(256) void k15_seeds(const unsigned *__restrict__ s2, int64_t m, int n_seeds, int *__restrict__ seeds)
+{
+    __shared__ unsigned long long keys[K15_SEL];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long mine = i < m ? (((unsigned long long)s2[i] << 32) | (unsigned)~(unsigned)i) : ~0ull;
+    unsigned rank = 0;
+    for (int64_t j0 = 0; j0 < m; j0 += K15_SEL) {
+        __syncthreads();
+        for (int e = threadIdx.x; e < K15_SEL; e += 256) {
+            const int64_t j = j0 + e;
+            keys[e] = j < m ? (((unsigned long long)s2[j] << 32) | (unsigned)~(unsigned)j) : 0ull; // (0: above nobody)
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int c = 0; c < K15_SEL; ++c) rank += keys[c] > mine ? 1u : 0u; // one address for the whole wave: a broadcast read
+    }
+    if (i < m && (mine >> 32) != 0 && rank < (unsigned)n_seeds) seeds[rank] = (int)i;
+}
+
+#define K15_FRAG(ROW0, KS) (*reinterpret_cast<const k14_i4 *>(bp + (ROW0) * K14_KC + roff[KS]))
+// the K-chunk [K0, K0 + K14_KC) of the 320 rows into buffer BUF: instruction u of wave w fills rows 16 (w + 8 u) .. + 15
+#define K15_DMA(K0, BUF)                                                                                            \
+    {                                                                                                               \
+        const unsigned dst_ = lds_base + (unsigned)(BUF) * K15_BUF + 1024u * wave_u;                                \
+        K14_DMA16(src[0] + (K0), dst_)                                                                              \
+        K14_DMA16(src[1] + (K0), dst_ + 8192u)                                                                      \
+        if (wave_u < 4) K14_DMA16(src[2] + (K0), dst_ + 16384u)                                                     \
+    }
+
+// grid: (seed tiles of K15_TS, column tiles of K14_T).  rows: n_seeds x m_pad uint32, every entry of rows s < n_seeds written.
+__global__ __launch_bounds__(512) void k15_seed_rows(const unsigned char *__restrict__ cmat, int64_t m, int64_t m_pad,
+                                                     const int *__restrict__ seeds, int n_seeds, unsigned *__restrict__ rows)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char Ls[2 * K15_BUF];
+    __shared__ int seed_sh[K15_TS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r31 = lane & 31, h = lane >> 5;
+    const int s0 = (int)blockIdx.x * K15_TS;
+    const int64_t col_tile = (int64_t)blockIdx.y * K14_T;
+    if (tid < K15_TS) {
+        const int sd = s0 + tid < n_seeds ? seeds[s0 + tid] : -1;
+        seed_sh[tid] = (sd >= 0 && sd < m) ? sd : -1;
+    }
+    __syncthreads();
+    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)Ls;
+    const unsigned wave_u = (unsigned)__builtin_amdgcn_readfirstlane(wave);
+    const unsigned char *src[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+        const int P = 64 * (wave + 8 * u) + lane, c = (P & 3) ^ ((P >> 4) & 3);
+        const int row = (P >> 2) < K15_ROWS ? (P >> 2) : 0; // (waves 4 .. 7 have no third piece: never issued)
+        int64_t grow;
+        if (row < K15_TS) {
+            const int sd = seed_sh[row];
+            grow = sd >= 0 ? sd : 0;
+        } else {
+            grow = col_tile + (row - K15_TS);
+        }
+        src[u] = cmat + grow * m_pad + 16 * c;
+    }
+    unsigned roff[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) roff[ks] = (unsigned)(r31 * K14_KC + (((2 * ks + h) ^ ((r31 >> 2) & 3)) * 16));
+    k14_i16 acc[2];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[bi][r] = 0;
+    const int64_t nk = m_pad / K14_KC;
+    K15_DMA(0, 0)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int64_t kc = 0; kc < nk; ++kc) {
+        const int buf = (int)(kc & 1);
+        if (kc + 1 < nk) K15_DMA((kc + 1) * K14_KC, buf ^ 1)
+        const unsigned char *bp = Ls + buf * K15_BUF;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const k14_i4 fb = K15_FRAG(K15_TS + 32 * wave, ks);
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+                acc[bi] = __builtin_amdgcn_mfma_i32_32x32x32_i8(K15_FRAG(32 * bi, ks), fb, acc[bi], 0, 0, 0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's DMA pieces of the next chunk have landed
+        __syncthreads();
+    }
+    const int64_t col = col_tile + 32 * wave + r31; // < m_pad
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rl = 32 * bi + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (s0 + rl >= n_seeds) continue;
+            const int sd = seed_sh[rl];
+            const unsigned cv = sd >= 0 ? (unsigned)cmat[(int64_t)sd * m_pad + col] : 0u;
+            rows[(int64_t)(s0 + rl) * m_pad + col] = (unsigned)acc[bi][r] * cv; // 32 lanes: 128 consecutive bytes
+        }
+}
+#undef K15_DMA
+#undef K15_FRAG
+#undef K14_DMA16
+
+// NV sums over the block, the same total in every thread: lanes by the xor ladder, the four waves in wave order.
+template <int NV>
+__device__ __forceinline__ void k15_block_sums(double (&v)[NV], double (*sh)[9])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads(); // (the previous use of sh has been read)
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        double x = v[q];
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+        if (lane == 0) sh[wave][q] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NV; ++q) v[q] = ((sh[0][q] + sh[1][q]) + sh[2][q]) + sh[3][q];
+}
+
+// grid: one block a seed.  status: 0 a transform, 1 fewer than three members, 2 no unique rotation (K11's rule and constants),
+// 3 no seed in this slot.  sums (nullable): sf_ransac_refit_sums's layout, [16] = 0.  member (nullable): n_seeds x m bytes.
+__global__ __launch_bounds__(K15_FIT) void k15_fit(const double *__restrict__ a, const double *__restrict__ b, int64_t m, int64_t m_pad,
+                                                   const int *__restrict__ seeds, const unsigned *__restrict__ rows, double share,
+                                                   unsigned char *__restrict__ status, int *__restrict__ size, double *__restrict__ Rt,
+                                                   double *__restrict__ sums, unsigned char *__restrict__ member)
+{
+    __shared__ double sh[4][9];
+    __shared__ unsigned shu[K15_FIT / SF_WAVE];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    int64_t sd = seeds[s];
+    if (sd >= m) sd = -1;
+    const unsigned *row = rows + (int64_t)s * m_pad;
+    unsigned char *mem = member ? member + (int64_t)s * m : nullptr;
+    unsigned top = 0;
+    if (sd >= 0)
+        for (int64_t j = tid; j < m; j += K15_FIT) top = row[j] > top ? row[j] : top;
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned y = __shfl_xor(top, off);
+        top = y > top ? y : top;
+    }
+    if ((tid & (SF_WAVE - 1)) == 0) shu[tid / SF_WAVE] = top;
+    __syncthreads();
+    for (int w = 0; w < K15_FIT / SF_WAVE; ++w) top = shu[w] > top ? shu[w] : top;
+    const double cut = share * (double)top;
+    // pass 0: the members, their count and their sums (a thread takes positions tid, tid + 256, .. in ascending order)
+    double v0[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) v0[q] = 0.0;
+    for (int64_t j = tid; j < m; j += K15_FIT) {
+        const unsigned r = sd >= 0 ? row[j] : 0u;
+        const bool in = sd >= 0 && (j == sd || (r >= 1u && (double)r >= cut));
+        if (mem) mem[j] = in ? 1 : 0;
+        if (!in) continue;
+        v0[0] += 1.0;
+        v0[1] += a[3 * j]; v0[2] += a[3 * j + 1]; v0[3] += a[3 * j + 2];
+        v0[4] += b[3 * j]; v0[5] += b[3 * j + 1]; v0[6] += b[3 * j + 2];
+    }
+    k15_block_sums<7>(v0, sh);
+    const double n = v0[0];
+    const bool fit = n >= 3.0;
+    double mean[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) mean[q] = n > 0.0 ? v0[1 + q] / n : 0.0;
+    // pass 1: the centred cross-covariance over the same members (of any count: the sums are an output of their own)
+    double v1[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) v1[q] = 0.0;
+    if (sd >= 0)
+        for (int64_t j = tid; j < m; j += K15_FIT) {
+            const unsigned r = row[j];
+            if (!(j == sd || (r >= 1u && (double)r >= cut))) continue;
+            const double ux = a[3 * j] - mean[0], uy = a[3 * j + 1] - mean[1], uz = a[3 * j + 2] - mean[2];
+            const double vx = b[3 * j] - mean[3], vy = b[3 * j + 1] - mean[4], vz = b[3 * j + 2] - mean[5];
+            v1[0] += ux * vx; v1[1] += ux * vy; v1[2] += ux * vz;
+            v1[3] += uy * vx; v1[4] += uy * vy; v1[5] += uy * vz;
+            v1[6] += uz * vx; v1[7] += uz * vy; v1[8] += uz * vz;
+        }
+    k15_block_sums<9>(v1, sh);
+    if (tid != 0) return;
+    unsigned char st = sd < 0 ? 3 : (fit ? 0 : 1);
+    double o[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) o[q] = 0.0;
+    if (st == 0) {
+        const sf_horn::rot3 R = sf_horn::kabsch_rotation(v1[0], v1[1], v1[2], v1[3], v1[4], v1[5], v1[6], v1[7], v1[8]);
+        const double t0 = mean[3] - ((R.r0 * mean[0] + R.r1 * mean[1]) + R.r2 * mean[2]);
+        const double t1 = mean[4] - ((R.r3 * mean[0] + R.r4 * mean[1]) + R.r5 * mean[2]);
+        const double t2 = mean[5] - ((R.r6 * mean[0] + R.r7 * mean[1]) + R.r8 * mean[2]);
+        const double mag = (((fabs(R.r0) + fabs(R.r1)) + (fabs(R.r2) + fabs(R.r3))) + ((fabs(R.r4) + fabs(R.r5)) + (fabs(R.r6) + fabs(R.r7)))) +
+                           ((fabs(R.r8) + fabs(t0)) + (fabs(t1) + fabs(t2)));
+        if (R.gap > 1e-6 * R.s1 && mag <= K13_DBL_MAX) { // K11's rule (ransac.hip)
+            o[0] = R.r0; o[1] = R.r1; o[2] = R.r2; o[3] = R.r3; o[4] = R.r4; o[5] = R.r5; o[6] = R.r6; o[7] = R.r7; o[8] = R.r8;
+            o[9] = t0; o[10] = t1; o[11] = t2;
+        } else {
+            st = 2;
+        }
+    }
+    status[s] = st;
+    size[s] = (int)n;
+#pragma unroll
+    for (int q = 0; q < 12; ++q) Rt[12 * (int64_t)s + q] = o[q];
+    if (sums) {
+        double *out = sums + 24 * (int64_t)s;
+        out[0] = n;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) { out[1 + q] = mean[q]; out[17 + q] = v0[1 + q]; }
+#pragma unroll
+        for (int q = 0; q < 9; ++q) out[7 + q] = v1[q];
+        out[16] = 0.0;
+        out[23] = 0.0;
+    }
+}
+
+// counts[i] <- -1 for the slots past the scored ones (tallies[0]): K11's first maximum never takes them
+__global__ void k15_mask_tail(int64_t *__restrict__ counts, int n_seeds, const unsigned long long *__restrict__ tallies)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n_seeds && (unsigned long long)i >= tallies[0]) counts[i] = -1;
+}
+
+// the chain's result (sf_sc2_registration) from the tallies of the compaction and the winner of the first maximum
+__global__ void k15_result(const unsigned long long *__restrict__ tallies, const int64_t *__restrict__ win, const int *__restrict__ seeds,
+                           const int *__restrict__ size, int n_seeds, int64_t *__restrict__ out)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int64_t slot = win[1]; // the winner's position among the seeds
+    out[0] = (int64_t)n_seeds - (int64_t)tallies[3];
+    out[1] = (int64_t)tallies[1];
+    out[2] = (int64_t)tallies[2];
+    out[3] = (int64_t)tallies[0];
+    out[4] = slot >= 0 ? (int64_t)seeds[slot] : -1;
+    out[5] = win[2];
+    out[6] = slot;
+    out[7] = slot >= 0 ? (int64_t)size[slot] : 0;
+}
+
+int k15_check_seeds(const char *who, int64_t n_seeds)
+{
+    if (n_seeds < 1 || n_seeds > SF_SC2_MAX_SEEDS) {
+        sf_set_error("%s: n_seeds %lld outside 1 .. %d", who, (long long)n_seeds, SF_SC2_MAX_SEEDS);
+        return SF_ERR_ARG;
+    }
+    return SF_OK;
+}
+
+int k15_check_share(const char *who, double share)
+{
+    if (!(share > 0.0 && share <= 1.0)) { sf_set_error("%s: group_share %g outside (0, 1]", who, share); return SF_ERR_ARG; }
+    return SF_OK;
+}
+
+int k15_launch_seeds(sf_ctx *ctx, const unsigned *s2, int64_t m, int n_seeds, int *seeds)
+{
+    SF_HIP(hipMemsetAsync(seeds, 0xff, (size_t)n_seeds * sizeof(int), ctx->stream)); // -1
+    SF_LAUNCH(ctx, "k15_seeds", k15_seeds, dim3((unsigned)sf_div_up(m, 256)), dim3(256), s2, m, n_seeds, seeds);
+    return SF_OK;
+}
+
+int k15_launch_seed_rows(sf_ctx *ctx, const unsigned char *cmat, int64_t m, const int *seeds, int n_seeds, unsigned *rows)
+{
+    const int64_t m_pad = k14_pad(m);
+    SF_LAUNCH(ctx, "k15_seed_rows", k15_seed_rows, dim3((unsigned)sf_div_up(n_seeds, K15_TS), (unsigned)(m_pad / K14_T)), dim3(512), cmat, m,
+              m_pad, seeds, n_seeds, rows);
+    return SF_OK;
+}
+
+int k15_launch_fit(sf_ctx *ctx, const double *a, const double *b, int64_t m, const int *seeds, const unsigned *rows, int n_seeds,
+                   double share, unsigned char *status, int *size, double *Rt, double *sums, unsigned char *member)
+{
+    SF_LAUNCH(ctx, "k15_fit", k15_fit, dim3((unsigned)n_seeds), dim3(K15_FIT), a, b, m, k14_pad(m), seeds, rows, share, status, size, Rt,
+              sums, member);
+    return SF_OK;
+}
 } // namespace
 
 extern "C" int sf_consistency_degree(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m,
@@ -450,5 +756,101 @@ extern "C" int sf_consistency_sc2_group(sf_ctx *ctx, const double *a_dev, const 
     SF_HIP(hipStreamSynchronize(ctx->stream)); // the one wait of the call
     for (int v = 0; v < IN_SIZE; ++v) info[v] = hi[v];
     if (info[IN_STATUS] != 0) info[IN_SEED] = -1; // no consistent triple: no seed, no group
+    return SF_OK;
+}
+
+extern "C" int sf_sc2_seeds(sf_ctx *ctx, const unsigned *s2_dev, int64_t m, int64_t n_seeds, int *seeds_dev)
+{
+    SF_CHECK(k14_check_count("sf_sc2_seeds", ctx && s2_dev && seeds_dev, m));
+    SF_CHECK(k15_check_seeds("sf_sc2_seeds", n_seeds));
+    if (m == 0) return SF_OK;
+    SF_HIP(hipSetDevice(ctx->device));
+    return k15_launch_seeds(ctx, s2_dev, m, (int)n_seeds, seeds_dev);
+}
+
+extern "C" int sf_sc2_seed_rows(sf_ctx *ctx, const unsigned char *cmat_dev, int64_t m, const int *seeds_dev, int64_t n_seeds,
+                                unsigned *rows_dev)
+{
+    SF_CHECK(k14_check_count("sf_sc2_seed_rows", ctx && cmat_dev && seeds_dev && rows_dev, m));
+    SF_CHECK(k15_check_seeds("sf_sc2_seed_rows", n_seeds));
+    if (m == 0) return SF_OK;
+    SF_HIP(hipSetDevice(ctx->device));
+    return k15_launch_seed_rows(ctx, cmat_dev, m, seeds_dev, (int)n_seeds, rows_dev);
+}
+
+extern "C" int sf_sc2_seed_fits(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const int *seeds_dev,
+                                const unsigned *rows_dev, int64_t n_seeds, double group_share, unsigned char *status_dev,
+                                int *size_dev, double *Rt_dev, double *sums_dev, unsigned char *member_dev)
+{
+    SF_CHECK(k14_check_count("sf_sc2_seed_fits", ctx && a_dev && b_dev && seeds_dev && rows_dev && status_dev && size_dev && Rt_dev, m));
+    SF_CHECK(k15_check_seeds("sf_sc2_seed_fits", n_seeds));
+    SF_CHECK(k15_check_share("sf_sc2_seed_fits", group_share));
+    if (m == 0) return SF_OK;
+    SF_HIP(hipSetDevice(ctx->device));
+    return k15_launch_fit(ctx, a_dev, b_dev, m, seeds_dev, rows_dev, (int)n_seeds, group_share, status_dev, size_dev, Rt_dev, sums_dev,
+                          member_dev);
+}
+
+extern "C" int sf_sc2_registration(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, double distance_threshold,
+                                   double min_edge, int64_t n_seeds, double group_share, unsigned *s2_dev, int *seeds_dev,
+                                   unsigned char *status_dev, int *size_dev, double *Rt_dev, int64_t *map_dev, int64_t *counts_dev,
+                                   int64_t *result, double *best_Rt)
+{
+    SF_CHECK(k13_check("sf_sc2_registration", ctx && a_dev && b_dev && result && best_Rt, m, distance_threshold, min_edge));
+    SF_CHECK(k14_check_count("sf_sc2_registration", true, m)); // (before anything is allocated)
+    SF_CHECK(k15_check_seeds("sf_sc2_registration", n_seeds));
+    SF_CHECK(k15_check_share("sf_sc2_registration", group_share));
+    if (m == 0) return SF_OK;
+    SF_HIP(hipSetDevice(ctx->device));
+    sf_pool_guard tmp(ctx);
+    const int ns = (int)n_seeds;
+    const int64_t m_pad = k14_pad(m), nblocks = sf_k11_blocks(ns);
+    unsigned char *cmat = nullptr;
+    unsigned *rows = nullptr;
+    double *Rt_all = nullptr, *dbest = nullptr;
+    int *block_count = nullptr;
+    int64_t *block_off = nullptr, *dwin = nullptr, *dres = nullptr;
+    unsigned long long *tallies = nullptr;
+    if (!s2_dev) SF_CHECK(tmp.alloc(&s2_dev, (size_t)m));
+    if (!seeds_dev) SF_CHECK(tmp.alloc(&seeds_dev, (size_t)ns));
+    if (!status_dev) SF_CHECK(tmp.alloc(&status_dev, (size_t)ns));
+    if (!size_dev) SF_CHECK(tmp.alloc(&size_dev, (size_t)ns));
+    if (!Rt_dev) SF_CHECK(tmp.alloc(&Rt_dev, (size_t)ns * 12));
+    if (!map_dev) SF_CHECK(tmp.alloc(&map_dev, (size_t)ns));
+    if (!counts_dev) SF_CHECK(tmp.alloc(&counts_dev, (size_t)ns));
+    SF_CHECK(tmp.alloc(&cmat, (size_t)m_pad * (size_t)m_pad));
+    SF_CHECK(tmp.alloc(&rows, (size_t)ns * (size_t)m_pad));
+    SF_CHECK(tmp.alloc(&Rt_all, (size_t)ns * 12));
+    SF_CHECK(tmp.alloc(&block_count, (size_t)nblocks));
+    SF_CHECK(tmp.alloc(&block_off, (size_t)nblocks));
+    SF_CHECK(tmp.alloc(&tallies, 4));
+    SF_CHECK(tmp.alloc(&dwin, 4));
+    SF_CHECK(tmp.alloc(&dbest, 12));
+    SF_CHECK(tmp.alloc(&dres, 8));
+    // queued back to back: nothing below waits for the device.  The compacted rows past the scored ones are zero transforms whose
+    // counts are set to -1 before the first maximum, so K9 and K11's arg-max run over n_seeds slots without knowing how many count.
+    SF_CHECK(k14_launch_matrix(ctx, a_dev, b_dev, m, distance_threshold, min_edge, cmat));
+    SF_CHECK(k14_launch_sc2(ctx, cmat, m, s2_dev));
+    SF_CHECK(k15_launch_seeds(ctx, s2_dev, m, ns, seeds_dev));
+    SF_CHECK(k15_launch_seed_rows(ctx, cmat, m, seeds_dev, ns, rows));
+    SF_CHECK(k15_launch_fit(ctx, a_dev, b_dev, m, seeds_dev, rows, ns, group_share, status_dev, size_dev, Rt_all, nullptr, nullptr));
+    SF_HIP(hipMemsetAsync(Rt_dev, 0, (size_t)ns * 12 * sizeof(double), ctx->stream));
+    SF_HIP(hipMemsetAsync(map_dev, 0xff, (size_t)ns * sizeof(int64_t), ctx->stream)); // -1
+    SF_CHECK(sf_k11_compact(ctx, status_dev, Rt_all, ns, Rt_dev, map_dev, block_count, block_off, tallies));
+    SF_CHECK(sf_ransac_score(ctx, a_dev, b_dev, m, Rt_dev, ns, distance_threshold, counts_dev, SF_IN_DEVICE | SF_OUT_DEVICE));
+    SF_LAUNCH(ctx, "k15_mask_tail", k15_mask_tail, dim3((unsigned)sf_div_up(ns, 256)), dim3(256), counts_dev, ns,
+              (const unsigned long long *)tallies);
+    SF_CHECK(sf_k11_first_max(ctx, counts_dev, ns, map_dev, Rt_dev, dwin, dbest));
+    SF_LAUNCH(ctx, "k15_result", k15_result, dim3(1), dim3(64), (const unsigned long long *)tallies, (const int64_t *)dwin,
+              (const int *)seeds_dev, (const int *)size_dev, ns, dres);
+    void *pin = nullptr;
+    SF_CHECK(sf_ctx_pinned(ctx, &pin));
+    int64_t *hr = (int64_t *)pin;
+    double *hb = (double *)((char *)pin + 64);
+    SF_HIP(hipMemcpyAsync(hr, dres, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipMemcpyAsync(hb, dbest, 12 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream)); // the one wait of the call
+    for (int v = 0; v < 8; ++v) result[v] = hr[v];
+    memcpy(best_Rt, hb, 12 * sizeof(double));
     return SF_OK;
 }

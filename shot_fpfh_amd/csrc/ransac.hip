@@ -274,6 +274,31 @@ int launch_hypotheses(sf_ctx *ctx, const char *who, const double *a, const doubl
 
 } // namespace
 
+// ---- the back half of K11, for the other estimators that rank fitted transforms (K15, consistency.hip) ------------------------------
+// The status-0 rows of Rt_all compacted in order into Rt_out, map[slot] = their position; tallies (4, zeroed here) <- the number of
+// status 0 (after the scan), 1, 2, 3.  block_count / block_off: sf_k11_blocks(n) entries of scratch each.  Queued, no host wait.
+int64_t sf_k11_blocks(int64_t n) { return std::max<int64_t>(sf_div_up(n, K11_BLOCK), 1); }
+
+int sf_k11_compact(sf_ctx *ctx, const unsigned char *status, const double *Rt_all, int64_t n, double *Rt_out, int64_t *map,
+                   int *block_count, int64_t *block_off, unsigned long long *tallies)
+{
+    const int64_t nblocks = sf_div_up(n, K11_BLOCK);
+    SF_HIP(hipMemsetAsync(tallies, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    SF_LAUNCH(ctx, "k11_count", k11_count, dim3((unsigned)nblocks), dim3(K11_BLOCK), status, n, block_count, tallies);
+    SF_LAUNCH(ctx, "k11_scan", k11_scan, dim3(1), dim3(256), (const int *)block_count, nblocks, block_off, tallies);
+    SF_LAUNCH(ctx, "k11_scatter", k11_scatter, dim3((unsigned)nblocks), dim3(K11_BLOCK), status, Rt_all, n, (const int64_t *)block_off,
+              Rt_out, map);
+    return SF_OK;
+}
+
+// The first maximum of counts[0 .. n): win (3, device) <- {slot, map[slot], count} ({-1, -1, 0} when no count is >= 0), best_rt
+// (12, device) <- that slot's row of Rt.  Queued, no host wait.
+int sf_k11_first_max(sf_ctx *ctx, const int64_t *counts, int64_t n, const int64_t *map, const double *Rt, int64_t *win, double *best_rt)
+{
+    SF_LAUNCH(ctx, "k11_argmax", k11_argmax, dim3(1), dim3(1024), counts, n, map, Rt, win, best_rt);
+    return SF_OK;
+}
+
 extern "C" int sf_ransac_hypotheses(sf_ctx *ctx, const double *a_dev, const double *b_dev, int64_t m, const int64_t *draws_dev,
                                     int64_t n_draws, int draw_size, double edge_similarity, unsigned char *status_dev,
                                     double *Rt_dev)
@@ -347,12 +372,7 @@ extern "C" int sf_ransac_prerejective(sf_ctx *ctx, const double *a_dev, const do
     SF_CHECK(launch_hypotheses(ctx, "sf_ransac_prerejective", a_dev, b_dev, m, draws_dev, n_draws, draw_size, edge_similarity,
                                status_dev, Rt_all));
     if (!n_draws) return SF_OK;
-    SF_HIP(hipMemsetAsync(tallies, 0, 4 * sizeof(unsigned long long), ctx->stream));
-    SF_LAUNCH(ctx, "k11_count", k11_count, dim3((unsigned)nblocks), dim3(K11_BLOCK), (const unsigned char *)status_dev, n_draws,
-              block_count, tallies);
-    SF_LAUNCH(ctx, "k11_scan", k11_scan, dim3(1), dim3(256), (const int *)block_count, nblocks, block_off, tallies);
-    SF_LAUNCH(ctx, "k11_scatter", k11_scatter, dim3((unsigned)nblocks), dim3(K11_BLOCK), (const unsigned char *)status_dev,
-              (const double *)Rt_all, n_draws, (const int64_t *)block_off, Rt_dev, map_dev);
+    SF_CHECK(sf_k11_compact(ctx, status_dev, Rt_all, n_draws, Rt_dev, map_dev, block_count, block_off, tallies));
     // the number of survivors sizes K9's launch: the one read-back between the two halves
     void *pin = nullptr;
     SF_CHECK(sf_ctx_pinned(ctx, &pin));
@@ -367,8 +387,7 @@ extern "C" int sf_ransac_prerejective(sf_ctx *ctx, const double *a_dev, const do
     }
     if (!n_scored) return SF_OK;
     SF_CHECK(sf_ransac_score(ctx, a_dev, b_dev, m, Rt_dev, n_scored, thr, counts_dev, SF_IN_DEVICE | SF_OUT_DEVICE));
-    SF_LAUNCH(ctx, "k11_argmax", k11_argmax, dim3(1), dim3(1024), (const int64_t *)counts_dev, n_scored, (const int64_t *)map_dev,
-              (const double *)Rt_dev, dwin, dbest);
+    SF_CHECK(sf_k11_first_max(ctx, counts_dev, n_scored, map_dev, Rt_dev, dwin, dbest));
     int64_t *hw = (int64_t *)pin;
     double *hb = (double *)((char *)pin + 64);
     SF_HIP(hipMemcpyAsync(hw, dwin, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));

@@ -646,6 +646,80 @@ class Engine:
                                                      member.ptr, group_degree.ptr, _ptr(info)), "sf_consistency_sc2_group")
         return s2, member, group_degree, info
 
+    # ---- SC2 registration (K15) -------------------------------------------------------------------------------
+    SC2_MAX_SEEDS = 1024  # SF_SC2_MAX_SEEDS
+    SC2_SEED_TILE = 64    # SF_SC2_SEED_TILE: seeds of a workgroup of the seed-row GEMM
+
+    def _sc2_seed_count(self, who: str, n_seeds: int) -> int:
+        n_seeds = int(n_seeds)
+        if not 1 <= n_seeds <= self.SC2_MAX_SEEDS:
+            raise ValueError(f"{who}: n_seeds must be 1 .. {self.SC2_MAX_SEEDS}, got {n_seeds}")
+        return n_seeds
+
+    @staticmethod
+    def _sc2_outputs(who: str, n_seeds: int, arrays) -> None:
+        for arr, dt, row in arrays:
+            if arr is not None and (arr.dtype != dt or arr.nbytes < n_seeds * row):
+                raise ValueError(f"{who}: an array of the wrong type or smaller than n_seeds rows")
+
+    def sc2_seeds_device(self, s2: DeviceArray, m: int, n_seeds: int, seeds: DeviceArray) -> DeviceArray:
+        """sf_sc2_seeds: seeds (n_seeds int32, resident) <- the matches of the n_seeds largest s2 > 0, s2 descending and position
+        ascending, then -1.  Asynchronous."""
+        m, n_seeds = int(m), self._sc2_seed_count("sc2_seeds_device", n_seeds)
+        if not 0 <= m <= self.SC2_MAX_MATCHES or s2.dtype != np.uint32 or s2.nbytes < 4 * m:
+            raise ValueError(f"sc2_seeds_device: s2 must hold {m} uint32, at most {self.SC2_MAX_MATCHES}")
+        self._sc2_outputs("sc2_seeds_device", n_seeds, [(seeds, np.int32, 4)])
+        _ffi.check(self.lib.sf_sc2_seeds(self.h, s2.ptr, m, n_seeds, seeds.ptr), "sf_sc2_seeds")
+        return seeds
+
+    def sc2_seed_rows_device(self, cmat: DeviceArray, m: int, seeds: DeviceArray, n_seeds: int, rows: DeviceArray) -> DeviceArray:
+        """sf_sc2_seed_rows: rows (n_seeds x sc2_padded(m) uint32, resident) <- C[seed, j] sum_k C[seed, k] C[j, k] of a resident
+        0/1 byte matrix in K14's layout, on the int8 matrix cores.  A seed of -1 gives a zero row.  Asynchronous."""
+        m, n_seeds = int(m), self._sc2_seed_count("sc2_seed_rows_device", n_seeds)
+        self._sc2_matrix("sc2_seed_rows_device", cmat, m)
+        self._sc2_outputs("sc2_seed_rows_device", n_seeds, [(seeds, np.int32, 4), (rows, np.uint32, 4 * self.sc2_padded(m))])
+        _ffi.check(self.lib.sf_sc2_seed_rows(self.h, cmat.ptr, m, seeds.ptr, n_seeds, rows.ptr), "sf_sc2_seed_rows")
+        return rows
+
+    def sc2_seed_fits_device(self, a: DeviceArray, b: DeviceArray, m: int, seeds: DeviceArray, rows: DeviceArray, n_seeds: int,
+                             group_share: float, status: DeviceArray, size: DeviceArray, rt: DeviceArray,
+                             sums: Optional[DeviceArray] = None, member: Optional[DeviceArray] = None) -> None:
+        """sf_sc2_seed_fits: per seed the consensus set of its row (the filter's rule), its size and its Kabsch fit -> status
+        (n_seeds uint8: 0 transform, 1 fewer than three members, 2 degenerate, 3 no seed), size (n_seeds int32), rt (n_seeds x 12)
+        and, when given, sums (n_seeds x 24, the layout of `ransac_refit_sums`) and member (n_seeds x m uint8).  Asynchronous."""
+        m, n_seeds = int(m), self._sc2_seed_count("sc2_seed_fits_device", n_seeds)
+        self._consistency_sizes("sc2_seed_fits_device", a, b, m)
+        if not 0 <= m <= self.SC2_MAX_MATCHES:
+            raise ValueError(f"sc2_seed_fits_device: {m} matches, at most {self.SC2_MAX_MATCHES}")
+        self._sc2_outputs("sc2_seed_fits_device", n_seeds,
+                          [(seeds, np.int32, 4), (rows, np.uint32, 4 * self.sc2_padded(m)), (status, np.uint8, 1), (size, np.int32, 4),
+                           (rt, np.float64, 96), (sums, np.float64, 192), (member, np.uint8, m)])
+        _ffi.check(self.lib.sf_sc2_seed_fits(self.h, a.ptr, b.ptr, m, seeds.ptr, rows.ptr, n_seeds, float(group_share), status.ptr,
+                                             size.ptr, rt.ptr, None if sums is None else sums.ptr,
+                                             None if member is None else member.ptr), "sf_sc2_seed_fits")
+
+    def sc2_registration_device(self, a: DeviceArray, b: DeviceArray, m: int, distance_threshold: float, min_edge: float,
+                                n_seeds: int, group_share: float, *, s2: Optional[DeviceArray] = None,
+                                seeds: Optional[DeviceArray] = None, status: Optional[DeviceArray] = None,
+                                size: Optional[DeviceArray] = None, rt: Optional[DeviceArray] = None,
+                                slot_seed: Optional[DeviceArray] = None, counts: Optional[DeviceArray] = None
+                                ) -> tuple[np.ndarray, np.ndarray]:
+        """sf_sc2_registration: the matrix, s2, the seeds, their rows and fits, the order-preserving compaction, K9 and the first
+        maximum, queued back to back with one host wait.  Returns (result, best_rt): result = [seeds found, too small,
+        degenerate, scored, the winning seed's match or -1, its inlier count, its position among the seeds, its consensus size]
+        (int64) and the winner's 12 doubles.  The optional resident outputs receive s2 (m uint32), the seeds, status bytes and
+        sizes (n_seeds each), the compacted transforms, the slot -> seed position map and K9's counts per slot."""
+        m, n_seeds = int(m), self._sc2_seed_count("sc2_registration_device", n_seeds)
+        self._consistency_sizes("sc2_registration_device", a, b, m, u32=() if s2 is None else (s2,))
+        self._sc2_outputs("sc2_registration_device", n_seeds,
+                          [(seeds, np.int32, 4), (status, np.uint8, 1), (size, np.int32, 4), (rt, np.float64, 96),
+                           (slot_seed, np.int64, 8), (counts, np.int64, 8)])
+        result, best = np.array([0, 0, 0, 0, -1, 0, -1, 0], dtype=np.int64), np.zeros(12, dtype=np.float64)  # (what stays for m = 0)
+        opt = [None if x is None else x.ptr for x in (s2, seeds, status, size, rt, slot_seed, counts)]
+        _ffi.check(self.lib.sf_sc2_registration(self.h, a.ptr, b.ptr, m, float(distance_threshold), float(min_edge), n_seeds,
+                                                float(group_share), *opt, _ptr(result), _ptr(best)), "sf_sc2_registration")
+        return result, best
+
     # ---- multi-GPU (RCCL) -------------------------------------------------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)

@@ -5,6 +5,7 @@ from .fgr import FgrRecord, fast_global_registration
 from .match import basic_matching, double_matching_with_rejects, match_descriptors, match_two_nearest, ratio_test_matching
 from .ransac import RansacRecord, ransac_on_matches, ransac_prerejective
 from .sc2 import SecondOrderRecord, second_order_consistency_filter
+from .sc2_registration import Sc2RegistrationRecord, sc2_registration
 
 __all__ = [
     "FilterFunction",
@@ -25,4 +26,6 @@ __all__ = [
     "ConsistencyRecord",
     "second_order_consistency_filter",
     "SecondOrderRecord",
+    "sc2_registration",
+    "Sc2RegistrationRecord",
 ]

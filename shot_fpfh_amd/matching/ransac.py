@@ -297,23 +297,8 @@ def ransac_prerejective(
         if record.n_scored == 0:
             raise ValueError(f"no draw survived: {record.n_rejected} of {n_draws} rejected by the edge test at similarity "
                              f"{edge_similarity}, {record.n_degenerate} degenerate")
-        current, count = np.array(best, dtype=np.float64), record.winner_inliers
-        sums = eng.ransac_refit_sums(matched.a, matched.b, n_matches, current, thr) if refit_iterations else None
-        for _ in range(refit_iterations):
-            if int(sums[0]) < 3:
-                break
-            fit = kabsch_from_covariance(sums[7:16].reshape(3, 3), sums[1:4], sums[4:7]).as_row12()
-            if not np.isfinite(fit).all():
-                break
-            new_sums = eng.ransac_refit_sums(matched.a, matched.b, n_matches, fit, thr)
-            new_count = int(new_sums[0])
-            if new_count < count:
-                break
-            unchanged = new_count == count
-            current, count, sums = fit, new_count, new_sums
-            record.refit_inliers.append(new_count)
-            if unchanged:
-                break
+        current, count, record.refit_inliers = _refit_over_inliers(eng, matched, n_matches, best, record.winner_inliers, thr,
+                                                                   refit_iterations)
     finally:
         for h in held:
             h.free()
@@ -324,6 +309,32 @@ def ransac_prerejective(
     transform = RigidTransform(current[:9].reshape(3, 3).copy(), current[9:].copy())
     transform.normalize_rotation()
     return count / n_matches, transform, record
+
+
+def _refit_over_inliers(eng: Engine, matched, n_matches: int, best, count: int, thr: float, refit_iterations: int
+                        ) -> tuple[np.ndarray, int, list]:
+    """The refit of a winning transform (`ransac_prerejective`, `sc2_registration`): refit_iterations times the Kabsch fit over
+    ALL inliers of the current transform -- sums on the device (sf_ransac_refit_sums), the 3 x 3 problem on the host -- kept while
+    the inlier count does not drop, stopped when it no longer changes or fewer than 3 inliers are left.  Returns (the 12 doubles
+    of the final transform, its inlier count, the counts after each kept refit)."""
+    current, kept = np.array(best, dtype=np.float64), []
+    sums = eng.ransac_refit_sums(matched.a, matched.b, n_matches, current, thr) if refit_iterations else None
+    for _ in range(refit_iterations):
+        if int(sums[0]) < 3:
+            break
+        fit = kabsch_from_covariance(sums[7:16].reshape(3, 3), sums[1:4], sums[4:7]).as_row12()
+        if not np.isfinite(fit).all():
+            break
+        new_sums = eng.ransac_refit_sums(matched.a, matched.b, n_matches, fit, thr)
+        new_count = int(new_sums[0])
+        if new_count < count:
+            break
+        unchanged = new_count == count
+        current, count, sums = fit, new_count, new_sums
+        kept.append(new_count)
+        if unchanged:
+            break
+    return current, count, kept
 
 
 def _solve_chunk(scan_d: np.ndarray, ref_d: np.ndarray, records: np.ndarray) -> None:

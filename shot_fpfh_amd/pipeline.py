@@ -28,6 +28,7 @@ from .matching import (
     geometric_consistency_filter,
     ransac_on_matches,
     ransac_prerejective,
+    sc2_registration,
     ratio_test_matching,
     second_order_consistency_filter,
     threshold_filter,
@@ -216,14 +217,16 @@ class RegistrationPipeline:
     # ---- stage 4: coarse registration (pipeline.py:445-486) ----------------------------------------------------
     def run_ransac(self, *, n_draws: int = 10000, draw_size: int = 4, max_inliers_distance: float = 2,
                    exact_transformation: RigidTransform | None = None,
-                   disable_progress_bar: bool = False, method: Literal["reference", "prerejective", "fgr"] = "reference",
+                   disable_progress_bar: bool = False, method: Literal["reference", "prerejective", "fgr", "sc2"] = "reference",
                    edge_similarity: float = 0.9, refit_iterations: int = 2, fgr_iterations: int = 64,
-                   fgr_tuple_count: int = 0) -> tuple[RigidTransform, float]:
+                   fgr_tuple_count: int = 0, sc2_seeds: int = 256) -> tuple[RigidTransform, float]:
         """method="reference": the reference's RANSAC.  method="prerejective": draws that fail the edge-length test at
         `edge_similarity` are dropped unscored and the winner is refitted over its inliers `refit_iterations` times (three
         points determine the fit: pass draw_size=3 there, the default of `ransac_prerejective` itself).  method="fgr": fast global
         registration, which draws nothing -- `max_inliers_distance` is its threshold, `n_draws` and `draw_size` are ignored,
-        `fgr_iterations` Gauss-Newton steps are taken over all matches (or over `fgr_tuple_count` tuples of them)."""
+        `fgr_iterations` Gauss-Newton steps are taken over all matches (or over `fgr_tuple_count` tuples of them).
+        method="sc2": `sc2_registration`, one fit per second-order seed -- `max_inliers_distance` is its threshold, `sc2_seeds`
+        the number of seeds, the winner is refitted `refit_iterations` times, `n_draws` and `draw_size` are ignored."""
         logging.info(" -- Aligning the point clouds by RANSAC-ing the matches --")
         if method == "reference":
             inliers_ratio, transformation = ransac_on_matches(
@@ -241,6 +244,12 @@ class RegistrationPipeline:
                 *self.matches, self.scan[self.scan_keypoints], self.ref[self.ref_keypoints],
                 distance_threshold=max_inliers_distance, iterations=fgr_iterations, tuple_count=fgr_tuple_count)
             logging.info(f"{fgr_record.iterations} iterations over {fgr_record.rows} rows, {fgr_record.inliers} inliers")
+        elif method == "sc2":
+            inliers_ratio, transformation, sc2_record = sc2_registration(
+                *self.matches, self.scan[self.scan_keypoints], self.ref[self.ref_keypoints],
+                distance_threshold=max_inliers_distance, n_seeds=sc2_seeds, refit_iterations=refit_iterations)
+            logging.info(f"{sc2_record.n_scored} of {sc2_record.seeds.shape[0]} seeds scored, inliers {sc2_record.winner_inliers} -> "
+                         f"{sc2_record.refit_inliers}")
         else:
             raise ValueError("Incorrect RANSAC method selected.")
         if exact_transformation is not None:
