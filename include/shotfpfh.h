@@ -559,6 +559,22 @@ int sf_icp_accumulate(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const i
                       double d_max, int mode, double *sums /* 40 */);
 int sf_transform_points(sf_ctx *ctx, double *pts_dev, int64_t n, const double *Rt /* 12 */);
 
+/* ---- generalized (plane-to-plane) ICP, K16 (Segal, Haehnel, Thrun, RSS 2009; no counterpart in the reference) --------
+ * One iteration's device work, the chain of the call above with a third sums pass.  Every point carries the covariance
+ * C = I - (1 - epsilon) n n^T of its unit normal n (a zero normal: C = I; the sign of n does not matter).  The reference
+ * cloud needs normals; nrm_dev holds the scan's, one row per row of pts_dev (n x 3 doubles on the device), and a row is
+ * reached through sel_dev exactly as its point is (repeated ids allowed).  Rt as above; NULL leaves the normals alone too.
+ * For a kept pair (distance <= d_max) with p the moved point, b its neighbour, nb b's normal and m = R n_scan:
+ *   S = 2 I - (1 - epsilon) (nb nb^T + m m^T),  M = S^-1 (symmetric adjugate over the determinant),  r = b - p,
+ *   J = [-[p]x, I] (3 x 6).
+ * sums[40] (host):
+ *   [0] pair count, [1..3] sum of p, [4..6] sum of b,
+ *   [8..28] upper triangle of H = sum J^T M J, row by row, [29..34] g = sum J^T M r,
+ *   [35] sum r^T M r, [36] sum |r|^2; the rest is zero.
+ * The Gauss-Newton step is xi = H^-1 g, (rotation vector, translation), applied on the left.  0 < epsilon <= 1. */
+int sf_icp_accumulate_gicp(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev /* n x 3, scan normals */,
+                           const int64_t *sel_dev, int64_t m, const double *Rt, double d_max, double epsilon, double *sums /* 40 */);
+
 /* ---- multi-GPU: RCCL over xGMI (no counterpart in the reference) --------------------------
  * One process per GPU.  Rank 0 calls sf_comm_unique_id, ships the 128 bytes to the other ranks by
  * any host channel, then every rank calls sf_comm_init.  sf_comm_allgather gathers

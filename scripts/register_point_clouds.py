@@ -61,7 +61,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--ransac-edge-similarity", type=float, default=0.9), p.add_argument("--ransac-refit", type=int, default=2)
     p.add_argument("--ransac-threshold", type=float, default=1.0)
     p.add_argument("--fgr-iterations", type=int, default=64), p.add_argument("--fgr-tuples", type=int, default=0)
-    p.add_argument("--icp", default="point_to_plane", choices=["point_to_point", "point_to_plane", "none"])
+    p.add_argument("--icp", default="point_to_plane", choices=["point_to_point", "point_to_plane", "generalized", "none"],
+                   help="generalized: plane-to-plane ICP, every pair weighted by the local surface of both clouds")
+    p.add_argument("--gicp-neighbors", type=int, default=20, metavar="K",
+                   help="--icp generalized: neighbours of a normal that the clouds do not bring along")
+    p.add_argument("--gicp-epsilon", type=float, default=1e-3, metavar="EPS",
+                   help="--icp generalized: a point's covariance along its normal, in (0, 1]")
     p.add_argument("--icp-dmax", type=float, default=0.5), p.add_argument("--icp-voxel", type=float, default=0.2)
     p.add_argument("--icp-max-iter", type=int, default=50), p.add_argument("--icp-rms", type=float, default=1e-3)
     p.add_argument("--metric-threshold", type=float, default=0.1)
@@ -101,7 +106,8 @@ def main(argv=None) -> int:
     if args.icp != "none":
         transformation, rms, converged = pipe.run_icp(args.icp, transformation, d_max=args.icp_dmax, voxel_size=args.icp_voxel,
                                                        max_iter=args.icp_max_iter, rms_threshold=args.icp_rms,
-                                                       disable_progress_bar=True)
+                                                       disable_progress_bar=True, gicp_neighbors=args.gicp_neighbors,
+                                                       gicp_epsilon=args.gicp_epsilon)
         logging.info(f"ICP rms {rms:.3e}, converged: {bool(converged)}\n{transformation}")
         if args.write:
             outputs.append((f"{args.write}_icp.ply", transformation))

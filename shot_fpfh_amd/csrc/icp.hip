@@ -14,6 +14,10 @@
 // Sums are accumulated per thread, folded per block (shuffles + LDS) and then over the block partials by ONE block in a
 // fixed order, so a run is reproducible bit for bit.  Point-to-point is centred in a second pass (centroids first),
 // which keeps the cross-covariance free of cancellation, like the reference's explicit centring.
+//
+// K16, generalized (plane-to-plane) ICP (Segal, Haehnel, Thrun, RSS 2009; no counterpart in the reference): the same chain
+// with a third pass B, k_gicp_sums, which weights every pair by M = (C_b + R C_a R^T)^-1, C = I - (1 - eps) n n^T from the
+// unit normal of either point, and leaves the 6x6 Gauss-Newton system of sum r^T M r for the host (sf_icp_accumulate_gicp).
 #include "common.h"
 #include "device_util.h"
 
@@ -112,6 +116,87 @@ __global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx,
     block_fold<NV>(acc, partial + (size_t)blockIdx.x * ICP_NV);
 }
 
+// pass B of generalized ICP (K16).  Per kept pair, with p the moved scan point, b its nearest reference point, nb b's normal,
+// na the scan point's normal (row qrow[slot] of the scan, through sel) and c = 1 - eps -- every line one rounding per
+// operation, left to right, which tests/gicp_numpy.py repeats operation by operation:
+//   m   = (na.x R0 + na.y R1) + na.z R2 per row of R (no t; m = na when Rt is null)
+//   S   = 2 I - c (nb nb^T + m m^T):  S_ii = 2 - c (nb_i nb_i + m_i m_i),  S_ij = -(c (nb_i nb_j + m_i m_j))
+//   adj = symmetric adjugate of S, each entry ONE difference of two products; det = (S00 adj00 + S01 adj01) + S02 adj02
+//   M   = adj * (1 / det)                                                    (six entries)
+//   r   = b - p,  u = M r with u_i = (M_i0 r0 + M_i1 r1) + M_i2 r2
+//   Q   = [p]x M  (Q_0j = py M_2j - pz M_1j, ...),  T = Q [p]x^T  (T_i0 = py Q_i2 - pz Q_i1, ...)
+//   H   = J^T M J = [[T, Q], [Q^T, M]] (upper triangle, 21),  g = J^T M r = [p x u; u] (6),  r.u,  |r|^2  with J = [-[p]x, I]
+// A zero normal makes its dyad vanish (C = I); the sign of a normal cancels in the dyad.
+__global__ __launch_bounds__(256) void k_gicp_sums(const double *__restrict__ qx, const double *__restrict__ qy,
+                                                   const double *__restrict__ qz, const int32_t *__restrict__ idx,
+                                                   const int32_t *__restrict__ qrow, const double *__restrict__ rec,
+                                                   const double *__restrict__ nrm, const int64_t *__restrict__ sel,
+                                                   const double *__restrict__ Rt, int64_t m, double d_max, double epsilon,
+                                                   double *__restrict__ partial)
+{
+    constexpr int NV = 29;
+    double acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (Rt) {
+#pragma unroll
+        for (int v = 0; v < 9; ++v) R[v] = Rt[v];
+    }
+    const double c = 1.0 - epsilon;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const double px = qx[i], py = qy[i], pz = qz[i];
+        double x, y, z, bx, by, bz;
+        sf_load_pn(rec, idx[i], x, y, z, bx, by, bz);
+        const double r0 = x - px, r1 = y - py, r2 = z - pz;
+        const double d2 = (r0 * r0 + r1 * r1) + r2 * r2;
+        if (!(sqrt(d2) <= d_max)) continue; // the test k_icp_sums makes
+        const int64_t row = qrow ? (int64_t)qrow[i] : i;
+        const int64_t j = sel ? sel[row] : row;
+        const double ax = nrm[3 * j], ay = nrm[3 * j + 1], az = nrm[3 * j + 2];
+        double m0 = ax, m1 = ay, m2 = az;
+        if (Rt) {
+            m0 = (ax * R[0] + ay * R[1]) + az * R[2];
+            m1 = (ax * R[3] + ay * R[4]) + az * R[5];
+            m2 = (ax * R[6] + ay * R[7]) + az * R[8];
+        }
+        const double s00 = 2.0 - c * (bx * bx + m0 * m0), s11 = 2.0 - c * (by * by + m1 * m1), s22 = 2.0 - c * (bz * bz + m2 * m2);
+        const double s01 = -(c * (bx * by + m0 * m1)), s02 = -(c * (bx * bz + m0 * m2)), s12 = -(c * (by * bz + m1 * m2));
+        const double a00 = s11 * s22 - s12 * s12, a01 = s02 * s12 - s01 * s22, a02 = s01 * s12 - s02 * s11;
+        const double a11 = s00 * s22 - s02 * s02, a12 = s01 * s02 - s00 * s12, a22 = s00 * s11 - s01 * s01;
+        const double det = (s00 * a00 + s01 * a01) + s02 * a02;
+        const double inv = 1.0 / det;
+        const double M[3][3] = {{a00 * inv, a01 * inv, a02 * inv}, {a01 * inv, a11 * inv, a12 * inv}, {a02 * inv, a12 * inv, a22 * inv}};
+        double Q[3][3], u[3];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            Q[0][b] = py * M[2][b] - pz * M[1][b];
+            Q[1][b] = pz * M[0][b] - px * M[2][b];
+            Q[2][b] = px * M[1][b] - py * M[0][b];
+            u[b] = (M[b][0] * r0 + M[b][1] * r1) + M[b][2] * r2;
+        }
+        acc[0] += py * Q[0][2] - pz * Q[0][1];  // H row 0: T00 T01 T02 Q00 Q01 Q02
+        acc[1] += pz * Q[0][0] - px * Q[0][2];
+        acc[2] += px * Q[0][1] - py * Q[0][0];
+        acc[3] += Q[0][0]; acc[4] += Q[0][1]; acc[5] += Q[0][2];
+        acc[6] += pz * Q[1][0] - px * Q[1][2];  // row 1: T11 T12 Q10 Q11 Q12
+        acc[7] += px * Q[1][1] - py * Q[1][0];
+        acc[8] += Q[1][0]; acc[9] += Q[1][1]; acc[10] += Q[1][2];
+        acc[11] += px * Q[2][1] - py * Q[2][0]; // row 2: T22 Q20 Q21 Q22
+        acc[12] += Q[2][0]; acc[13] += Q[2][1]; acc[14] += Q[2][2];
+        acc[15] += M[0][0]; acc[16] += M[0][1]; acc[17] += M[0][2]; // rows 3 .. 5: M
+        acc[18] += M[1][1]; acc[19] += M[1][2];
+        acc[20] += M[2][2];
+        acc[21] += py * u[2] - pz * u[1];       // g = [p x u; u]
+        acc[22] += pz * u[0] - px * u[2];
+        acc[23] += px * u[1] - py * u[0];
+        acc[24] += u[0]; acc[25] += u[1]; acc[26] += u[2];
+        acc[27] += (r0 * u[0] + r1 * u[1]) + r2 * u[2];
+        acc[28] += d2;
+    }
+    block_fold<NV>(acc, partial + (size_t)blockIdx.x * ICP_NV);
+}
+
 // fold the block partials in block order; pass A also leaves the centroids (means) for pass B
 __global__ __launch_bounds__(64) void k_icp_final(const double *__restrict__ partial, int nblocks, int nv, double *__restrict__ out,
                                                   double *__restrict__ mean)
@@ -182,6 +267,46 @@ extern "C" int sf_icp_accumulate(sf_ctx *ctx, sf_cloud *ref, const double *pts_d
                   (const double *)nullptr, partial);
         SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, 28, dout + 8, (double *)nullptr);
     }
+    SF_HIP(hipMemcpyAsync(sums, dout, 40 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    return SF_OK;
+}
+
+extern "C" int sf_icp_accumulate_gicp(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev, const int64_t *sel_dev,
+                                      int64_t m, const double *Rt, double d_max, double epsilon, double *sums)
+{
+    if (!ctx || !ref || !pts_dev || !nrm_dev || !sums || m < 0 || !(epsilon > 0.0 && epsilon <= 1.0)) {
+        sf_set_error("sf_icp_accumulate_gicp: bad argument (epsilon must lie in (0, 1])");
+        return SF_ERR_ARG;
+    }
+    SF_HIP(hipSetDevice(ctx->device));
+    for (int i = 0; i < 40; ++i) sums[i] = 0.0;
+    if (!m) return SF_OK;
+    if (ref->n < 1) { sf_set_error("sf_icp_accumulate_gicp: empty reference cloud"); return SF_ERR_ARG; }
+    sf_pool_guard tmp(ctx);
+    double *dRt = nullptr, *moved = nullptr, *partial = nullptr, *dout = nullptr, *dmean = nullptr;
+    if (Rt) {
+        SF_CHECK(tmp.alloc(&dRt, 12));
+        SF_HIP(hipMemcpyAsync(dRt, Rt, 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    SF_CHECK(tmp.alloc(&moved, (size_t)m * 3));
+    SF_CHECK(tmp.alloc(&partial, (size_t)ICP_BLOCKS * ICP_NV));
+    SF_CHECK(tmp.alloc(&dout, 80));
+    SF_CHECK(tmp.alloc(&dmean, 8));
+    SF_LAUNCH(ctx, "i0_transform", k_transform, dim3((unsigned)sf_div_up(m, 256)), dim3(256), pts_dev, sel_dev, m,
+              (const double *)dRt, moved);
+    sf_nbrs *nb = sf_knn_search(ctx, ref, moved, m, 1, SF_IN_DEVICE);
+    if (!nb) return SF_ERR_HIP;
+    struct nb_guard { sf_ctx *c; sf_nbrs *n; ~nb_guard() { sf_nbrs_free(c, n); } } nbg{ctx, nb};
+    SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, ref)); // fails when the reference cloud was uploaded without normals
+    SF_HIP(hipMemsetAsync(dout, 0, 40 * sizeof(double), ctx->stream)); // [7] and [37..39] belong to no pass
+    const dim3 grid(ICP_BLOCKS), block(256);
+    SF_LAUNCH(ctx, "i1_icp_sums", (k_icp_sums<0, 0>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, ref->rec, m, d_max,
+              (const double *)nullptr, partial);
+    SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, 7, dout, dmean);
+    SF_LAUNCH(ctx, "i2_gicp_sums", k_gicp_sums, grid, block, nb->qx, nb->qy, nb->qz, nb->idx, (const int32_t *)nb->qrow, ref->rec,
+              nrm_dev, sel_dev, (const double *)dRt, m, d_max, epsilon, partial);
+    SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, 29, dout + 8, (double *)nullptr);
     SF_HIP(hipMemcpyAsync(sums, dout, 40 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
     return SF_OK;

@@ -8,8 +8,13 @@ points and the reference cloud live in HBM for the whole run and ONE device call
 csrc/icp.hip) does the transform, the nearest-neighbour search (grid k-NN kernel, k = 1), the `d_max` filter and the
 reductions; what crosses the bus per iteration is a 12-number transform one way and ~30 sums the other.  The host keeps
 only the tiny dense step -- a 3x3 SVD (`_rigid_fit`) or a 6x6 solve (`_plane_fit`) on those sums -- and the bookkeeping of
-the running transform.  `_Registration` is that device state; the three public functions differ only in which rows they
+the running transform.  `_Registration` is that device state; the public functions differ only in which rows they
 feed it, which fit they ask for and what they return.
+
+`icp_generalized` (K16) has no counterpart in the reference: generalized, or plane-to-plane, ICP (Segal, Haehnel, Thrun, RSS
+2009).  Every point carries the covariance C = I - (1 - epsilon) n n^T of its unit normal, a pair (a, b) is weighted by
+M = (C_b + R C_a R^T)^-1, and the device call (`sf_icp_accumulate_gicp`, the same chain with a third sums pass) returns the
+6x6 Gauss-Newton system of sum r^T M r; the host solves it and applies the exact exponential of the step (`_gicp_fit`).
 
 Deviation, on purpose: the reference's `icp_point_to_point` computes its RMS from `ref[neighbors]` (all queried points,
 shape (n, 1, 3)) instead of `ref[inliers_neighbors]` (icp.py:122-124); the broadcast yields an array, and formatting it for
@@ -20,6 +25,7 @@ from __future__ import annotations
 
 import ctypes as C
 import logging
+import math
 from typing import Optional
 
 import numpy as np
@@ -29,17 +35,19 @@ from scipy.spatial.transform import Rotation
 from . import _ffi
 from .core import RigidTransform, grid_subsampling
 from .core.geometry import kabsch_from_covariance
+from .descriptors.normals import compute_normals
 from .engine import Cloud, DeviceArray, Engine, default_engine
 
 __all__ = [
     "icp_point_to_point_with_sampling",
     "icp_point_to_point",
     "icp_point_to_plane",
+    "icp_generalized",
     "compute_point_to_point_error",
     "nearest_within",
 ]
 
-_POINT, _PLANE = 0, 1
+_POINT, _PLANE, _GICP = 0, 1, 2
 _TRIU = np.triu_indices(6)
 
 
@@ -47,6 +55,7 @@ class _PairSums:
     """What one device pass returns about the inlier pairs (p = moved working point, q = its nearest reference point)."""
 
     def __init__(self, raw: np.ndarray, mode: int):
+        self.raw = raw
         self.count = int(raw[0])
         self.sum_p, self.sum_q = raw[1:4], raw[4:7]
         if mode == _POINT:
@@ -57,7 +66,11 @@ class _PairSums:
             self.gtg[_TRIU] = raw[8:29]
             self.gtg = self.gtg + np.triu(self.gtg, 1).T
             self.gth = raw[29:35]
-            self.abs_h = float(raw[35])               # sum |(q - p) . n|
+            if mode == _PLANE:
+                self.abs_h = float(raw[35])           # sum |(q - p) . n|
+            else:                                     # generalized: gtg = sum J^T M J, gth = sum J^T M r, J = [-[p]x, I], r = q - p
+                self.mahalanobis = float(raw[35])     # sum r^T M r
+                self.sq_dist = float(raw[36])         # sum |r|^2
 
     def require_pairs(self) -> None:
         if self.count == 0:
@@ -77,10 +90,30 @@ def _plane_fit(s: _PairSums) -> RigidTransform:
     return RigidTransform(Rotation.from_euler("xyz", sol[:3]).as_matrix(), sol[3:6])
 
 
-class _Registration:
-    """Working points + reference cloud resident on one GPU for the length of an ICP run."""
+def _rodrigues(omega: np.ndarray) -> np.ndarray:
+    """exp([omega]x) = I + (sin th / th) K + 1/2 (sin(th/2) / (th/2))^2 K^2, K = [omega]x, th = |omega|."""
+    th = math.sqrt((omega[0] * omega[0] + omega[1] * omega[1]) + omega[2] * omega[2])
+    if not th > 0.0:
+        return np.eye(3)
+    ca = math.sin(th) / th
+    h = math.sin(0.5 * th) / (0.5 * th)
+    K = np.array([[0.0, -omega[2], omega[1]], [omega[2], 0.0, -omega[0]], [-omega[1], omega[0], 0.0]])
+    return np.eye(3) + ca * K + (0.5 * (h * h)) * (K @ K)
 
-    def __init__(self, points, ref, ref_normals=None, engine: Optional[Engine] = None):
+
+def _gicp_fit(s: _PairSums) -> RigidTransform:
+    """Gauss-Newton step of sum r^T M r from H = sum J^T M J and g = sum J^T M r: the EXACT exponential of the rotation part
+    (`_plane_fit`'s Euler product is the reference's and stays with it)."""
+    s.require_pairs()
+    s.step = np.linalg.solve(s.gtg, s.gth)
+    return RigidTransform(_rodrigues(s.step[:3]), s.step[3:6])
+
+
+class _Registration:
+    """Working points + reference cloud resident on one GPU for the length of an ICP run; for generalized ICP also the
+    working points' normals (`scan_normals`, one unit or zero row per point)."""
+
+    def __init__(self, points, ref, ref_normals=None, engine: Optional[Engine] = None, scan_normals=None):
         self.engine = engine or default_engine()
         self.ref = Cloud(self.engine, ref, ref_normals)
         pts = np.ascontiguousarray(points, dtype=np.float64)
@@ -89,8 +122,16 @@ class _Registration:
         self.n = pts.shape[0]
         self.points: DeviceArray = self.engine.empty((max(self.n, 1), 3)).from_host(pts if self.n else np.zeros((1, 3)))
         self.rows: Optional[DeviceArray] = None
+        self.normals: Optional[DeviceArray] = None
+        if scan_normals is not None:
+            nrm = np.ascontiguousarray(scan_normals, dtype=np.float64)
+            if nrm.shape != pts.shape:
+                self.close()
+                raise ValueError(f"scan normals of shape {nrm.shape} for points of shape {pts.shape}")
+            self.normals = self.engine.empty((max(self.n, 1), 3)).from_host(nrm if self.n else np.zeros((1, 3)))
 
-    def pairs(self, mode: int, d_max: float, moved_by: Optional[RigidTransform] = None, rows=None) -> _PairSums:
+    def pairs(self, mode: int, d_max: float, moved_by: Optional[RigidTransform] = None, rows=None,
+              epsilon: float = 1e-3) -> _PairSums:
         """Inlier-pair sums of the working points (all of them, or the given `rows`) after `moved_by`."""
         m, sel = self.n, None
         if rows is not None:
@@ -105,6 +146,16 @@ class _Registration:
             sel = self.rows.ptr
         rt = None if moved_by is None else np.ascontiguousarray(moved_by.as_row12())
         raw = np.zeros(40)
+        if mode == _GICP:
+            if self.normals is None:
+                raise ValueError("generalized ICP needs the normals of the working points")
+            _ffi.check(
+                self.engine.lib.sf_icp_accumulate_gicp(self.engine.h, self.ref.h, self.points.ptr, self.normals.ptr, sel, m,
+                                                       None if rt is None else rt.ctypes.data_as(C.c_void_p), float(d_max),
+                                                       float(epsilon), raw.ctypes.data_as(C.c_void_p)),
+                "sf_icp_accumulate_gicp",
+            )
+            return _PairSums(raw, mode)
         _ffi.check(
             self.engine.lib.sf_icp_accumulate(self.engine.h, self.ref.h, self.points.ptr, sel, m,
                                               None if rt is None else rt.ctypes.data_as(C.c_void_p), float(d_max), mode,
@@ -123,7 +174,7 @@ class _Registration:
         return self.points.to_host()[: self.n]
 
     def close(self) -> None:
-        for obj in (self.points, self.rows, self.ref):
+        for obj in (self.points, self.rows, self.normals, self.ref):
             if obj is not None:
                 obj.free()
 
@@ -159,23 +210,34 @@ def icp_point_to_point_with_sampling(
         reg.close()
 
 
-def _refine(reg: _Registration, start: RigidTransform, mode: int, d_max: float, max_iter: int, rms_threshold: float):
-    """The loop shared by icp_point_to_point and icp_point_to_plane: the working points stay where they are, the
-    running transform is what moves (icp.py:103-130, 155-189)."""
-    total, rms = start, 0.0
-    fit = _rigid_fit if mode == _POINT else _plane_fit
+def _refine(reg: _Registration, start: RigidTransform, mode: int, d_max: float, max_iter: int, rms_threshold: float,
+            epsilon: float = 1e-3, step_tolerance: float = 0.0):
+    """The loop shared by icp_point_to_point, icp_point_to_plane and icp_generalized: the working points stay where they are,
+    the running transform is what moves (icp.py:103-130, 155-189).  Generalized ICP also stops, converged, once no component of
+    its step reaches `step_tolerance`."""
+    total, rms, small_step = start, 0.0, False
+    fit = {_POINT: _rigid_fit, _PLANE: _plane_fit, _GICP: _gicp_fit}[mode]
     try:
         for _ in range(max_iter):
-            found = reg.pairs(mode, d_max, moved_by=total)
+            found = reg.pairs(mode, d_max, moved_by=total, epsilon=epsilon)
             total = fit(found) @ total
             # residual of the pairs the fit was computed FROM (before this iteration's update), as in the reference
-            rms = float(np.sqrt(found.sq_dist)) if mode == _POINT else found.abs_h / found.count
+            if mode == _POINT:
+                rms = float(np.sqrt(found.sq_dist))
+            elif mode == _PLANE:
+                rms = found.abs_h / found.count
+            else:
+                rms = float(np.sqrt(found.sq_dist / found.count))
+                small_step = bool(np.abs(found.step).max() < step_tolerance)
             if rms < rms_threshold:
                 logging.info("RMS threshold reached.")
                 break
+            if small_step:
+                logging.info("Step tolerance reached.")
+                break
     except KeyboardInterrupt:
         logging.info("ICP interrupted by user.")
-    return total, rms, rms < rms_threshold
+    return total, rms, rms < rms_threshold or small_step
 
 
 def icp_point_to_point(
@@ -214,6 +276,58 @@ def icp_point_to_plane(
     reg = _Registration(scan[grid_subsampling(scan, voxel_size)], ref, ref_normals)
     try:
         return _refine(reg, transformation_init, _PLANE, d_max, max_iter, rms_threshold)
+    finally:
+        reg.close()
+
+
+def _unit_rows(normals, n: int, what: str) -> np.ndarray:
+    """(n, 3) float64 rows scaled to unit length on the host; zero rows stay zero."""
+    nrm = np.array(normals, dtype=np.float64)
+    if nrm.shape != (n, 3):
+        raise ValueError(f"{what} of shape {nrm.shape}: expected ({n}, 3), one row per point")
+    length = np.sqrt((nrm[:, 0] * nrm[:, 0] + nrm[:, 1] * nrm[:, 1]) + nrm[:, 2] * nrm[:, 2])
+    return np.ascontiguousarray(nrm / np.where(length > 0.0, length, 1.0)[:, None])
+
+
+def icp_generalized(
+    scan: npt.NDArray[np.float64],
+    ref: npt.NDArray[np.float64],
+    transformation_init: RigidTransform,
+    d_max: float,
+    *,
+    scan_normals: Optional[npt.NDArray[np.float64]] = None,
+    ref_normals: Optional[npt.NDArray[np.float64]] = None,
+    k_normals: int = 20,
+    epsilon: float = 1e-3,
+    voxel_size: float = 0.2,
+    max_iter: int = 50,
+    rms_threshold: float = 1e-2,
+    step_tolerance: float = 1e-9,
+) -> tuple[RigidTransform, float, bool]:
+    """Generalized (plane-to-plane) ICP, K16: every pair is weighted by the local surface of BOTH clouds, a point's covariance
+    being I - (1 - epsilon) n n^T of its unit normal.  Normals that are not given are computed on the full clouds from
+    `k_normals` neighbours; the scan is then voxel-subsampled like its siblings' and its normals follow the selection.
+    Returns (transform, rms = sqrt(mean squared distance) of the pairs the last step was fitted on, converged); converged
+    means rms < rms_threshold or a step whose largest component is below step_tolerance."""
+    scan, ref = np.asarray(scan, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    for name, a in (("scan", scan), ("ref", ref)):
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name}: expected an (N, 3) array, got shape {a.shape}")
+    if not 0.0 < epsilon <= 1.0:
+        raise ValueError(f"epsilon={epsilon} must lie in (0, 1]")
+    if not step_tolerance >= 0.0:
+        raise ValueError(f"step_tolerance={step_tolerance} must not be negative")
+    given = [None if nrm is None else _unit_rows(nrm, a.shape[0], f"{name} normals")
+             for name, a, nrm in (("scan", scan, scan_normals), ("ref", ref, ref_normals))]
+    for name, a, nrm in (("scan", scan, given[0]), ("ref", ref, given[1])):
+        if nrm is None and not 3 <= int(k_normals) <= a.shape[0]:
+            raise ValueError(f"k_normals={k_normals} must be between 3 and the number of {name} points ({a.shape[0]})")
+    scan_normals, ref_normals = (nrm if nrm is not None else _unit_rows(compute_normals(a, a, k=int(k_normals)), a.shape[0], "normals")
+                                 for a, nrm in ((scan, given[0]), (ref, given[1])))
+    keep = grid_subsampling(scan, voxel_size)
+    reg = _Registration(scan[keep], ref, ref_normals, scan_normals=scan_normals[keep])
+    try:
+        return _refine(reg, transformation_init, _GICP, d_max, max_iter, rms_threshold, epsilon, step_tolerance)
     finally:
         reg.close()
 

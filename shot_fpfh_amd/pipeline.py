@@ -19,7 +19,7 @@ from . import keypoint_selection as _ks
 from .core import RigidTransform
 from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor
 from .helpers import write_ply
-from .icp import icp_point_to_plane, icp_point_to_point, nearest_within
+from .icp import icp_generalized, icp_point_to_plane, icp_point_to_point, nearest_within
 from .matching import (
     basic_matching,
     double_matching_with_rejects,
@@ -260,15 +260,22 @@ class RegistrationPipeline:
         return transformation, inliers_ratio
 
     # ---- stage 5: fine registration (pipeline.py:488-542) ---------------------------------------------------------
-    def run_icp(self, icp_type: Literal["point_to_point", "point_to_plane"], transformation_init: RigidTransform, *,
+    def run_icp(self, icp_type: Literal["point_to_point", "point_to_plane", "generalized"], transformation_init: RigidTransform, *,
                 d_max: float, voxel_size: float = 0.2, max_iter: int = 30, rms_threshold: float = 1e-2,
-                disable_progress_bar: bool = False) -> tuple[RigidTransform, float, bool]:
+                disable_progress_bar: bool = False, gicp_neighbors: int = 20,
+                gicp_epsilon: float = 1e-3) -> tuple[RigidTransform, float, bool]:
+        """"generalized" (K16, no counterpart in the reference): plane-to-plane ICP with the pipeline's reference normals and
+        scan normals from `gicp_neighbors` neighbours of the full scan (the scan's stored normals when it has them)."""
         common = dict(d_max=d_max, voxel_size=voxel_size, max_iter=max_iter, rms_threshold=rms_threshold,
                       disable_progress_bar=disable_progress_bar)
         if icp_type == "point_to_point":
             return icp_point_to_point(self.scan, self.ref, transformation_init, **common)
         if icp_type == "point_to_plane":
             return icp_point_to_plane(self.scan, self.ref, self.ref_normals, transformation_init, **common)
+        if icp_type == "generalized":
+            return icp_generalized(self.scan, self.ref, transformation_init, d_max, scan_normals=self.scan_normals,
+                                   ref_normals=self.ref_normals, k_normals=gicp_neighbors, epsilon=gicp_epsilon,
+                                   voxel_size=voxel_size, max_iter=max_iter, rms_threshold=rms_threshold)
         raise ValueError("Incorrect ICP type selected.")
 
     # ---- evaluation / output (pipeline.py:544-608) ---------------------------------------------------------------------
