@@ -553,7 +553,8 @@ void sf_voxels_free(sf_ctx *ctx, sf_voxels *vox);
  *     [0] inlier count, [1..3] sum of inlier points p, [4..6] sum of their neighbours q,
  *     mode 0 (point to point): [8..16] sum (p - pbar)(q - qbar)^T row-major, [17] sum |p - q|^2
  *     mode 1 (point to plane; the cloud needs normals): [8..28] upper triangle of G^T G row by row, [29..34] G^T h,
- *       [35] sum |h|, with g = [p x n, n], h = (q - p) . n.
+ *       [35] sum |h|, with g = [p x n, n], h = (q - p) . n;
+ *     the rest is zero, and so is everything when no pair is kept.
  * sf_transform_points: p <- p R^T + t in place on resident points (RigidTransform.__getitem__). */
 int sf_icp_accumulate(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const int64_t *sel_dev, int64_t m, const double *Rt,
                       double d_max, int mode, double *sums /* 40 */);

@@ -253,6 +253,7 @@ extern "C" int sf_icp_accumulate(sf_ctx *ctx, sf_cloud *ref, const double *pts_d
     if (!nb) return SF_ERR_HIP;
     struct nb_guard { sf_ctx *c; sf_nbrs *n; ~nb_guard() { sf_nbrs_free(c, n); } } nbg{ctx, nb};
     if (mode == 1) SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, ref));
+    SF_HIP(hipMemsetAsync(dout, 0, 40 * sizeof(double), ctx->stream)); // [7], [18..39] (mode 0) and [36..39] (mode 1) belong to no pass
     // the k-NN lists are in PROCESSING order (queries sorted by cell): sums do not care, and qx / qy / qz follow it
     const dim3 grid(ICP_BLOCKS), block(256);
     SF_LAUNCH(ctx, "i1_icp_sums", (k_icp_sums<0, 0>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, ref->rec, m, d_max,

@@ -51,6 +51,20 @@ _POINT, _PLANE, _GICP = 0, 1, 2
 _TRIU = np.triu_indices(6)
 
 
+def _checked_rows(rows, n: int) -> np.ndarray:
+    """A row selection as the int64 array the device reads (it gathers pts[3 * rows[i]] unchecked): one-dimensional, every
+    id in 0 .. n-1, repeats allowed; an empty selection stays empty."""
+    ids = np.asarray(rows)
+    if ids.ndim != 1:
+        raise ValueError(f"rows: expected a one-dimensional selection, got shape {ids.shape}")
+    if ids.size and ids.dtype.kind not in "iu":
+        raise TypeError(f"rows: expected integer ids, got dtype {ids.dtype}")
+    bad = np.flatnonzero((ids < 0) | (ids >= n)) if ids.size else ids[:0]  # (compared in the caller's dtype: a uint64 id >= 2^63 is caught)
+    if bad.size:
+        raise IndexError(f"rows[{int(bad[0])}] = {int(ids[bad[0]])} is not a row of the {n} working points (0 .. {n - 1})")
+    return np.ascontiguousarray(ids, dtype=np.int64)
+
+
 class _PairSums:
     """What one device pass returns about the inlier pairs (p = moved working point, q = its nearest reference point)."""
 
@@ -135,7 +149,7 @@ class _Registration:
         """Inlier-pair sums of the working points (all of them, or the given `rows`) after `moved_by`."""
         m, sel = self.n, None
         if rows is not None:
-            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            rows = _checked_rows(rows, self.n)
             m = rows.shape[0]
             if self.rows is None or self.rows.shape[0] < m:
                 if self.rows is not None:
