@@ -576,6 +576,34 @@ int sf_transform_points(sf_ctx *ctx, double *pts_dev, int64_t n, const double *R
 int sf_icp_accumulate_gicp(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev /* n x 3, scan normals */,
                            const int64_t *sel_dev, int64_t m, const double *Rt, double d_max, double epsilon, double *sums /* 40 */);
 
+/* ---- robust losses for all three modes, K17 (no counterpart in the reference) --------
+ * The chain of the two calls above -- transform, k = 1 search, the d_max gate, pass A, pass B, one copy back, one wait -- with a
+ * weight w = psi(r) / r per kept pair (iteratively reweighted least squares).  mode 0 point to point, 1 point to plane (the
+ * reference cloud needs normals), 2 generalized (nrm_dev and epsilon as above; both are ignored in modes 0 and 1, nrm_dev may
+ * be NULL there).  The gate is applied first and is unchanged.  The pair's squared residual r2:
+ *   mode 0: |q - p|^2     mode 1: h^2, h = (q - p) . n     mode 2: r^T M r, clamped at 0
+ * and its weight from `loss` and `scale` = k (positive, finite; in the unit of sqrt(r2): a length in modes 0 and 1, a Mahalanobis
+ * distance in mode 2, where a residual h across both surfaces counts as h / sqrt(2 epsilon)), with s = r2 / (k k):
+ *   0 none           w = 1
+ *   1 Huber          w = 1 for sqrt(r2) <= k, else k / sqrt(r2)
+ *   2 Cauchy         w = 1 / (1 + s)
+ *   3 Geman-McClure  w = 1 / (1 + s)^2
+ *   4 Tukey          w = (1 - s)^2 for s <= 1, else 0
+ * sums[48] (host):
+ *   [0] pair count, [1..3] sum p, [4..6] sum q            unweighted, as above
+ *   [7] sum w
+ *   [8..36] the mode's layout above with every FIT term times w: mode 0 [8..16] sum w (p - pw)(q - qw)^T, centred with the
+ *           WEIGHTED centroids pw = sum w p / sum w, qw = sum w q / sum w (zero when sum w is 0); mode 1 [8..28] G^T W G,
+ *           [29..34] G^T W h; mode 2 [8..28] sum w J^T M J, [29..34] sum w J^T M r.  The residual sums stay unweighted:
+ *           [17] sum |p - q|^2 (mode 0), [35] sum |h| (mode 1) or sum r^T M r (mode 2), [36] sum |r|^2 (mode 2)
+ *   [40..42] sum w p, [43..45] sum w q, [46] sum w r2
+ *   the rest, [47] included, is zero, and so is everything when no pair is kept.
+ * With loss 0, or Huber with k above every residual, [0..39] are the numbers of sf_icp_accumulate / sf_icp_accumulate_gicp bit for
+ * bit, [7] = [0] and [40..45] = [1..6].  SF_ERR_ARG names the offending argument in sf_last_error(). */
+int sf_icp_accumulate_robust(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev /* NULL unless mode 2 */,
+                             const int64_t *sel_dev, int64_t m, const double *Rt, double d_max, int mode /* 0, 1, 2 */, double epsilon,
+                             int loss /* 0 .. 4 */, double scale, double *sums /* 48 */);
+
 /* ---- multi-GPU: RCCL over xGMI (no counterpart in the reference) --------------------------
  * One process per GPU.  Rank 0 calls sf_comm_unique_id, ships the 128 bytes to the other ranks by
  * any host channel, then every rank calls sf_comm_init.  sf_comm_allgather gathers

@@ -67,11 +67,22 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="--icp generalized: neighbours of a normal that the clouds do not bring along")
     p.add_argument("--gicp-epsilon", type=float, default=1e-3, metavar="EPS",
                    help="--icp generalized: a point's covariance along its normal, in (0, 1]")
+    p.add_argument("--icp-loss", default=None, choices=["none", "huber", "cauchy", "geman_mcclure", "tukey"],
+                   help="robust loss of the ICP stage: pairs within --icp-dmax are weighted by their residual (needs --icp-loss-scale)")
+    p.add_argument("--icp-loss-scale", type=float, default=None, metavar="K",
+                   help="--icp-loss: the loss's scale in the residual's unit, a few sigma of the noise")
+    p.add_argument("--icp-loss-scale-start", type=float, default=None, metavar="K0",
+                   help="--icp-loss: the scale of the first iteration, divided by 1.4 per iteration down to K (default: --icp-dmax)")
     p.add_argument("--icp-dmax", type=float, default=0.5), p.add_argument("--icp-voxel", type=float, default=0.2)
     p.add_argument("--icp-max-iter", type=int, default=50), p.add_argument("--icp-rms", type=float, default=1e-3)
     p.add_argument("--metric-threshold", type=float, default=0.1)
     p.add_argument("--write", default=None, help="basename for the aligned clouds (<name>_ransac.ply, <name>_icp.ply)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.icp_loss is not None and args.icp_loss_scale is None:
+        p.error("--icp-loss needs --icp-loss-scale")
+    if args.icp_loss is None and (args.icp_loss_scale is not None or args.icp_loss_scale_start is not None):
+        p.error("--icp-loss-scale and --icp-loss-scale-start need --icp-loss")
+    return args
 
 
 def main(argv=None) -> int:
@@ -107,7 +118,8 @@ def main(argv=None) -> int:
         transformation, rms, converged = pipe.run_icp(args.icp, transformation, d_max=args.icp_dmax, voxel_size=args.icp_voxel,
                                                        max_iter=args.icp_max_iter, rms_threshold=args.icp_rms,
                                                        disable_progress_bar=True, gicp_neighbors=args.gicp_neighbors,
-                                                       gicp_epsilon=args.gicp_epsilon)
+                                                       gicp_epsilon=args.gicp_epsilon, robust_loss=args.icp_loss,
+                                                       robust_scale=args.icp_loss_scale, robust_scale_start=args.icp_loss_scale_start)
         logging.info(f"ICP rms {rms:.3e}, converged: {bool(converged)}\n{transformation}")
         if args.write:
             outputs.append((f"{args.write}_icp.ply", transformation))

@@ -18,6 +18,11 @@
 // K16, generalized (plane-to-plane) ICP (Segal, Haehnel, Thrun, RSS 2009; no counterpart in the reference): the same chain
 // with a third pass B, k_gicp_sums, which weights every pair by M = (C_b + R C_a R^T)^-1, C = I - (1 - eps) n n^T from the
 // unit normal of either point, and leaves the 6x6 Gauss-Newton system of sum r^T M r for the host (sf_icp_accumulate_gicp).
+//
+// K17, robust losses for all three modes (no counterpart in the reference): the same chain with sibling sums kernels,
+// k_robust_sums, which give every kept pair a weight psi(r) / r of its residual (Huber, Cauchy, Geman-McClure, Tukey) and leave the
+// weighted sums for the host (sf_icp_accumulate_robust).  The kernels above it are untouched: the two older calls launch what
+// they launched before.
 #include "common.h"
 #include "device_util.h"
 
@@ -212,6 +217,172 @@ __global__ __launch_bounds__(64) void k_icp_final(const double *__restrict__ par
     }
 }
 
+// ---- K17: robust losses (sf_icp_accumulate_robust) -------------------------------------------------------------------------------
+// The weight psi(r) / r of a kept pair from its squared residual r2 and the scale k (kk = k * k), one rounding per operation,
+// which tests/icp_robust_numpy.py repeats operation by operation:
+//   0 none            1
+//   1 Huber           a = sqrt(r2);  a <= k ? 1 : k / a
+//   2 Cauchy          s = r2 / kk;   1 / (1 + s)
+//   3 Geman-McClure   c = 1 / (1 + s);  c c
+//   4 Tukey           s <= 1 ? (1 - s)(1 - s) : 0
+// `loss` is uniform over the launch: one kernel per (pass, mode), not one per loss.
+__device__ inline double robust_weight(int loss, double r2, double k, double kk)
+{
+    if (loss == 0) return 1.0;
+    if (loss == 1) {
+        const double a = sqrt(r2);
+        return a <= k ? 1.0 : k / a;
+    }
+    const double s = r2 / kk;
+    if (loss == 4) {
+        const double o = 1.0 - s;
+        return s <= 1.0 ? o * o : 0.0;
+    }
+    const double c = 1.0 / (1.0 + s);
+    return loss == 2 ? c : c * c;
+}
+
+// Both passes of the three modes with a weight w per kept pair.  The pair's terms are those of k_icp_sums / k_gicp_sums, formed by
+// the same operations in the same order; its squared residual r2 is d2 (MODE 0), h h (MODE 1) or the Mahalanobis term
+// (r0 u0 + r1 u1) + r2 u2 clamped at 0 (MODE 2), and both passes form w from it by the same operations, so they get the same bits.
+//   PASS 0 (15): 1, p, q as pass A of k_icp_sums, then w, w p (3), w q (3), w r2
+//   PASS 1: every fit term of the mode's pass B times w (one more rounding); the residual sums the host reports as rms stay
+//           unweighted: d2 (MODE 0: [9], MODE 2: [28]), |h| (MODE 1: [27]), the Mahalanobis term as formed (MODE 2: [27]).
+//           MODE 0 centres with `mean`, the WEIGHTED centroids k_robust_final leaves.
+// With w = 1 (loss none, or Huber with k above every residual) w * term is the term: the numbers of today's kernels, bit for bit.
+template <int PASS, int MODE>
+__global__ __launch_bounds__(256) void k_robust_sums(const double *__restrict__ qx, const double *__restrict__ qy,
+                                                     const double *__restrict__ qz, const int32_t *__restrict__ idx,
+                                                     const int32_t *__restrict__ qrow, const double *__restrict__ rec,
+                                                     const double *__restrict__ nrm, const int64_t *__restrict__ sel,
+                                                     const double *__restrict__ Rt, int64_t m, double d_max, double epsilon, int loss,
+                                                     double k, const double *__restrict__ mean /* 6, PASS 1 MODE 0 */,
+                                                     double *__restrict__ partial)
+{
+    constexpr int NV = PASS == 0 ? 15 : (MODE == 0 ? 10 : (MODE == 1 ? 28 : 29));
+    double acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+    const double kk = k * k;
+    double pm[3] = {0, 0, 0}, qm[3] = {0, 0, 0};
+    if (PASS == 1 && MODE == 0) {
+        pm[0] = mean[0]; pm[1] = mean[1]; pm[2] = mean[2];
+        qm[0] = mean[3]; qm[1] = mean[4]; qm[2] = mean[5];
+    }
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (MODE == 2 && Rt) {
+#pragma unroll
+        for (int v = 0; v < 9; ++v) R[v] = Rt[v];
+    }
+    const double c = 1.0 - epsilon;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const double px = qx[i], py = qy[i], pz = qz[i];
+        double x, y, z, nx = 0, ny = 0, nz = 0;
+        if (MODE == 0) sf_load_xyz(rec, idx[i], x, y, z);
+        else sf_load_pn(rec, idx[i], x, y, z, nx, ny, nz);
+        const double dx = x - px, dy = y - py, dz = z - pz;
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        if (!(sqrt(d2) <= d_max)) continue; // the gate of k_icp_sums, applied first
+        double r2 = d2, h = 0.0, maha = 0.0, M[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, u[3] = {0, 0, 0};
+        if (MODE == 1) {
+            h = (dx * nx + dy * ny) + dz * nz;
+            r2 = h * h;
+        }
+        if (MODE == 2) { // M and u as k_gicp_sums forms them
+            const int64_t row = qrow ? (int64_t)qrow[i] : i;
+            const int64_t j = sel ? sel[row] : row;
+            const double ax = nrm[3 * j], ay = nrm[3 * j + 1], az = nrm[3 * j + 2];
+            double m0 = ax, m1 = ay, m2 = az;
+            if (Rt) {
+                m0 = (ax * R[0] + ay * R[1]) + az * R[2];
+                m1 = (ax * R[3] + ay * R[4]) + az * R[5];
+                m2 = (ax * R[6] + ay * R[7]) + az * R[8];
+            }
+            const double s00 = 2.0 - c * (nx * nx + m0 * m0), s11 = 2.0 - c * (ny * ny + m1 * m1), s22 = 2.0 - c * (nz * nz + m2 * m2);
+            const double s01 = -(c * (nx * ny + m0 * m1)), s02 = -(c * (nx * nz + m0 * m2)), s12 = -(c * (ny * nz + m1 * m2));
+            const double a00 = s11 * s22 - s12 * s12, a01 = s02 * s12 - s01 * s22, a02 = s01 * s12 - s02 * s11;
+            const double a11 = s00 * s22 - s02 * s02, a12 = s01 * s02 - s00 * s12, a22 = s00 * s11 - s01 * s01;
+            const double det = (s00 * a00 + s01 * a01) + s02 * a02;
+            const double inv = 1.0 / det;
+            M[0][0] = a00 * inv; M[0][1] = M[1][0] = a01 * inv; M[0][2] = M[2][0] = a02 * inv;
+            M[1][1] = a11 * inv; M[1][2] = M[2][1] = a12 * inv; M[2][2] = a22 * inv;
+#pragma unroll
+            for (int b = 0; b < 3; ++b) u[b] = (M[b][0] * dx + M[b][1] * dy) + M[b][2] * dz;
+            maha = (dx * u[0] + dy * u[1]) + dz * u[2];
+            r2 = maha < 0.0 ? 0.0 : maha;
+        }
+        const double w = robust_weight(loss, r2, k, kk);
+        if constexpr (PASS == 0) {
+            acc[0] += 1.0;
+            acc[1] += px; acc[2] += py; acc[3] += pz;
+            acc[4] += x; acc[5] += y; acc[6] += z;
+            acc[7] += w;
+            acc[8] += w * px; acc[9] += w * py; acc[10] += w * pz;
+            acc[11] += w * x; acc[12] += w * y; acc[13] += w * z;
+            acc[14] += w * r2;
+        } else if constexpr (MODE == 0) {
+            const double ax = px - pm[0], ay = py - pm[1], az = pz - pm[2];
+            const double bx = x - qm[0], by = y - qm[1], bz = z - qm[2];
+            acc[0] += w * (ax * bx); acc[1] += w * (ax * by); acc[2] += w * (ax * bz);
+            acc[3] += w * (ay * bx); acc[4] += w * (ay * by); acc[5] += w * (ay * bz);
+            acc[6] += w * (az * bx); acc[7] += w * (az * by); acc[8] += w * (az * bz);
+            acc[9] += d2;
+        } else if constexpr (MODE == 1) {
+            const double g[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+            int t = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) acc[t++] += w * (g[a] * g[b]);
+#pragma unroll
+            for (int a = 0; a < 6; ++a) acc[21 + a] += w * (g[a] * h);
+            acc[27] += fabs(h);
+        } else {
+            double Q[3][3];
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                Q[0][b] = py * M[2][b] - pz * M[1][b];
+                Q[1][b] = pz * M[0][b] - px * M[2][b];
+                Q[2][b] = px * M[1][b] - py * M[0][b];
+            }
+            acc[0] += w * (py * Q[0][2] - pz * Q[0][1]);  // H row 0: T00 T01 T02 Q00 Q01 Q02
+            acc[1] += w * (pz * Q[0][0] - px * Q[0][2]);
+            acc[2] += w * (px * Q[0][1] - py * Q[0][0]);
+            acc[3] += w * Q[0][0]; acc[4] += w * Q[0][1]; acc[5] += w * Q[0][2];
+            acc[6] += w * (pz * Q[1][0] - px * Q[1][2]);  // row 1: T11 T12 Q10 Q11 Q12
+            acc[7] += w * (px * Q[1][1] - py * Q[1][0]);
+            acc[8] += w * Q[1][0]; acc[9] += w * Q[1][1]; acc[10] += w * Q[1][2];
+            acc[11] += w * (px * Q[2][1] - py * Q[2][0]); // row 2: T22 Q20 Q21 Q22
+            acc[12] += w * Q[2][0]; acc[13] += w * Q[2][1]; acc[14] += w * Q[2][2];
+            acc[15] += w * M[0][0]; acc[16] += w * M[0][1]; acc[17] += w * M[0][2]; // rows 3 .. 5: M
+            acc[18] += w * M[1][1]; acc[19] += w * M[1][2];
+            acc[20] += w * M[2][2];
+            acc[21] += w * (py * u[2] - pz * u[1]);       // g = [p x u; u]
+            acc[22] += w * (pz * u[0] - px * u[2]);
+            acc[23] += w * (px * u[1] - py * u[0]);
+            acc[24] += w * u[0]; acc[25] += w * u[1]; acc[26] += w * u[2];
+            acc[27] += maha;
+            acc[28] += d2;
+        }
+    }
+    block_fold<NV>(acc, partial + (size_t)blockIdx.x * ICP_NV);
+}
+
+// fold PASS 0's block partials in block order into sums[48]: [0..7] as they are, w p, w q, w r2 to [40..46]; and leave the
+// weighted centroids sum w p / sum w, sum w q / sum w (zero when sum w is not positive) for PASS 1 of MODE 0
+__global__ __launch_bounds__(64) void k_robust_final(const double *__restrict__ partial, int nblocks, double *__restrict__ out,
+                                                     double *__restrict__ mean)
+{
+    const int v = threadIdx.x;
+    double a = 0.0;
+    if (v < 15)
+        for (int b = 0; b < nblocks; ++b) a += partial[(size_t)b * ICP_NV + v];
+    if (v < 8) out[v] = a;
+    else if (v < 15) out[32 + v] = a;
+    const double sw = __shfl(a, 7);
+    if (v >= 8 && v <= 13) mean[v - 8] = sw > 0.0 ? a / sw : 0.0;
+}
+
 } // namespace
 
 extern "C" int sf_transform_points(sf_ctx *ctx, double *pts_dev, int64_t n, const double *Rt)
@@ -309,6 +480,65 @@ extern "C" int sf_icp_accumulate_gicp(sf_ctx *ctx, sf_cloud *ref, const double *
               nrm_dev, sel_dev, (const double *)dRt, m, d_max, epsilon, partial);
     SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, 29, dout + 8, (double *)nullptr);
     SF_HIP(hipMemcpyAsync(sums, dout, 40 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    return SF_OK;
+}
+
+// K17: the chain of the two calls above with a robust weight per kept pair (sums[48], layout in include/shotfpfh.h)
+extern "C" int sf_icp_accumulate_robust(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev, const int64_t *sel_dev,
+                                        int64_t m, const double *Rt, double d_max, int mode, double epsilon, int loss, double scale,
+                                        double *sums)
+{
+    const char *bad = nullptr;
+    if (!ctx) bad = "ctx";
+    else if (!ref) bad = "ref";
+    else if (!pts_dev) bad = "pts_dev";
+    else if (!sums) bad = "sums";
+    else if (m < 0) bad = "m (negative)";
+    else if (mode < 0 || mode > 2) bad = "mode (0 point to point, 1 point to plane, 2 generalized)";
+    else if (mode == 2 && !nrm_dev) bad = "nrm_dev (mode 2 needs the scan's normals)";
+    else if (mode == 2 && !(epsilon > 0.0 && epsilon <= 1.0)) bad = "epsilon (must lie in (0, 1])";
+    else if (loss < 0 || loss > 4) bad = "loss (0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey)";
+    else if (!(scale > 0.0 && scale < INFINITY)) bad = "scale (must be positive and finite)";
+    if (bad) { sf_set_error("sf_icp_accumulate_robust: bad argument %s", bad); return SF_ERR_ARG; }
+    SF_HIP(hipSetDevice(ctx->device));
+    for (int i = 0; i < 48; ++i) sums[i] = 0.0;
+    if (!m) return SF_OK;
+    if (ref->n < 1) { sf_set_error("sf_icp_accumulate_robust: empty reference cloud"); return SF_ERR_ARG; }
+    sf_pool_guard tmp(ctx);
+    double *dRt = nullptr, *moved = nullptr, *partial = nullptr, *dout = nullptr, *dmean = nullptr;
+    if (Rt) {
+        SF_CHECK(tmp.alloc(&dRt, 12));
+        SF_HIP(hipMemcpyAsync(dRt, Rt, 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    SF_CHECK(tmp.alloc(&moved, (size_t)m * 3));
+    SF_CHECK(tmp.alloc(&partial, (size_t)ICP_BLOCKS * ICP_NV));
+    SF_CHECK(tmp.alloc(&dout, 80));
+    SF_CHECK(tmp.alloc(&dmean, 8));
+    SF_LAUNCH(ctx, "i0_transform", k_transform, dim3((unsigned)sf_div_up(m, 256)), dim3(256), pts_dev, sel_dev, m,
+              (const double *)dRt, moved);
+    sf_nbrs *nb = sf_knn_search(ctx, ref, moved, m, 1, SF_IN_DEVICE);
+    if (!nb) return SF_ERR_HIP;
+    struct nb_guard { sf_ctx *c; sf_nbrs *n; ~nb_guard() { sf_nbrs_free(c, n); } } nbg{ctx, nb};
+    if (mode != 0) SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, ref)); // both passes read them: the weight comes from h or from M
+    SF_HIP(hipMemsetAsync(dout, 0, 48 * sizeof(double), ctx->stream)); // the slots of no pass, [47] among them
+    const dim3 grid(ICP_BLOCKS), block(256);
+    const int32_t *qrow = (const int32_t *)nb->qrow;
+    const double *no_mean = nullptr;
+#define SF_ROBUST_PASS(PASS, MODE, mean)                                                                                              \
+    SF_LAUNCH(ctx, "i3_robust_sums", (k_robust_sums<PASS, MODE>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, qrow, ref->rec, nrm_dev, \
+              sel_dev, (const double *)dRt, m, d_max, epsilon, loss, scale, mean, partial)
+    if (mode == 0) { SF_ROBUST_PASS(0, 0, no_mean); }
+    else if (mode == 1) { SF_ROBUST_PASS(0, 1, no_mean); }
+    else { SF_ROBUST_PASS(0, 2, no_mean); }
+    SF_LAUNCH(ctx, "i3_robust_final", k_robust_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, dout, dmean);
+    if (mode == 0) { SF_ROBUST_PASS(1, 0, (const double *)dmean); }
+    else if (mode == 1) { SF_ROBUST_PASS(1, 1, no_mean); }
+    else { SF_ROBUST_PASS(1, 2, no_mean); }
+#undef SF_ROBUST_PASS
+    SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, mode == 0 ? 10 : (mode == 1 ? 28 : 29),
+              dout + 8, (double *)nullptr);
+    SF_HIP(hipMemcpyAsync(sums, dout, 48 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
     return SF_OK;
 }

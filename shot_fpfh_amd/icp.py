@@ -16,6 +16,11 @@ feed it, which fit they ask for and what they return.
 M = (C_b + R C_a R^T)^-1, and the device call (`sf_icp_accumulate_gicp`, the same chain with a third sums pass) returns the
 6x6 Gauss-Newton system of sum r^T M r; the host solves it and applies the exact exponential of the step (`_gicp_fit`).
 
+`icp_robust` (K17) runs any of the three with a robust loss: the device call (`sf_icp_accumulate_robust`) weights every pair inside
+`d_max` by psi(r) / r of its residual (Huber, Cauchy, Geman-McClure, Tukey) and returns the weighted sums; the host solves the
+same small systems and anneals the loss's scale from `scale_start` down to `scale`, the graduated scheme of
+`fast_global_registration`.  From a coarse start a fixed small scale is no better than no loss at all, so the annealing is part of it.
+
 Deviation, on purpose: the reference's `icp_point_to_point` computes its RMS from `ref[neighbors]` (all queried points,
 shape (n, 1, 3)) instead of `ref[inliers_neighbors]` (icp.py:122-124); the broadcast yields an array, and formatting it for
 the progress bar raises TypeError on the first iteration, so that function cannot run there at all.  Here the RMS is taken
@@ -43,12 +48,15 @@ __all__ = [
     "icp_point_to_point",
     "icp_point_to_plane",
     "icp_generalized",
+    "icp_robust",
     "compute_point_to_point_error",
     "nearest_within",
 ]
 
 _POINT, _PLANE, _GICP = 0, 1, 2
 _TRIU = np.triu_indices(6)
+_MODES = {"point_to_point": _POINT, "point_to_plane": _PLANE, "generalized": _GICP}
+LOSSES = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3, "tukey": 4}  # the `loss` of sf_icp_accumulate_robust
 
 
 def _checked_rows(rows, n: int) -> np.ndarray:
@@ -66,10 +74,15 @@ def _checked_rows(rows, n: int) -> np.ndarray:
 
 
 class _PairSums:
-    """What one device pass returns about the inlier pairs (p = moved working point, q = its nearest reference point)."""
+    """What one device pass returns about the inlier pairs (p = moved working point, q = its nearest reference point).  The 48
+    numbers of a pass with a robust loss have every fit term weighted, and the weight's own sums behind them."""
 
     def __init__(self, raw: np.ndarray, mode: int):
         self.raw = raw
+        if raw.shape[0] == 48:
+            self.sum_w = float(raw[7])                # sum w
+            self.sum_wp, self.sum_wq = raw[40:43], raw[43:46]
+            self.sum_wr2 = float(raw[46])             # sum w r2 (r2: the mode's squared residual)
         self.count = int(raw[0])
         self.sum_p, self.sum_q = raw[1:4], raw[4:7]
         if mode == _POINT:
@@ -90,6 +103,12 @@ class _PairSums:
         if self.count == 0:
             raise np.linalg.LinAlgError("ICP: no scan point has a reference point within d_max")
 
+    def require_weight(self, scale: float) -> None:
+        self.require_pairs()
+        if not self.sum_w > 0.0:
+            raise np.linalg.LinAlgError(f"ICP: all {self.count} pairs within d_max have weight zero at the loss's scale {scale!r}: "
+                                        "every residual lies beyond it")
+
 
 def _rigid_fit(s: _PairSums) -> RigidTransform:
     """Kabsch from the centred cross-covariance (core/solvers.py:9-30: same SVD, same reflection rule)."""
@@ -97,10 +116,15 @@ def _rigid_fit(s: _PairSums) -> RigidTransform:
     return kabsch_from_covariance(s.cross_cov, s.sum_p / s.count, s.sum_q / s.count)
 
 
+def _weighted_rigid_fit(s: _PairSums) -> RigidTransform:
+    """Kabsch on the weighted cross-covariance and the weighted centroids the device centred it with."""
+    return kabsch_from_covariance(s.cross_cov, s.sum_wp / s.sum_w, s.sum_wq / s.sum_w)
+
+
 def _plane_fit(s: _PairSums) -> RigidTransform:
     """Linearised point-to-plane step from G^T G and G^T h (core/solvers.py:33-48)."""
     s.require_pairs()
-    sol = np.linalg.solve(s.gtg, s.gth)
+    s.step = sol = np.linalg.solve(s.gtg, s.gth)
     return RigidTransform(Rotation.from_euler("xyz", sol[:3]).as_matrix(), sol[3:6])
 
 
@@ -145,8 +169,9 @@ class _Registration:
             self.normals = self.engine.empty((max(self.n, 1), 3)).from_host(nrm if self.n else np.zeros((1, 3)))
 
     def pairs(self, mode: int, d_max: float, moved_by: Optional[RigidTransform] = None, rows=None,
-              epsilon: float = 1e-3) -> _PairSums:
-        """Inlier-pair sums of the working points (all of them, or the given `rows`) after `moved_by`."""
+              epsilon: float = 1e-3, loss: Optional[int] = None, scale: float = 1.0) -> _PairSums:
+        """Inlier-pair sums of the working points (all of them, or the given `rows`) after `moved_by`; with a `loss` (0 .. 4,
+        `LOSSES`) the 48 weighted sums of sf_icp_accumulate_robust at `scale`."""
         m, sel = self.n, None
         if rows is not None:
             rows = _checked_rows(rows, self.n)
@@ -159,6 +184,18 @@ class _Registration:
                 _ffi.check(self.engine.lib.sf_h2d(self.engine.h, self.rows.ptr, rows.ctypes.data_as(C.c_void_p), m * 8), "sf_h2d")
             sel = self.rows.ptr
         rt = None if moved_by is None else np.ascontiguousarray(moved_by.as_row12())
+        if loss is not None:
+            if mode == _GICP and self.normals is None:
+                raise ValueError("generalized ICP needs the normals of the working points")
+            raw = np.zeros(48)
+            _ffi.check(
+                self.engine.lib.sf_icp_accumulate_robust(self.engine.h, self.ref.h, self.points.ptr,
+                                                         self.normals.ptr if mode == _GICP else None, sel, m,
+                                                         None if rt is None else rt.ctypes.data_as(C.c_void_p), float(d_max), int(mode),
+                                                         float(epsilon), int(loss), float(scale), raw.ctypes.data_as(C.c_void_p)),
+                "sf_icp_accumulate_robust",
+            )
+            return _PairSums(raw, mode)
         raw = np.zeros(40)
         if mode == _GICP:
             if self.normals is None:
@@ -303,6 +340,18 @@ def _unit_rows(normals, n: int, what: str) -> np.ndarray:
     return np.ascontiguousarray(nrm / np.where(length > 0.0, length, 1.0)[:, None])
 
 
+def _both_normals(scan, ref, scan_normals, ref_normals, k_normals: int):
+    """Unit normals of both clouds for generalized ICP: the given ones scaled to unit length, the others from `k_normals`
+    neighbours of the full cloud."""
+    given = [None if nrm is None else _unit_rows(nrm, a.shape[0], f"{name} normals")
+             for name, a, nrm in (("scan", scan, scan_normals), ("ref", ref, ref_normals))]
+    for name, a, nrm in (("scan", scan, given[0]), ("ref", ref, given[1])):
+        if nrm is None and not 3 <= int(k_normals) <= a.shape[0]:
+            raise ValueError(f"k_normals={k_normals} must be between 3 and the number of {name} points ({a.shape[0]})")
+    return tuple(nrm if nrm is not None else _unit_rows(compute_normals(a, a, k=int(k_normals)), a.shape[0], "normals")
+                 for a, nrm in ((scan, given[0]), (ref, given[1])))
+
+
 def icp_generalized(
     scan: npt.NDArray[np.float64],
     ref: npt.NDArray[np.float64],
@@ -331,17 +380,115 @@ def icp_generalized(
         raise ValueError(f"epsilon={epsilon} must lie in (0, 1]")
     if not step_tolerance >= 0.0:
         raise ValueError(f"step_tolerance={step_tolerance} must not be negative")
-    given = [None if nrm is None else _unit_rows(nrm, a.shape[0], f"{name} normals")
-             for name, a, nrm in (("scan", scan, scan_normals), ("ref", ref, ref_normals))]
-    for name, a, nrm in (("scan", scan, given[0]), ("ref", ref, given[1])):
-        if nrm is None and not 3 <= int(k_normals) <= a.shape[0]:
-            raise ValueError(f"k_normals={k_normals} must be between 3 and the number of {name} points ({a.shape[0]})")
-    scan_normals, ref_normals = (nrm if nrm is not None else _unit_rows(compute_normals(a, a, k=int(k_normals)), a.shape[0], "normals")
-                                 for a, nrm in ((scan, given[0]), (ref, given[1])))
+    scan_normals, ref_normals = _both_normals(scan, ref, scan_normals, ref_normals, k_normals)
     keep = grid_subsampling(scan, voxel_size)
     reg = _Registration(scan[keep], ref, ref_normals, scan_normals=scan_normals[keep])
     try:
         return _refine(reg, transformation_init, _GICP, d_max, max_iter, rms_threshold, epsilon, step_tolerance)
+    finally:
+        reg.close()
+
+
+def annealed_scale(scale: float, scale_start: float, division_factor: float, iteration: int) -> float:
+    """The loss's scale of iteration i: max(scale, scale_start / division_factor**i)."""
+    try:
+        return max(scale, scale_start / division_factor**iteration)
+    except OverflowError:  # division_factor**i beyond the doubles: the quotient is long below any scale
+        return scale
+
+
+def _refine_robust(reg: _Registration, start: RigidTransform, mode: int, d_max: float, loss: int, scale: float, scale_start: float,
+                   division_factor: float, max_iter: int, rms_threshold: float, epsilon: float, step_tolerance: float):
+    """The loop of `_refine` with a weight per pair: the scale of iteration i is `annealed_scale(.., i)`, the residual reported is
+    the mode's unweighted one, and a small step stops the run only once the scale has come down to `scale`."""
+    total, rms, small_step = start, 0.0, False
+    fit = {_POINT: _weighted_rigid_fit, _PLANE: _plane_fit, _GICP: _gicp_fit}[mode]
+    try:
+        for i in range(max_iter):
+            k = annealed_scale(scale, scale_start, division_factor, i)
+            found = reg.pairs(mode, d_max, moved_by=total, epsilon=epsilon, loss=loss, scale=k)
+            found.require_weight(k)
+            step = fit(found)
+            total = step @ total
+            if mode == _POINT:
+                rms = float(np.sqrt(found.sq_dist))
+                size = max(float(np.abs(step.rotation - np.eye(3)).max()), float(np.abs(step.translation).max()))
+            else:
+                rms = found.abs_h / found.count if mode == _PLANE else float(np.sqrt(found.sq_dist / found.count))
+                size = float(np.abs(found.step).max())
+            small_step = k == scale and size < step_tolerance
+            if rms < rms_threshold:
+                logging.info("RMS threshold reached.")
+                break
+            if small_step:
+                logging.info("Step tolerance reached.")
+                break
+    except KeyboardInterrupt:
+        logging.info("ICP interrupted by user.")
+    return total, rms, rms < rms_threshold or small_step
+
+
+def icp_robust(
+    scan: npt.NDArray[np.float64],
+    ref: npt.NDArray[np.float64],
+    transformation_init: RigidTransform,
+    d_max: float,
+    *,
+    mode: str = "point_to_plane",
+    loss: str = "cauchy",
+    scale: float,
+    scale_start: Optional[float] = None,
+    division_factor: float = 1.4,
+    ref_normals: Optional[npt.NDArray[np.float64]] = None,
+    scan_normals: Optional[npt.NDArray[np.float64]] = None,
+    k_normals: int = 20,
+    epsilon: float = 1e-3,
+    voxel_size: float = 0.2,
+    max_iter: int = 50,
+    rms_threshold: float = 1e-2,
+    step_tolerance: float = 1e-9,
+) -> tuple[RigidTransform, float, bool]:
+    """Point-to-point, point-to-plane or generalized ICP with a robust loss, K17: every pair within `d_max` is weighted by
+    psi(r) / r of its residual r -- the distance, the distance along the reference normal, or the Mahalanobis distance
+    sqrt(r^T M r) of generalized ICP -- so that what the scan sees and the reference does not (clutter, another object, the part
+    without overlap) stops pulling the fit.  `loss`: "none", "huber", "cauchy", "geman_mcclure", "tukey".  `scale` is the loss's
+    k in the residual's unit (a few sigma of the noise); iteration i uses max(scale, scale_start / division_factor**i), with
+    `scale_start` = `d_max` unless given, and `scale_start=scale` switches the annealing off.
+    "point_to_plane" needs `ref_normals`; "generalized" treats normals as `icp_generalized` does.
+    Returns (transform, rms, converged) with the mode's own UNWEIGHTED rms (see its function), so that runs with and without a
+    loss compare; converged means rms < rms_threshold, or, once the scale has reached `scale`, a step below `step_tolerance`:
+    max|xi| of the 6-vector step, max(|dR - I|, |dt|) for point-to-point.  When every pair has weight zero (Tukey with all
+    residuals beyond the scale) numpy.linalg.LinAlgError names the scale."""
+    if mode not in _MODES:
+        raise ValueError(f"mode={mode!r}: expected one of {sorted(_MODES)}")
+    if loss not in LOSSES:
+        raise ValueError(f"loss={loss!r}: expected one of {sorted(LOSSES)}")
+    if scale is None or not 0.0 < float(scale) < math.inf:
+        raise ValueError(f"scale={scale!r} must be positive and finite")
+    scale_start = d_max if scale_start is None else scale_start
+    if not 0.0 < float(scale_start) < math.inf:
+        raise ValueError(f"scale_start={scale_start!r} must be positive and finite (it defaults to d_max)")
+    if not 1.0 < float(division_factor) < math.inf:
+        raise ValueError(f"division_factor={division_factor!r} must be greater than 1 (scale_start=scale switches the annealing off)")
+    if not 0.0 < epsilon <= 1.0:
+        raise ValueError(f"epsilon={epsilon} must lie in (0, 1]")
+    if not step_tolerance >= 0.0:
+        raise ValueError(f"step_tolerance={step_tolerance} must not be negative")
+    scan, ref = np.asarray(scan, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    for name, a in (("scan", scan), ("ref", ref)):
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name}: expected an (N, 3) array, got shape {a.shape}")
+    kind = _MODES[mode]
+    if kind == _PLANE and ref_normals is None:
+        raise ValueError("mode='point_to_plane' needs ref_normals")
+    if kind == _GICP:
+        scan_normals, ref_normals = _both_normals(scan, ref, scan_normals, ref_normals, k_normals)
+    keep = grid_subsampling(scan, voxel_size)
+    reg = _Registration(scan[keep], ref, ref_normals if kind != _POINT else None,
+                        scan_normals=scan_normals[keep] if kind == _GICP else None)
+    try:
+        return _refine_robust(reg, transformation_init, kind, d_max, LOSSES[loss], float(scale), float(scale_start),
+                              float(division_factor), max_iter, rms_threshold, epsilon, step_tolerance)
     finally:
         reg.close()
 
