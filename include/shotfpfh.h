@@ -316,6 +316,17 @@ int sf_spfh_export(sf_ctx *ctx, sf_cloud *cloud, sf_spfh *spfh, double *out /* n
 void sf_spfh_free(sf_ctx *ctx, sf_spfh *spfh);
 int sf_fpfh(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *self_nbrs, sf_spfh *spfh, const int64_t *kp_idx, int64_t m,
             double *out /* m x nb^3 */, int flags);
+/* The frame moments of sf_spfh_compute_moments from K7's weight pass instead of K6's sweep (K6 has no issue slot nor
+ * register to spare, K7 has both): sf_fpfh_moments is sf_fpfh over every query of `self_nbrs` (no kp_idx) that also leaves
+ * the 6 doubles per query in cov_dev -- bit for bit what sf_spfh_compute_moments leaves there -- so that the table can be
+ * computed by the plain sf_spfh_compute.  Only some forms of K7 carry the moments (the byte table with at most two live
+ * 16-bin blocks, no list longer than 192 points): sf_fpfh_carries_moments says, from what the host knows and without a
+ * launch, whether a call on these lists and this table would (1) or not (0); asked BEFORE sf_spfh_compute it still holds
+ * after it unless the data of that pass widens the table's block mask.  sf_fpfh_moments returns SF_ERR_UNSUPPORTED, having
+ * launched nothing, when the form does not carry them: the caller then runs sf_spfh_compute_moments and sf_fpfh. */
+int sf_fpfh_carries_moments(sf_ctx *ctx, sf_nbrs *self_nbrs, sf_spfh *spfh);
+int sf_fpfh_moments(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *self_nbrs, sf_spfh *spfh, int64_t m, double *out /* m x nb^3 */,
+                    double *cov_dev /* m x 6 */, int flags);
 
 /* ---- matching: cdist + argmin (matching.py:47-52, 63-65, 164-168), K8 ---------------------
  * a: m1 x d, b: m2 x d.  idx[i] = first j minimising sqrt(sum_t (a[i,t]-b[j,t])^2), summed left to

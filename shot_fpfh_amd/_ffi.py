@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libshotfpfh.so")
 SF_HOST, SF_OUT_DEVICE, SF_IN_DEVICE = 0, 1, 2
 SHOT_LEN = 352
 MAX_COSINE_BINS = 64  # SF_SHOT_MAX_COSINE_BINS: sf_shot_serial_bins takes 1 .. 64 cosine bins (rows of 32 n)
+SF_ERR_UNSUPPORTED = -6  # e.g. sf_fpfh_moments: K7's form for this table does not carry the frame moments
 SF_ERR_BIN_RANGE = -7  # sf_shot_serial_bins: a neighbour in cosine bin n (the reference's IndexError)
 MAX_FPFH_BINS = 1290  # SF_MAX_FPFH_BINS: n_bins^3 fits an int (n_bins above 8 take the generic kernels; memory is the real bound)
 
@@ -97,6 +98,8 @@ SIGNATURES = {
     "sf_spfh_export": (_int, [_vp, _vp, _vp, _vp, _int]),
     "sf_spfh_free": (None, [_vp, _vp]),
     "sf_fpfh": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _int]),
+    "sf_fpfh_carries_moments": (_int, [_vp, _vp, _vp]),
+    "sf_fpfh_moments": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _int]),
     "sf_match_argmin": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _int]),
     "sf_match_top2": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _int]),
     "sf_rows_nonzero": (_int, [_vp, _vp, _i64, _i64, _vp]),

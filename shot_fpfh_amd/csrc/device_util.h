@@ -89,6 +89,22 @@ __device__ inline double sf_wave_max_nonneg(double v)
                             __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 
+// gfx950's lane-swap instructions: v_permlane32_swap(a, b) leaves a = {a[0..31], b[0..31]}, b = {a[32..63], b[32..63]} -- both
+// halves of the wave then hold "mine and the partner's" of an exchange with lane ^ 32 in one instruction per 32-bit half, where
+// a shuffle through the LDS crossbar is two ds_bpermute plus the selects that pick what to keep and what to send.
+// v_permlane16_swap does the same between the 16-lane rows 0/1 and 2/3 (tools/ubench/permlane_swap.hip).
+typedef unsigned sf_u2 __attribute__((ext_vector_type(2)));
+template <int W>
+__device__ __forceinline__ void sf_lane_swap(double &a, double &b)
+{
+    const unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
+    const unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
+    const sf_u2 lo = W == 32 ? __builtin_amdgcn_permlane32_swap(alo, blo, false, false) : __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
+    const sf_u2 hi = W == 32 ? __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false) : __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+
 // Eight sums over the 64 lanes at once, by a transposing butterfly: after the exchanges with lane ^ 32, ^ 16 and ^ 8 a
 // lane keeps ONE of the eight partial sums, v[4 b5 + 2 b4 + b3] (b = bits of the lane number), which three DPP steps
 // then complete over the eight lanes that share those bits.  Returns that total: lane 8 i (and its seven neighbours)
@@ -96,17 +112,21 @@ __device__ inline double sf_wave_max_nonneg(double v)
 __device__ inline double sf_wave_sum8(const double (&v)[8])
 {
     const int lane = sf_lane();
-    const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
+    const bool b3 = lane & 8;
     double k4[4], k2[2];
+    // (after a swap the lower half / the even rows hold {mine, the partner's} of the first operand and the others of the second:
+    // a + b pairs the same two numbers as "mine + what lane ^ 32 sent" did -- the same sum, bit for bit)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const double mine = b5 ? v[4 + i] : v[i], send = b5 ? v[i] : v[4 + i];
-        k4[i] = mine + __shfl_xor(send, 32);
+        double a = v[i], b = v[4 + i];
+        sf_lane_swap<32>(a, b);
+        k4[i] = a + b;
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const double mine = b4 ? k4[2 + i] : k4[i], send = b4 ? k4[i] : k4[2 + i];
-        k2[i] = mine + __shfl_xor(send, 16);
+        double a = k4[i], b = k4[2 + i];
+        sf_lane_swap<16>(a, b);
+        k2[i] = a + b;
     }
     double r;
     {
@@ -133,16 +153,16 @@ __device__ inline double sf_wave_sum8(const double (&v)[8])
 // instructions of two sf_wave_sum calls, a third of three.
 __device__ inline double sf_wave_sum4(const double (&v)[4])
 {
-    const int lane = sf_lane();
-    const bool b5 = lane & 32, b4 = lane & 16;
     double k2[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const double mine = b5 ? v[2 + i] : v[i], send = b5 ? v[i] : v[2 + i];
-        k2[i] = mine + __shfl_xor(send, 32);
+    for (int i = 0; i < 2; ++i) { // (lane swaps: see sf_wave_sum8)
+        double a = v[i], b = v[2 + i];
+        sf_lane_swap<32>(a, b);
+        k2[i] = a + b;
     }
-    const double mine = b4 ? k2[1] : k2[0], send = b4 ? k2[0] : k2[1];
-    double r = mine + __shfl_xor(send, 16);
+    double r0 = k2[0], r1 = k2[1];
+    sf_lane_swap<16>(r0, r1);
+    double r = r0 + r1;
 #define SF_DPP_ADD(ctrl)                                                                                  \
     {                                                                                                     \
         const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(r), ctrl, 0xf, 0xf, false);          \

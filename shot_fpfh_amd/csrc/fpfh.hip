@@ -258,14 +258,17 @@ __global__ __launch_bounds__(64 * SF_MC_WPB) __attribute__((amdgpu_waves_per_eu(
 // K7 when at most two of the table's eight 16-bin blocks hold anything at all (K6's OR over every row): the reference's
 // un-normalised v keeps alpha in ONE of its bins whenever the radius is well below that bin's width, so 100 of the 125
 // bins are structurally empty -- only those blocks are streamed and multiplied (fpfh_mc_body_sparse)
-template <int NKS, bool HI>
+// MOM: the weight pass also leaves the moments of the SHOT frames in `cov` (fpfh_mc_weights) -- instantiated for at most three
+// chunks: 64 registers at three, still eight waves; the four-chunk instantiation would spill into its sweep.
+template <int NKS, bool HI, bool MOM = false>
 __global__ __launch_bounds__(64 * SF_MC_WPB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fpfh_mc_sparse(
     const double *__restrict__ rec, const int64_t *__restrict__ offset, const int32_t *__restrict__ cnt,
     const int32_t *__restrict__ idx, int64_t nbrs_begin, const int32_t *__restrict__ kp_pos, int64_t m, sf_bin_window W,
     const uint8_t *__restrict__ counts, unsigned table_bytes, const double *__restrict__ p4, const unsigned *__restrict__ live,
     const uint8_t *__restrict__ packed, unsigned packed_bytes, double *__restrict__ out, const uint8_t *__restrict__ hi, int limit,
-    const int32_t *__restrict__ sel, int64_t nsel, int64_t view_first)
+    const int32_t *__restrict__ sel, int64_t nsel, int64_t view_first, double mom_radius, double *__restrict__ cov)
 {
+    static_assert(!MOM || NKS <= 3, "the moments ride on the forms of at most three chunks");
     __shared__ __attribute__((aligned(16))) unsigned rowbuf_all[SF_MC_WPB][32 * 32]; // four steps of 32 rows x 32 B
     __shared__ __attribute__((aligned(16))) unsigned char abuf_all[SF_MC_WPB][9 * 64];
     const int wv_id = threadIdx.x >> 6;
@@ -287,11 +290,11 @@ __global__ __launch_bounds__(64 * SF_MC_WPB) __attribute__((amdgpu_waves_per_eu(
     // ... from the packed copy (32 bytes per row: four rows per cache line) when every row of it was written under this
     // very mask, else from the table itself
     if (sf_uniform(live[1]) == mask) {
-        fpfh_mc_body_sparse<NKS, true, HI>(rec, offset, cnt, idx, nbrs_begin, kp_pos, W, counts, packed, packed_bytes, p4, out, q,
-                                           b0, b1, rowbuf_all[wv_id], abuf_all[wv_id], hi, limit);
+        fpfh_mc_body_sparse<NKS, true, HI, MOM>(rec, offset, cnt, idx, nbrs_begin, kp_pos, W, counts, packed, packed_bytes, p4, out, q,
+                                                b0, b1, rowbuf_all[wv_id], abuf_all[wv_id], hi, limit, mom_radius, cov);
     } else {
-        fpfh_mc_body_sparse<NKS, false, HI>(rec, offset, cnt, idx, nbrs_begin, kp_pos, W, counts, counts, table_bytes, p4, out, q,
-                                            b0, b1, rowbuf_all[wv_id], abuf_all[wv_id], hi, limit);
+        fpfh_mc_body_sparse<NKS, false, HI, MOM>(rec, offset, cnt, idx, nbrs_begin, kp_pos, W, counts, counts, table_bytes, p4, out, q,
+                                                 b0, b1, rowbuf_all[wv_id], abuf_all[wv_id], hi, limit, mom_radius, cov);
     }
 }
 
@@ -444,7 +447,20 @@ static int launch_fpfh(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const
     return SF_OK;
 }
 
-static int launch_fpfh_mc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const int32_t *kp_pos, int64_t m, double *dout)
+// Whether a K7 over these lists, on this table as the host knows it NOW, runs a form that carries the frame moments: the
+// sparse form (a byte table whose block mask the host knows exactly, at most two blocks live) over lists of at most three
+// chunks.  Host knowledge only -- no launch, no read-back.
+static bool fpfh_mc_carries_moments(const sf_nbrs *nb, const sf_spfh *sp)
+{
+    if (sp->elem_bytes != 1 || sp->stride != 128 || sp->win_len > 127 || !nb->self || nb->max_count > 192 || nb->max_count < 1) return false;
+    if (!sp->host_live_valid || !sp->mask_known || __builtin_popcount(sp->host_live[0] & 0xffu) > 2) return false;
+    const sf_dispatch d = sf_nbrs_dispatch(nb);
+    return d.chunks >= 1 && d.chunks <= 3 && d.n_tail == 0;
+}
+
+// cov != NULL: the launch must carry the frame moments (checked by the caller: fpfh_mc_carries_moments) and serve every query.
+static int launch_fpfh_mc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const int32_t *kp_pos, int64_t m, double *dout,
+                          double *cov = nullptr)
 {
     const dim3 grid(sf_xcd_grid(sf_div_up(m, SF_MC_WPB))), block(64 * SF_MC_WPB);
     const size_t tb = (size_t)sp->rows_alloc * 128;
@@ -480,6 +496,28 @@ static int launch_fpfh_mc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, co
 #define SF_MC_ARGS c->rec, nb->offset, nb->count, nb->idx, nb->self_begin, kp_pos, m, W, (const uint8_t *)sp->counts,       \
                    (unsigned)tb, (const double *)sp->p4, (const unsigned *)sp->live, (const uint8_t *)sp->packed,                \
                    (unsigned)((size_t)sp->rows_alloc * 32), dout, hi
+    if (cov) {
+        // K7 with the frame moments: the sparse form, at most three chunks.  The few lists that need more chunks than the bulk
+        // (sf_dispatch::mid_sel) take the THREE-chunk instantiation here -- none is longer -- where the plain launch uses four.
+        if (kp_pos || !fpfh_mc_carries_moments(nb, sp)) {
+            sf_set_error("sf_fpfh_moments: these lists / this table do not take a K7 form that carries the frame moments");
+            return SF_ERR_UNSUPPORTED;
+        }
+#define SF_MCM_LAUNCH2(NAME, GRID, NKS, HI, LIMIT, SELP, NSEL)                                                        \
+        SF_LAUNCH(ctx, NAME, (k_fpfh_mc_sparse<NKS, HI, true>), GRID, block, SF_MC_ARGS, LIMIT, SELP, NSEL, d.view_first, nb->radius, cov)
+#define SF_MCM_LAUNCH(NAME, GRID, NKS, LIMIT, SELP, NSEL)                                                             \
+        if (hi) { SF_MCM_LAUNCH2(NAME, GRID, NKS, true, LIMIT, SELP, NSEL); } else { SF_MCM_LAUNCH2(NAME, GRID, NKS, false, LIMIT, SELP, NSEL); }
+        if (d.chunks <= 1) { SF_MCM_LAUNCH("k7_fpfh", grid, 1, d.limit, (const int32_t *)nullptr, (int64_t)0) }
+        else if (d.chunks == 2) { SF_MCM_LAUNCH("k7_fpfh", grid, 2, d.limit, (const int32_t *)nullptr, (int64_t)0) }
+        else { SF_MCM_LAUNCH("k7_fpfh", grid, 3, d.limit, (const int32_t *)nullptr, (int64_t)0) }
+        if (d.n_mid) {
+            const dim3 grid_mid(sf_xcd_grid(sf_div_up(d.n_mid, SF_MC_WPB)));
+            SF_MCM_LAUNCH("k7_fpfh_mid", grid_mid, 3, 255, d.mid_sel, d.n_mid)
+        }
+#undef SF_MCM_LAUNCH
+#undef SF_MCM_LAUNCH2
+        return SF_OK;
+    }
     // Which form runs is decided here, on the table-wide block mask -- read back once per K6 (8 bytes; the one host
     // round trip of sf_fpfh: it waits for K6, so a caller that wants it hidden queues independent work first, as
     // DescriptorJob does with the frame eigen-solves on the side stream).  Both kernels re-check the mask on the device.
@@ -497,7 +535,7 @@ static int launch_fpfh_mc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, co
     }
     const bool sparse = __builtin_popcount(sp->host_live[0] & 0xffu) <= 2;
 #define SF_MC_LAUNCH2(NAME, GRID, NKS, HI, LIMIT, SELP, NSEL)                                                         \
-    if (sparse) { SF_LAUNCH(ctx, NAME, (k_fpfh_mc_sparse<NKS, HI>), GRID, block, SF_MC_ARGS, LIMIT, SELP, NSEL, d.view_first); } \
+    if (sparse) { SF_LAUNCH(ctx, NAME, (k_fpfh_mc_sparse<NKS, HI>), GRID, block, SF_MC_ARGS, LIMIT, SELP, NSEL, d.view_first, 0.0, (double *)nullptr); } \
     else if (padc) { SF_LAUNCH(ctx, NAME, (k_fpfh_mc<4, true, true>), GRID, block, SF_MC_ARGS, LIMIT, SELP, NSEL, d.view_first); } \
     else { SF_LAUNCH(ctx, NAME, (k_fpfh_mc<NKS, true>), GRID, block, SF_MC_ARGS, LIMIT, SELP, NSEL, d.view_first); }
 #define SF_MC_LAUNCH(NKS)                                                                                            \
@@ -532,8 +570,35 @@ static int launch_fpfh_mc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, co
     return SF_OK;
 }
 
+extern "C" int sf_fpfh_carries_moments(sf_ctx *ctx, sf_nbrs *nb, sf_spfh *sp)
+{
+    if (!ctx || !nb || !sp) return 0;
+    return fpfh_mc_carries_moments(nb, sp) ? 1 : 0;
+}
+
+static int fpfh_run(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const int64_t *kp_idx, int64_t m, double *out, int flags,
+                    double *cov);
+
 extern "C" int sf_fpfh(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const int64_t *kp_idx, int64_t m, double *out,
                        int flags)
+{
+    return fpfh_run(ctx, c, nb, sp, kp_idx, m, out, flags, nullptr);
+}
+
+// K7 of every query of `nb` that also leaves the weighted covariance of the SHOT frames in cov_dev (what
+// sf_spfh_compute_moments leaves there, bit for bit), for a K6 that ran WITHOUT them (sf_spfh_compute).
+extern "C" int sf_fpfh_moments(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, int64_t m, double *out, double *cov_dev, int flags)
+{
+    if (!cov_dev) { sf_set_error("sf_fpfh_moments: null cov"); return SF_ERR_ARG; }
+    if (nb && sp && !fpfh_mc_carries_moments(nb, sp)) { // (before anything is allocated or launched)
+        sf_set_error("sf_fpfh_moments: these lists / this table do not take a K7 form that carries the frame moments");
+        return SF_ERR_UNSUPPORTED;
+    }
+    return fpfh_run(ctx, c, nb, sp, nullptr, m, out, flags, cov_dev);
+}
+
+static int fpfh_run(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const int64_t *kp_idx, int64_t m, double *out, int flags,
+                    double *cov)
 {
     if (!ctx || !c || !nb || !sp || !out || m < 0) { sf_set_error("sf_fpfh: bad argument"); return SF_ERR_ARG; }
     if (!nb->self) { sf_set_error("sf_fpfh: needs a sf_radius_search_self result"); return SF_ERR_ARG; }
@@ -581,7 +646,7 @@ extern "C" int sf_fpfh(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const
         SF_LAUNCH(ctx, "k7_fpfh", k_fpfh_generic, dim3((unsigned)m), dim3(256), c->rec, nb->offset, nb->count, nb->idx,
                   nb->self_begin, (const int32_t *)pos, m, sp->nb3, sp->stride, (const unsigned *)sp->counts, sp->k, dout);
     } else if (m)
-        rc = sp->elem_bytes == 1   ? launch_fpfh_mc(ctx, c, nb, sp, pos, m, dout)
+        rc = sp->elem_bytes == 1   ? launch_fpfh_mc(ctx, c, nb, sp, pos, m, dout, cov)
              : sp->elem_bytes == 2 ? launch_fpfh<uint16_t>(ctx, c, nb, sp, pos, m, dout)
                                    : launch_fpfh<uint32_t>(ctx, c, nb, sp, pos, m, dout);
     if (rc == SF_OK && owned) {

@@ -73,17 +73,7 @@ typedef int v2i_t __attribute__((ext_vector_type(2)));
 #define SF_MC_WPB 4 // waves (= keypoints in flight) per workgroup: 4.6 KB of LDS each
 #endif
 
-typedef unsigned sf_u2 __attribute__((ext_vector_type(2)));
-template <int W>
-__device__ __forceinline__ void sf_lane_swap(double &a, double &b)
-{
-    const unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
-    const unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
-    const sf_u2 lo = W == 32 ? __builtin_amdgcn_permlane32_swap(alo, blo, false, false) : __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
-    const sf_u2 hi = W == 32 ? __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false) : __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
-    a = __hiloint2double((int)hi[0], (int)lo[0]);
-    b = __hiloint2double((int)hi[1], (int)lo[1]);
-}
+// (sf_lane_swap, the exchange of the recombinations below: device_util.h)
 
 // ---- pieces shared by the full and the sparse-block form ---------------------------------------------------------
 // the lane's entries of the keypoint's neighbour list, chunk by chunk (lane t of chunk c <-> neighbour 64 c + t; -1 past the
@@ -105,9 +95,18 @@ __device__ __forceinline__ void fpfh_mc_list(const int32_t *__restrict__ idx, in
 // rows for the gathers that follow
 // HI: lm[c] = the lanes of chunk c whose neighbour has more than 255 neighbours of its own (its bins are lo + 256 hi: the
 // table of high bytes, fpfh_mc_hi)
-template <int NKS, bool HI>
+// MOM: the pass also forms the weighted covariance of the keypoint's SHOT frame (shot.py:27-35: w = r - ||c||, the keypoint
+// itself included): mom_out of lane 8 e, e = 1 .. 6, is c11 c21 c31 c22 c32 c33.  It walks the very pairs K6's sweep walks --
+// same lane <-> entry assignment, the same doubles (the record is a copy of the cloud's), c and d2 formed by the same
+// expressions -- and repeats k_spfh's moments() and epilogue operation by operation (sf_sqrt_fast, the FMAs, chunks in
+// ascending order per lane, sf_wave_sum8, sf_rcp_fast), so the six numbers are K6's bit for bit.  K6 is bound by vector issue
+// with no register to spare; this kernel had idle issue slots and 18 registers free: +111 vector instructions here for -140
+// there (profiles/k7_moments_ab.md).  Done before the step loop: the accumulators are dead when the MFMA accumulators come to
+// life.  The caller keeps mom_out to the end of the kernel: a store from here sits in front of the step loop's vmcnt(0) wait.
+template <int NKS, bool HI, bool MOM = false>
 __device__ __forceinline__ int fpfh_mc_weights(const double *__restrict__ p4, double px, double py, double pz, int k,
-                                               int (&jv)[NKS], double (&wv)[NKS], unsigned long long (&lm)[NKS])
+                                               int (&jv)[NKS], double (&wv)[NKS], unsigned long long (&lm)[NKS],
+                                               double mom_radius, double &mom_out)
 {
     double gx[NKS], gy[NKS], gz[NKS], gk[NKS];
 #pragma unroll
@@ -121,12 +120,20 @@ __device__ __forceinline__ int fpfh_mc_weights(const double *__restrict__ p4, do
         }
     }
     double wmax = 0.0;
+    double ws = 0, a11 = 0, a21 = 0, a31 = 0, a22 = 0, a32 = 0, a33 = 0;
 #pragma unroll
     for (int c = 0; c < NKS; ++c) {
         wv[c] = 0.0;
         if (c == 0 || c * 64 < k) {
             const double cx = gx[c] - px, cy = gy[c] - py, cz = gz[c] - pz;
             const double d2 = (cx * cx + cy * cy) + cz * cz;
+            if (MOM && jv[c] >= 0) { // (k_spfh's moments(), spfh.hip)
+                const double w = mom_radius - sf_sqrt_fast(d2);
+                ws += w;
+                const double wx = cx * w, wy = cy * w, wz = cz * w;
+                a11 = __builtin_fma(cx, wx, a11); a21 = __builtin_fma(cy, wx, a21); a31 = __builtin_fma(cz, wx, a31);
+                a22 = __builtin_fma(cy, wy, a22); a32 = __builtin_fma(cz, wy, a32); a33 = __builtin_fma(cz, wz, a33);
+            }
             const double kd = gk[c], xx = d2 * (kd * kd);
             const double y0 = __builtin_amdgcn_rsq(xx);
             const double y1 = __builtin_fma(0.5 * y0, __builtin_fma(-(xx * y0), y0, 1.0), y0);
@@ -138,6 +145,12 @@ __device__ __forceinline__ int fpfh_mc_weights(const double *__restrict__ p4, do
             lm[c] = 0ull;
         }
         jv[c] = jv[c] < 0 ? 0 : jv[c];
+    }
+    if (MOM) { // (k_spfh's epilogue)
+        const double part[8] = {ws, a11, a21, a31, a22, a32, a33, 0.0};
+        const double tot = sf_wave_sum8(part); // lanes 8 i .. 8 i + 7 hold the sum of part[i]
+        const double iw = sf_rcp_fast(sf_read_lane(tot, 0));
+        mom_out = tot * iw; // lanes 8 e, e = 1 .. 6: c11 c21 c31 c22 c32 c33 (the caller stores them)
     }
     wmax = sf_wave_max_nonneg(wmax);
     // fixed point: W = floor(w 2^S) < 2^62 with S = 61 - floor(log2 wmax)
@@ -268,7 +281,8 @@ __device__ __forceinline__ void fpfh_mc_body(const double *__restrict__ rec, con
     unsigned long long lm[NKS];
     fpfh_mc_list<NKS>(idx, s, k, lane, jv);
     SF_MC_DMA(0) // in flight while the weights are computed
-    const int S = fpfh_mc_weights<NKS, HI>(p4, px, py, pz, k, jv, wv, lm);
+    double mom_unused = 0.0;
+    const int S = fpfh_mc_weights<NKS, HI>(p4, px, py, pz, k, jv, wv, lm, 0.0, mom_unused);
 
     v4i acc[8]; // acc[bb]: column a = bin 16 bb + a, rows = limbs 4 kb .. 4 kb + 3
 #pragma unroll
@@ -323,9 +337,8 @@ __device__ __forceinline__ void fpfh_mc_body(const double *__restrict__ rec, con
     // sum over the four limb groups g = kb, transposing as we go: after the exchange with lane ^ 32 a lane keeps only
     // the blocks bb = 4 (kb >> 1) + {0..3}, after the one with lane ^ 16 only bb = 4 (kb >> 1) + 2 (kb & 1) + {0, 1}
     // -- the two bins it writes
-    // gfx950's lane-swap instructions do the exchange AND the selection in one go, without the LDS: v_permlane32_swap(a, b)
-    // leaves a = {a[0..31], b[0..31]}, b = {a[32..63], b[32..63]}, so a + b is "my half's block plus the partner's" in both
-    // halves; v_permlane16_swap does the same between the 16-lane rows 0/1 and 2/3 (tools/ubench/permlane_swap.hip).
+    // gfx950's lane-swap instructions do the exchange AND the selection in one go, without the LDS (sf_lane_swap): a + b is
+    // "my half's block plus the partner's" in both halves
     double keep[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -373,7 +386,7 @@ __device__ __forceinline__ void fpfh_mc_body(const double *__restrict__ rec, con
 // --------------------------------------------------------------------------------------------------
 // PACKED: the two chunks come from K6's packed copy of the table (`rows`: 32 bytes per row = {chunk b0, chunk b1}) instead
 // of the table itself (`rows` = counts, 128 bytes per row): four rows per cache line for the gather.
-template <int NKS, bool PACKED, bool HI>
+template <int NKS, bool PACKED, bool HI, bool MOM = false>
 __device__ __forceinline__ void fpfh_mc_body_sparse(const double *__restrict__ rec, const int64_t *__restrict__ offset,
                                                     const int32_t *__restrict__ cnt, const int32_t *__restrict__ idx,
                                                     int64_t nbrs_begin, const int32_t *__restrict__ kp_pos, sf_bin_window W,
@@ -381,7 +394,8 @@ __device__ __forceinline__ void fpfh_mc_body_sparse(const double *__restrict__ r
                                                     unsigned rows_bytes, const double *__restrict__ p4,
                                                     double *__restrict__ out, int64_t q, int b0, int b1,
                                                     unsigned *rowbuf /* 4 KB: four steps of 1 KB */, unsigned char *abuf /* 576 B */,
-                                                    const uint8_t *__restrict__ hi, int limit)
+                                                    const uint8_t *__restrict__ hi, int limit, double mom_radius = 0.0,
+                                                    double *__restrict__ cov = nullptr /* MOM: 6 doubles per query */)
 {
     const int lane = threadIdx.x & 63;
     const int64_t i = kp_pos ? (int64_t)kp_pos[q] : nbrs_begin + q;
@@ -432,7 +446,8 @@ __device__ __forceinline__ void fpfh_mc_body_sparse(const double *__restrict__ r
     if (32 < k) SF_MCS_DMA(1)
     if (NKS >= 2 && 64 < k) SF_MCS_DMA(2)
     if (NKS >= 2 && 96 < k) SF_MCS_DMA(3)
-    const int S = fpfh_mc_weights<NKS, HI>(p4, px, py, pz, k, jv, wv, lm);
+    double mom = 0.0;
+    const int S = fpfh_mc_weights<NKS, HI, MOM>(p4, px, py, pz, k, jv, wv, lm, mom_radius, mom);
 
     v4i acc0 = v4i{0, 0, 0, 0}, acc1 = v4i{0, 0, 0, 0}, accp = v4i{0, 0, 0, 0}; // blocks b0, b1, and the padding column
     const long Bpad = (long)0x8080808080808080ull; // eight neighbours' padding bin: -128 each
@@ -483,6 +498,7 @@ __device__ __forceinline__ void fpfh_mc_body_sparse(const double *__restrict__ r
     double mine = tot, other = tot;
     sf_lane_swap<32>(mine, other); // lower half: mine = own (b0), other = b1's ; upper half: mine = b0's, other = own (b1)
     const double tot0 = mine, tot1 = other; // (after the swap `mine` is block b0's total in both halves, `other` b1's)
+    if (MOM && (lane & 7) == 0 && lane >= 8 && lane < 56) cov[6 * q + (lane >> 3) - 1] = mom;
     {
         double *o = out + q * (int64_t)W.nb3;
         fpfh_mc_zero_outside(o, W, lane);

@@ -110,16 +110,23 @@ __device__ inline int theta_bin_fast(const fpfh_edges &ed, int nb, double a, dou
 // NB: the bin count as a compile-time constant (1..8, one instantiation each): the edge comparisons unroll to exactly
 // NB - 1 per feature and only the edges in use occupy SGPRs.  With a run-time count every slot of the 4 x 9 edge
 // table stays live and the compiler spills SGPRs into VGPR lanes (a v_readlane per comparison: +40 % time).
+#ifndef SF_SPFH_PLAIN_WAVES
+#define SF_SPFH_PLAIN_WAVES 7 // waves per SIMD of the forms of up to three chunks WITHOUT the frame moments (64 registers)
+#endif
 #ifndef SF_SPFH_WPB
 #define SF_SPFH_WPB 2 // waves (= points) per workgroup (0.655 / 0.643 / 0.645 ms at C3 for 4 / 2 / 1)
 #endif
 
 // limit / SEL: dispatch by list length, per point (sf_nbrs_dispatch) -- the main launch leaves out the points whose own list
 // exceeds its form, a second launch (SEL, the streaming form) serves exactly those.
-template <typename CT, int NCH, int NB, bool SEL>
-// (waves per SIMD: six for the forms of up to three chunks -- 80 registers; the four-chunk and the streaming form, asked for six,
+// MOM: the sweep also accumulates the weighted moments of the SHOT frame (`cov`).  A compile-time switch: the seven float64
+// accumulators and the reduction behind them are a fifth of the kernel's vector instructions and 14 of its registers, and a
+// null pointer tested at run time keeps all of that allocated.  Without them the forms of up to three chunks fit 64 registers.
+template <typename CT, int NCH, int NB, bool SEL, bool MOM>
+// (waves per SIMD, at least: six for the forms of up to three chunks with the moments -- 72 registers at three chunks, which
+// gives seven -- and seven without them -- 64 registers, which gives eight; the four-chunk and the streaming form, asked for six,
 // spilled 52-140 bytes in their sweep: on the clustered cloud K6 1.09 + 0.34 ms, with five waves and no spill 0.81 + 0.27)
-__global__ __launch_bounds__(64 * SF_SPFH_WPB) __attribute__((amdgpu_waves_per_eu((NCH == 0 || NCH >= 4) ? 5 : 6))) void k_spfh(const double *__restrict__ rec,
+__global__ __launch_bounds__(64 * SF_SPFH_WPB) __attribute__((amdgpu_waves_per_eu((NCH == 0 || NCH >= 4) ? 5 : (MOM ? 6 : SF_SPFH_PLAIN_WAVES)))) void k_spfh(const double *__restrict__ rec,
                                               const int64_t *__restrict__ offset, const int32_t *__restrict__ cnt,
     const int32_t *__restrict__ idx,
                                               int64_t m, int64_t self_begin, fpfh_edges ed, int nb_rt, int nb3, int stride,
@@ -212,7 +219,7 @@ __global__ __launch_bounds__(64 * SF_SPFH_WPB) __attribute__((amdgpu_waves_per_e
             if ((ba | bp | bt) >= 0) atomicAdd(&h[(ba * nb + bp) * nb + bt - win_lo], 1u);
         }
     };
-    // Optional by-product (cov != NULL): the weighted covariance of the SHOT frame (shot.py:27-35, w = r - ||c||, the
+    // Optional by-product (MOM): the weighted covariance of the SHOT frame (shot.py:27-35, w = r - ||c||, the
     // point itself included), from the neighbours this wave gathers anyway -- K4 then only has its eigen-solves left.
     double ws = 0, a11 = 0, a21 = 0, a31 = 0, a22 = 0, a32 = 0, a33 = 0;
     auto moments = [&](double cx, double cy, double cz) {
@@ -248,18 +255,18 @@ __global__ __launch_bounds__(64 * SF_SPFH_WPB) __attribute__((amdgpu_waves_per_e
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if ((c == 0 || c * 64 < ku) && jj[c] >= 0) {
-                if (cov) moments(cx[c] - px, cy[c] - py, cz[c] - pz);
+                if (MOM) moments(cx[c] - px, cy[c] - py, cz[c] - pz);
                 pair(cx[c] - px, cy[c] - py, cz[c] - pz, ax[c], ay[c], az[c]);
             }
     } else {
         for (int t = lane; t < k; t += 64) {
             double x, y, z, a, b, c;
             sf_load_pn(rec, idx[s + t], x, y, z, a, b, c);
-            if (cov) moments(x - px, y - py, z - pz);
+            if (MOM) moments(x - px, y - py, z - pz);
             pair(x - px, y - py, z - pz, a, b, c);
         }
     }
-    if (cov) {
+    if (MOM) {
         const double part[8] = {ws, a11, a21, a31, a22, a32, a33, 0.0};
         const double tot = sf_wave_sum8(part); // lanes 8 i .. 8 i + 7 hold the sum of part[i]
         const double wsum = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(tot), 0),
@@ -634,11 +641,14 @@ static int spfh_compute(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, cons
     const dim3 grid_mid(sf_xcd_grid(sf_div_up(dsp.n_mid > 0 ? dsp.n_mid : 1, SF_SPFH_WPB)));
     uint8_t *const hi_rows = sp->elem_bytes == 1 ? sp->hi : nullptr;
 #define SF_SPFH_NB(NAME, GRID, CT, NCH, NB, SEL, SELP, NSEL)                                                            \
-    SF_LAUNCH(ctx, NAME, (k_spfh<CT, NCH, NB, SEL>), GRID, block, c->rec, nb->offset, nb->count, nb->idx, m,            \
+    SF_SPFH_MOM(NAME, GRID, CT, NCH, NB, SEL, SELP, NSEL, true) else SF_SPFH_MOM(NAME, GRID, CT, NCH, NB, SEL, SELP, NSEL, false)
+#define SF_SPFH_MOM(NAME, GRID, CT, NCH, NB, SEL, SELP, NSEL, MOM)                                                       \
+    if ((cov != nullptr) == MOM) {                                                                                      \
+    SF_LAUNCH(ctx, NAME, (k_spfh<CT, NCH, NB, SEL, MOM>), GRID, block, c->rec, nb->offset, nb->count, nb->idx, m,       \
               nb->self_begin, ed, nbn, sp->nb3, sp->stride, (CT *)sp->counts, sp->k, (unsigned)sp->bias, sp->p4, nb->radius, cov, \
               sizeof(CT) == 1 ? sp->live : (unsigned *)nullptr, alpha_bin, nrm_max, fused_packed, fused_b0, fused_b1,   \
               hi_rows, dsp.limit, SELP, NSEL, dsp.view_first, alpha_pair, sizeof(CT) == 1 ? sp->win_lo : 0,                \
-              sizeof(CT) == 1 ? sp->win_len : sp->nb3)
+              sizeof(CT) == 1 ? sp->win_len : sp->nb3); }
     // (9 and 11 bins: byte tables with a window only -- instantiated for that element type alone: WIDE = 1)
 #define SF_SPFH_WIDE_1(NAME, GRID, CT, NCH, SEL, SELP, NSEL)                                                            \
     if (nbn == 9) { SF_SPFH_NB(NAME, GRID, CT, NCH, 9, SEL, SELP, NSEL); }                                              \
@@ -719,6 +729,7 @@ static int spfh_compute(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, cons
 #undef SF_SPFH_WIDE_0
 #undef SF_SPFH_LAUNCH
 #undef SF_SPFH_NB
+#undef SF_SPFH_MOM
     return SF_OK;
 }
 

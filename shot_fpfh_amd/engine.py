@@ -1312,6 +1312,21 @@ class Spfh:
         )
         return res
 
+    def fpfh_carries_moments(self, self_nbrs: Neighbors) -> bool:
+        """Whether fpfh_moments() on these lists would run a K7 form that carries the frame moments (host knowledge only)."""
+        return bool(self.engine.lib.sf_fpfh_carries_moments(self.engine.h, self_nbrs.h, self.h))
+
+    def fpfh_moments(self, self_nbrs: Neighbors, out: DeviceArray, moments_out: DeviceArray) -> bool:
+        """K7 of every query of `self_nbrs` into `out` that also leaves the frame moments compute(..., moments_out=) would have
+        left, for a table computed WITHOUT them.  False, with nothing launched, when K7's form for this table and these lists
+        does not carry them (the caller falls back to compute(..., moments_out=) + fpfh())."""
+        rc = self.engine.lib.sf_fpfh_moments(self.engine.h, self.cloud.h, self_nbrs.h, self.h, self_nbrs.m, out.ptr,
+                                             moments_out.ptr, SF_OUT_DEVICE)
+        if rc == _ffi.SF_ERR_UNSUPPORTED:
+            return False
+        _ffi.check(rc, "sf_fpfh_moments")
+        return True
+
     def free(self) -> None:
         if getattr(self, "h", None) and self.engine.h:
             self.engine.lib.sf_spfh_free(self.engine.h, self.h)

@@ -24,6 +24,7 @@ on the cloud and the query, never on the block boundaries.
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -159,6 +160,7 @@ class DescriptorJob:
         self.spfh: Optional[Spfh] = None
         self._spfh_wide = -1
         self.last_pairs = 0
+        self.last_k7_moments = False  # whether the last step() took the frame moments from K7's weight pass (_step_k7_moments)
 
     def _spfh_table(self, max_count: int) -> Spfh:
         # table kind: bytes (3: with the high-byte rows of the points that have more than 255 neighbours), 16 or 32 bits.  Bytes
@@ -269,8 +271,30 @@ class DescriptorJob:
         finally:
             nb.free()
 
+    def _step_k7_moments(self, nb: Neighbors, spfh: Spfh) -> bool:
+        """K6 WITHOUT the frame moments, K7 with them, K4, K5 -- one stream.  K6 is bound by vector issue with no register to
+        spare; K7's weight pass walks the same pairs with both to spare, so the moments cost less there than they save here
+        (docs/history.md).  Taken only when the host knows, without asking the device, that K7 runs a form that carries them:
+        a self search over the whole block on one rank, the byte table in its sparse form, no list longer than three chunks.
+        SF_FPFH_NO_K7_MOMENTS=1 (read at every call) keeps the moments in K6.  False: nothing of this path was kept, the
+        caller runs the usual one (a K6 whose data widened the table's block mask under K7's feet: the table is computed again,
+        with the moments)."""
+        if os.environ.get("SF_FPFH_NO_K7_MOMENTS") or getattr(spfh, "elem_bytes", 0) != 1 or nb.max_count > 192:
+            return False
+        if not spfh.fpfh_carries_moments(nb):
+            return False
+        spfh.compute(nb)
+        if not spfh.fpfh_moments(nb, self.fpfh_out, self.moments):
+            return False
+        # (K4 alone between K7 and K5.  Hiding half of it under a first half of K5 -- the keypoints in two halves, the second
+        # half's eigen-solves on the side stream -- was measured slower: the second K5 launch costs more than half a K4.)
+        nb.lrf_raw_from_moments(self.moments, 0, self.lrf_out)
+        nb.shot_from_raw_lrf(self.lrf_out, self.normalize, self.min_nb, self.shot_out)
+        return True
+
     def step(self) -> None:
         cloud, (b, e) = self.cloud, self.plan.block()
+        self.last_k7_moments = False
         if self.plan.world > 1 and self.exchange == "neighbor":
             return self._step_neighbor()
         if self.plan.world > 1:
@@ -312,6 +336,9 @@ class DescriptorJob:
                         if self.moments is not None:
                             self.moments.free()
                         self.moments = self.engine.empty((nb.m, 6))
+                    if self.plan.world == 1 and blk is nb and not two_streams and self._step_k7_moments(nb, spfh):
+                        self.last_k7_moments = True
+                        return
                     spfh.compute(nb, moments_out=self.moments)  # K6 + frame moments, before the chains part
                 # the eigen-solves of the frames need only K6's moments and K7 needs only K6's table: side by side (the
                 # small, long-latency eigen kernel disappears under K7); K5 follows both
