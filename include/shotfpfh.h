@@ -572,7 +572,7 @@ int sf_icp_accumulate(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const i
 int sf_transform_points(sf_ctx *ctx, double *pts_dev, int64_t n, const double *Rt /* 12 */);
 
 /* ---- generalized (plane-to-plane) ICP, K16 (Segal, Haehnel, Thrun, RSS 2009; no counterpart in the reference) --------
- * One iteration's device work, the chain of the call above with a third sums pass.  Every point carries the covariance
+ * One iteration's device work, the chain of the call above in a third mode.  Every point carries the covariance
  * C = I - (1 - epsilon) n n^T of its unit normal n (a zero normal: C = I; the sign of n does not matter).  The reference
  * cloud needs normals; nrm_dev holds the scan's, one row per row of pts_dev (n x 3 doubles on the device), and a row is
  * reached through sel_dev exactly as its point is (repeated ids allowed).  Rt as above; NULL leaves the normals alone too.
@@ -609,8 +609,8 @@ int sf_icp_accumulate_gicp(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, co
  *           [17] sum |p - q|^2 (mode 0), [35] sum |h| (mode 1) or sum r^T M r (mode 2), [36] sum |r|^2 (mode 2)
  *   [40..42] sum w p, [43..45] sum w q, [46] sum w r2
  *   the rest, [47] included, is zero, and so is everything when no pair is kept.
- * With loss 0, or Huber with k above every residual, [0..39] are the numbers of sf_icp_accumulate / sf_icp_accumulate_gicp bit for
- * bit, [7] = [0] and [40..45] = [1..6].  SF_ERR_ARG names the offending argument in sf_last_error(). */
+ * sf_icp_accumulate and sf_icp_accumulate_gicp are this call with loss 0: they return its [0..39] with [7] cleared.  So with loss
+ * 0, or Huber with k above every residual, [0..39] are their numbers bit for bit, [7] = [0] and [40..45] = [1..6].  SF_ERR_ARG names the offending argument in sf_last_error(). */
 int sf_icp_accumulate_robust(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev /* NULL unless mode 2 */,
                              const int64_t *sel_dev, int64_t m, const double *Rt, double d_max, int mode /* 0, 1, 2 */, double epsilon,
                              int loss /* 0 .. 4 */, double scale, double *sums /* 48 */);

@@ -15,14 +15,15 @@
 // fixed order, so a run is reproducible bit for bit.  Point-to-point is centred in a second pass (centroids first),
 // which keeps the cross-covariance free of cancellation, like the reference's explicit centring.
 //
-// K16, generalized (plane-to-plane) ICP (Segal, Haehnel, Thrun, RSS 2009; no counterpart in the reference): the same chain
-// with a third pass B, k_gicp_sums, which weights every pair by M = (C_b + R C_a R^T)^-1, C = I - (1 - eps) n n^T from the
-// unit normal of either point, and leaves the 6x6 Gauss-Newton system of sum r^T M r for the host (sf_icp_accumulate_gicp).
-//
-// K17, robust losses for all three modes (no counterpart in the reference): the same chain with sibling sums kernels,
-// k_robust_sums, which give every kept pair a weight psi(r) / r of its residual (Huber, Cauchy, Geman-McClure, Tukey) and leave the
-// weighted sums for the host (sf_icp_accumulate_robust).  The kernels above it are untouched: the two older calls launch what
-// they launched before.
+// ONE kernel family, k_icp_sums<PASS, MODE>, and ONE host chain, icp_chain, serve the three entry points:
+//   MODE 0 point to point, MODE 1 point to plane (sf_icp_accumulate);
+//   MODE 2 generalized (plane-to-plane) ICP, K16 (Segal, Haehnel, Thrun, RSS 2009; no counterpart in the reference): every pair is
+//     weighted by M = (C_b + R C_a R^T)^-1, C = I - (1 - eps) n n^T from the unit normal of either point, and the 6x6 Gauss-Newton
+//     system of sum r^T M r is left for the host (sf_icp_accumulate_gicp);
+//   K17, robust losses for all three modes (no counterpart in the reference): every kept pair has a weight psi(r) / r of its
+//     residual (Huber, Cauchy, Geman-McClure, Tukey), and the weighted sums are left for the host (sf_icp_accumulate_robust).
+// The two plain entry points are the chain with loss none: every weight is 1.0, w * term is the term, and they return the first 40
+// of its 48 numbers with [7] (sum w) cleared.
 #include "common.h"
 #include "device_util.h"
 
@@ -67,142 +68,8 @@ __device__ inline void block_fold(double (&acc)[NV], double *__restrict__ partia
     if (threadIdx.x < NV) partial_row[threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
 }
 
-// pass A (both modes): inlier count, sum of inlier points, sum of their neighbours
-// pass B, MODE 0 (point to point): centred cross-covariance H = sum (p - pbar)(q - qbar)^T (9) and sum |p - q|^2
-// pass B, MODE 1 (point to plane): upper triangle of G^T G (21), G^T h (6), sum |h| with g = [p x n, n], h = (q - p) . n
-template <int PASS, int MODE>
-__global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx, const double *__restrict__ qy,
-                                                  const double *__restrict__ qz, const int32_t *__restrict__ idx,
-                                                  const double *__restrict__ rec, int64_t m, double d_max,
-                                                  const double *__restrict__ mean /* 6, pass B mode 0 */,
-                                                  double *__restrict__ partial)
-{
-    constexpr int NV = PASS == 0 ? 7 : (MODE == 0 ? 10 : 28);
-    double acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-    double pm[3] = {0, 0, 0}, qm[3] = {0, 0, 0};
-    if (PASS == 1 && MODE == 0) {
-        pm[0] = mean[0]; pm[1] = mean[1]; pm[2] = mean[2];
-        qm[0] = mean[3]; qm[1] = mean[4]; qm[2] = mean[5];
-    }
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-        const double px = qx[i], py = qy[i], pz = qz[i];
-        double x, y, z, nx = 0, ny = 0, nz = 0;
-        if (PASS == 1 && MODE == 1) sf_load_pn(rec, idx[i], x, y, z, nx, ny, nz);
-        else sf_load_xyz(rec, idx[i], x, y, z);
-        const double dx = x - px, dy = y - py, dz = z - pz;
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
-        if (!(sqrt(d2) <= d_max)) continue; // KDTree.query returns sqrt(d2); `distances <= d_max` (icp.py:64, 112, 164)
-        if (PASS == 0) {
-            acc[0] += 1.0;
-            acc[1] += px; acc[2] += py; acc[3] += pz;
-            acc[4] += x; acc[5] += y; acc[6] += z;
-        } else if (MODE == 0) {
-            const double ax = px - pm[0], ay = py - pm[1], az = pz - pm[2];
-            const double bx = x - qm[0], by = y - qm[1], bz = z - qm[2];
-            acc[0] += ax * bx; acc[1] += ax * by; acc[2] += ax * bz;
-            acc[3] += ay * bx; acc[4] += ay * by; acc[5] += ay * bz;
-            acc[6] += az * bx; acc[7] += az * by; acc[8] += az * bz;
-            acc[9] += d2;
-        } else {
-            const double g[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz}; // cross(p, n), n
-            const double h = (dx * nx + dy * ny) + dz * nz;
-            int t = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) acc[t++] += g[a] * g[b];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) acc[21 + a] += g[a] * h;
-            acc[27] += fabs(h);
-        }
-    }
-    block_fold<NV>(acc, partial + (size_t)blockIdx.x * ICP_NV);
-}
-
-// pass B of generalized ICP (K16).  Per kept pair, with p the moved scan point, b its nearest reference point, nb b's normal,
-// na the scan point's normal (row qrow[slot] of the scan, through sel) and c = 1 - eps -- every line one rounding per
-// operation, left to right, which tests/gicp_numpy.py repeats operation by operation:
-//   m   = (na.x R0 + na.y R1) + na.z R2 per row of R (no t; m = na when Rt is null)
-//   S   = 2 I - c (nb nb^T + m m^T):  S_ii = 2 - c (nb_i nb_i + m_i m_i),  S_ij = -(c (nb_i nb_j + m_i m_j))
-//   adj = symmetric adjugate of S, each entry ONE difference of two products; det = (S00 adj00 + S01 adj01) + S02 adj02
-//   M   = adj * (1 / det)                                                    (six entries)
-//   r   = b - p,  u = M r with u_i = (M_i0 r0 + M_i1 r1) + M_i2 r2
-//   Q   = [p]x M  (Q_0j = py M_2j - pz M_1j, ...),  T = Q [p]x^T  (T_i0 = py Q_i2 - pz Q_i1, ...)
-//   H   = J^T M J = [[T, Q], [Q^T, M]] (upper triangle, 21),  g = J^T M r = [p x u; u] (6),  r.u,  |r|^2  with J = [-[p]x, I]
-// A zero normal makes its dyad vanish (C = I); the sign of a normal cancels in the dyad.
-__global__ __launch_bounds__(256) void k_gicp_sums(const double *__restrict__ qx, const double *__restrict__ qy,
-                                                   const double *__restrict__ qz, const int32_t *__restrict__ idx,
-                                                   const int32_t *__restrict__ qrow, const double *__restrict__ rec,
-                                                   const double *__restrict__ nrm, const int64_t *__restrict__ sel,
-                                                   const double *__restrict__ Rt, int64_t m, double d_max, double epsilon,
-                                                   double *__restrict__ partial)
-{
-    constexpr int NV = 29;
-    double acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (Rt) {
-#pragma unroll
-        for (int v = 0; v < 9; ++v) R[v] = Rt[v];
-    }
-    const double c = 1.0 - epsilon;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-        const double px = qx[i], py = qy[i], pz = qz[i];
-        double x, y, z, bx, by, bz;
-        sf_load_pn(rec, idx[i], x, y, z, bx, by, bz);
-        const double r0 = x - px, r1 = y - py, r2 = z - pz;
-        const double d2 = (r0 * r0 + r1 * r1) + r2 * r2;
-        if (!(sqrt(d2) <= d_max)) continue; // the test k_icp_sums makes
-        const int64_t row = qrow ? (int64_t)qrow[i] : i;
-        const int64_t j = sel ? sel[row] : row;
-        const double ax = nrm[3 * j], ay = nrm[3 * j + 1], az = nrm[3 * j + 2];
-        double m0 = ax, m1 = ay, m2 = az;
-        if (Rt) {
-            m0 = (ax * R[0] + ay * R[1]) + az * R[2];
-            m1 = (ax * R[3] + ay * R[4]) + az * R[5];
-            m2 = (ax * R[6] + ay * R[7]) + az * R[8];
-        }
-        const double s00 = 2.0 - c * (bx * bx + m0 * m0), s11 = 2.0 - c * (by * by + m1 * m1), s22 = 2.0 - c * (bz * bz + m2 * m2);
-        const double s01 = -(c * (bx * by + m0 * m1)), s02 = -(c * (bx * bz + m0 * m2)), s12 = -(c * (by * bz + m1 * m2));
-        const double a00 = s11 * s22 - s12 * s12, a01 = s02 * s12 - s01 * s22, a02 = s01 * s12 - s02 * s11;
-        const double a11 = s00 * s22 - s02 * s02, a12 = s01 * s02 - s00 * s12, a22 = s00 * s11 - s01 * s01;
-        const double det = (s00 * a00 + s01 * a01) + s02 * a02;
-        const double inv = 1.0 / det;
-        const double M[3][3] = {{a00 * inv, a01 * inv, a02 * inv}, {a01 * inv, a11 * inv, a12 * inv}, {a02 * inv, a12 * inv, a22 * inv}};
-        double Q[3][3], u[3];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            Q[0][b] = py * M[2][b] - pz * M[1][b];
-            Q[1][b] = pz * M[0][b] - px * M[2][b];
-            Q[2][b] = px * M[1][b] - py * M[0][b];
-            u[b] = (M[b][0] * r0 + M[b][1] * r1) + M[b][2] * r2;
-        }
-        acc[0] += py * Q[0][2] - pz * Q[0][1];  // H row 0: T00 T01 T02 Q00 Q01 Q02
-        acc[1] += pz * Q[0][0] - px * Q[0][2];
-        acc[2] += px * Q[0][1] - py * Q[0][0];
-        acc[3] += Q[0][0]; acc[4] += Q[0][1]; acc[5] += Q[0][2];
-        acc[6] += pz * Q[1][0] - px * Q[1][2];  // row 1: T11 T12 Q10 Q11 Q12
-        acc[7] += px * Q[1][1] - py * Q[1][0];
-        acc[8] += Q[1][0]; acc[9] += Q[1][1]; acc[10] += Q[1][2];
-        acc[11] += px * Q[2][1] - py * Q[2][0]; // row 2: T22 Q20 Q21 Q22
-        acc[12] += Q[2][0]; acc[13] += Q[2][1]; acc[14] += Q[2][2];
-        acc[15] += M[0][0]; acc[16] += M[0][1]; acc[17] += M[0][2]; // rows 3 .. 5: M
-        acc[18] += M[1][1]; acc[19] += M[1][2];
-        acc[20] += M[2][2];
-        acc[21] += py * u[2] - pz * u[1];       // g = [p x u; u]
-        acc[22] += pz * u[0] - px * u[2];
-        acc[23] += px * u[1] - py * u[0];
-        acc[24] += u[0]; acc[25] += u[1]; acc[26] += u[2];
-        acc[27] += (r0 * u[0] + r1 * u[1]) + r2 * u[2];
-        acc[28] += d2;
-    }
-    block_fold<NV>(acc, partial + (size_t)blockIdx.x * ICP_NV);
-}
-
-// fold the block partials in block order; pass A also leaves the centroids (means) for pass B
+// fold the block partials in block order (PASS 1 of every mode); given `mean` it also leaves the centroids of slots 1 .. 6 over
+// slot 0, which no caller asks for since k_icp_means folds PASS 0
 __global__ __launch_bounds__(64) void k_icp_final(const double *__restrict__ partial, int nblocks, int nv, double *__restrict__ out,
                                                   double *__restrict__ mean)
 {
@@ -217,7 +84,7 @@ __global__ __launch_bounds__(64) void k_icp_final(const double *__restrict__ par
     }
 }
 
-// ---- K17: robust losses (sf_icp_accumulate_robust) -------------------------------------------------------------------------------
+// ---- the weight of a kept pair (K17) ------------------------------------------------------------------------------------------
 // The weight psi(r) / r of a kept pair from its squared residual r2 and the scale k (kk = k * k), one rounding per operation,
 // which tests/icp_robust_numpy.py repeats operation by operation:
 //   0 none            1
@@ -242,22 +109,35 @@ __device__ inline double robust_weight(int loss, double r2, double k, double kk)
     return loss == 2 ? c : c * c;
 }
 
-// Both passes of the three modes with a weight w per kept pair.  The pair's terms are those of k_icp_sums / k_gicp_sums, formed by
-// the same operations in the same order; its squared residual r2 is d2 (MODE 0), h h (MODE 1) or the Mahalanobis term
-// (r0 u0 + r1 u1) + r2 u2 clamped at 0 (MODE 2), and both passes form w from it by the same operations, so they get the same bits.
-//   PASS 0 (15): 1, p, q as pass A of k_icp_sums, then w, w p (3), w q (3), w r2
-//   PASS 1: every fit term of the mode's pass B times w (one more rounding); the residual sums the host reports as rms stay
-//           unweighted: d2 (MODE 0: [9], MODE 2: [28]), |h| (MODE 1: [27]), the Mahalanobis term as formed (MODE 2: [27]).
-//           MODE 0 centres with `mean`, the WEIGHTED centroids k_robust_final leaves.
-// With w = 1 (loss none, or Huber with k above every residual) w * term is the term: the numbers of today's kernels, bit for bit.
+// Both passes of the three modes, with a weight w per kept pair; every line one rounding per operation, left to right, which
+// tests/icp_numpy.py, tests/gicp_numpy.py and tests/icp_robust_numpy.py repeat operation by operation.
+//   PASS 0 (15): inlier count, sum of inlier points p, sum of their neighbours q (7), then w, w p (3), w q (3), w r2
+//   PASS 1, MODE 0 (point to point): centred cross-covariance H = sum w (p - pbar)(q - qbar)^T (9) and sum |p - q|^2, centred with
+//           `mean`, the WEIGHTED centroids k_icp_means leaves
+//   PASS 1, MODE 1 (point to plane): upper triangle of G^T G (21), G^T h (6), sum |h| with g = [p x n, n], h = (q - p) . n
+//   PASS 1, MODE 2 (generalized, K16): with p the moved scan point, b its nearest reference point, nb b's normal, na the scan point's
+//           normal (row qrow[slot] of the scan, through sel) and c = 1 - eps:
+//     m   = (na.x R0 + na.y R1) + na.z R2 per row of R (no t; m = na when Rt is null)
+//     S   = 2 I - c (nb nb^T + m m^T):  S_ii = 2 - c (nb_i nb_i + m_i m_i),  S_ij = -(c (nb_i nb_j + m_i m_j))
+//     adj = symmetric adjugate of S, each entry ONE difference of two products; det = (S00 adj00 + S01 adj01) + S02 adj02
+//     M   = adj * (1 / det)                                                    (six entries)
+//     r   = b - p,  u = M r with u_i = (M_i0 r0 + M_i1 r1) + M_i2 r2
+//     Q   = [p]x M  (Q_0j = py M_2j - pz M_1j, ...),  T = Q [p]x^T  (T_i0 = py Q_i2 - pz Q_i1, ...)
+//     H   = J^T M J = [[T, Q], [Q^T, M]] (upper triangle, 21),  g = J^T M r = [p x u; u] (6),  r.u,  |r|^2  with J = [-[p]x, I]
+//           A zero normal makes its dyad vanish (C = I); the sign of a normal cancels in the dyad.
+// The pair's squared residual r2 is d2 (MODE 0), h h (MODE 1) or the Mahalanobis term (r0 u0 + r1 u1) + r2 u2 clamped at 0 (MODE 2),
+// and both passes form w from it by the same operations, so they get the same bits.  PASS 1 multiplies every fit term by w (one
+// more rounding); the residual sums the host reports as rms stay unweighted: d2 (MODE 0: [9], MODE 2: [28]), |h| (MODE 1: [27]),
+// the Mahalanobis term as formed (MODE 2: [27]).
+// With w = 1 (loss none, or Huber with k above every residual) w * term is the term, bit for bit: the plain entry points.
 template <int PASS, int MODE>
-__global__ __launch_bounds__(256) void k_robust_sums(const double *__restrict__ qx, const double *__restrict__ qy,
-                                                     const double *__restrict__ qz, const int32_t *__restrict__ idx,
-                                                     const int32_t *__restrict__ qrow, const double *__restrict__ rec,
-                                                     const double *__restrict__ nrm, const int64_t *__restrict__ sel,
-                                                     const double *__restrict__ Rt, int64_t m, double d_max, double epsilon, int loss,
-                                                     double k, const double *__restrict__ mean /* 6, PASS 1 MODE 0 */,
-                                                     double *__restrict__ partial)
+__global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx, const double *__restrict__ qy,
+                                                  const double *__restrict__ qz, const int32_t *__restrict__ idx,
+                                                  const int32_t *__restrict__ qrow, const double *__restrict__ rec,
+                                                  const double *__restrict__ nrm, const int64_t *__restrict__ sel,
+                                                  const double *__restrict__ Rt, int64_t m, double d_max, double epsilon, int loss,
+                                                  double k, const double *__restrict__ mean /* 6, PASS 1 MODE 0 */,
+                                                  double *__restrict__ partial)
 {
     constexpr int NV = PASS == 0 ? 15 : (MODE == 0 ? 10 : (MODE == 1 ? 28 : 29));
     double acc[NV];
@@ -282,13 +162,13 @@ __global__ __launch_bounds__(256) void k_robust_sums(const double *__restrict__ 
         else sf_load_pn(rec, idx[i], x, y, z, nx, ny, nz);
         const double dx = x - px, dy = y - py, dz = z - pz;
         const double d2 = (dx * dx + dy * dy) + dz * dz;
-        if (!(sqrt(d2) <= d_max)) continue; // the gate of k_icp_sums, applied first
+        if (!(sqrt(d2) <= d_max)) continue; // KDTree.query returns sqrt(d2); `distances <= d_max` (icp.py:64, 112, 164)
         double r2 = d2, h = 0.0, maha = 0.0, M[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, u[3] = {0, 0, 0};
         if (MODE == 1) {
             h = (dx * nx + dy * ny) + dz * nz;
             r2 = h * h;
         }
-        if (MODE == 2) { // M and u as k_gicp_sums forms them
+        if (MODE == 2) {
             const int64_t row = qrow ? (int64_t)qrow[i] : i;
             const int64_t j = sel ? sel[row] : row;
             const double ax = nrm[3 * j], ay = nrm[3 * j + 1], az = nrm[3 * j + 2];
@@ -328,7 +208,7 @@ __global__ __launch_bounds__(256) void k_robust_sums(const double *__restrict__ 
             acc[6] += w * (az * bx); acc[7] += w * (az * by); acc[8] += w * (az * bz);
             acc[9] += d2;
         } else if constexpr (MODE == 1) {
-            const double g[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+            const double g[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz}; // cross(p, n), n
             int t = 0;
 #pragma unroll
             for (int a = 0; a < 6; ++a)
@@ -370,8 +250,8 @@ __global__ __launch_bounds__(256) void k_robust_sums(const double *__restrict__ 
 
 // fold PASS 0's block partials in block order into sums[48]: [0..7] as they are, w p, w q, w r2 to [40..46]; and leave the
 // weighted centroids sum w p / sum w, sum w q / sum w (zero when sum w is not positive) for PASS 1 of MODE 0
-__global__ __launch_bounds__(64) void k_robust_final(const double *__restrict__ partial, int nblocks, double *__restrict__ out,
-                                                     double *__restrict__ mean)
+__global__ __launch_bounds__(64) void k_icp_means(const double *__restrict__ partial, int nblocks, double *__restrict__ out,
+                                                  double *__restrict__ mean)
 {
     const int v = threadIdx.x;
     double a = 0.0;
@@ -400,14 +280,13 @@ extern "C" int sf_transform_points(sf_ctx *ctx, double *pts_dev, int64_t n, cons
     return SF_OK;
 }
 
-extern "C" int sf_icp_accumulate(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const int64_t *sel_dev, int64_t m,
-                                 const double *Rt, double d_max, int mode, double *sums)
+// The chain of the three entry points, which have checked their arguments, set the device and returned for m == 0: move the rows,
+// find their nearest reference points, both sums passes with their folds, and the 48 numbers (layout in include/shotfpfh.h) back
+// in `sums`.  `who` names the entry point in the empty-reference error.
+static int icp_chain(const char *who, sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev, const int64_t *sel_dev,
+                     int64_t m, const double *Rt, double d_max, int mode, double epsilon, int loss, double scale, double *sums)
 {
-    if (!ctx || !ref || !pts_dev || !sums || m < 0 || (mode != 0 && mode != 1)) { sf_set_error("sf_icp_accumulate: bad argument"); return SF_ERR_ARG; }
-    SF_HIP(hipSetDevice(ctx->device));
-    for (int i = 0; i < 40; ++i) sums[i] = 0.0;
-    if (!m) return SF_OK;
-    if (ref->n < 1) { sf_set_error("sf_icp_accumulate: empty reference cloud"); return SF_ERR_ARG; }
+    if (ref->n < 1) { sf_set_error("%s: empty reference cloud", who); return SF_ERR_ARG; }
     sf_pool_guard tmp(ctx);
     double *dRt = nullptr, *moved = nullptr, *partial = nullptr, *dout = nullptr, *dmean = nullptr;
     if (Rt) {
@@ -423,25 +302,50 @@ extern "C" int sf_icp_accumulate(sf_ctx *ctx, sf_cloud *ref, const double *pts_d
     sf_nbrs *nb = sf_knn_search(ctx, ref, moved, m, 1, SF_IN_DEVICE); // kdtree.query(points_aligned)
     if (!nb) return SF_ERR_HIP;
     struct nb_guard { sf_ctx *c; sf_nbrs *n; ~nb_guard() { sf_nbrs_free(c, n); } } nbg{ctx, nb};
-    if (mode == 1) SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, ref));
-    SF_HIP(hipMemsetAsync(dout, 0, 40 * sizeof(double), ctx->stream)); // [7], [18..39] (mode 0) and [36..39] (mode 1) belong to no pass
+    // both passes read the reference's normals: the weight comes from h or from M (fails when it was uploaded without normals)
+    if (mode != 0) SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, ref));
+    SF_HIP(hipMemsetAsync(dout, 0, 48 * sizeof(double), ctx->stream)); // the slots of no pass, [47] among them
     // the k-NN lists are in PROCESSING order (queries sorted by cell): sums do not care, and qx / qy / qz follow it
     const dim3 grid(ICP_BLOCKS), block(256);
-    SF_LAUNCH(ctx, "i1_icp_sums", (k_icp_sums<0, 0>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, ref->rec, m, d_max,
-              (const double *)nullptr, partial);
-    SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, 7, dout, dmean);
-    if (mode == 0) {
-        SF_LAUNCH(ctx, "i1_icp_sums", (k_icp_sums<1, 0>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, ref->rec, m, d_max,
-                  (const double *)dmean, partial);
-        SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, 10, dout + 8, (double *)nullptr);
-    } else {
-        SF_LAUNCH(ctx, "i1_icp_sums", (k_icp_sums<1, 1>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, ref->rec, m, d_max,
-                  (const double *)nullptr, partial);
-        SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, 28, dout + 8, (double *)nullptr);
-    }
-    SF_HIP(hipMemcpyAsync(sums, dout, 40 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const int32_t *qrow = (const int32_t *)nb->qrow;
+    const double *no_mean = nullptr;
+#define SF_ICP_PASS(PASS, MODE, mean)                                                                                                \
+    SF_LAUNCH(ctx, "i1_icp_sums", (k_icp_sums<PASS, MODE>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, qrow, ref->rec, nrm_dev,    \
+              sel_dev, (const double *)dRt, m, d_max, epsilon, loss, scale, mean, partial)
+    if (mode == 0) { SF_ICP_PASS(0, 0, no_mean); }
+    else if (mode == 1) { SF_ICP_PASS(0, 1, no_mean); }
+    else { SF_ICP_PASS(0, 2, no_mean); }
+    SF_LAUNCH(ctx, "i1_icp_means", k_icp_means, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, dout, dmean);
+    if (mode == 0) { SF_ICP_PASS(1, 0, (const double *)dmean); }
+    else if (mode == 1) { SF_ICP_PASS(1, 1, no_mean); }
+    else { SF_ICP_PASS(1, 2, no_mean); }
+#undef SF_ICP_PASS
+    SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, mode == 0 ? 10 : (mode == 1 ? 28 : 29),
+              dout + 8, (double *)nullptr);
+    SF_HIP(hipMemcpyAsync(sums, dout, 48 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
     return SF_OK;
+}
+
+// the chain without a loss, into the caller's sums[40]: every weight is 1.0, and [7], the sum of the weights, belongs to no pass here
+static int icp_chain_plain(const char *who, sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev,
+                           const int64_t *sel_dev, int64_t m, const double *Rt, double d_max, int mode, double epsilon, double *sums)
+{
+    double all[48];
+    SF_CHECK(icp_chain(who, ctx, ref, pts_dev, nrm_dev, sel_dev, m, Rt, d_max, mode, epsilon, 0, 1.0, all));
+    for (int i = 0; i < 40; ++i) sums[i] = all[i];
+    sums[7] = 0.0;
+    return SF_OK;
+}
+
+extern "C" int sf_icp_accumulate(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const int64_t *sel_dev, int64_t m,
+                                 const double *Rt, double d_max, int mode, double *sums)
+{
+    if (!ctx || !ref || !pts_dev || !sums || m < 0 || (mode != 0 && mode != 1)) { sf_set_error("sf_icp_accumulate: bad argument"); return SF_ERR_ARG; }
+    SF_HIP(hipSetDevice(ctx->device));
+    for (int i = 0; i < 40; ++i) sums[i] = 0.0;
+    if (!m) return SF_OK;
+    return icp_chain_plain("sf_icp_accumulate", ctx, ref, pts_dev, nullptr, sel_dev, m, Rt, d_max, mode, 1.0, sums);
 }
 
 extern "C" int sf_icp_accumulate_gicp(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev, const int64_t *sel_dev,
@@ -454,37 +358,10 @@ extern "C" int sf_icp_accumulate_gicp(sf_ctx *ctx, sf_cloud *ref, const double *
     SF_HIP(hipSetDevice(ctx->device));
     for (int i = 0; i < 40; ++i) sums[i] = 0.0;
     if (!m) return SF_OK;
-    if (ref->n < 1) { sf_set_error("sf_icp_accumulate_gicp: empty reference cloud"); return SF_ERR_ARG; }
-    sf_pool_guard tmp(ctx);
-    double *dRt = nullptr, *moved = nullptr, *partial = nullptr, *dout = nullptr, *dmean = nullptr;
-    if (Rt) {
-        SF_CHECK(tmp.alloc(&dRt, 12));
-        SF_HIP(hipMemcpyAsync(dRt, Rt, 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    }
-    SF_CHECK(tmp.alloc(&moved, (size_t)m * 3));
-    SF_CHECK(tmp.alloc(&partial, (size_t)ICP_BLOCKS * ICP_NV));
-    SF_CHECK(tmp.alloc(&dout, 80));
-    SF_CHECK(tmp.alloc(&dmean, 8));
-    SF_LAUNCH(ctx, "i0_transform", k_transform, dim3((unsigned)sf_div_up(m, 256)), dim3(256), pts_dev, sel_dev, m,
-              (const double *)dRt, moved);
-    sf_nbrs *nb = sf_knn_search(ctx, ref, moved, m, 1, SF_IN_DEVICE);
-    if (!nb) return SF_ERR_HIP;
-    struct nb_guard { sf_ctx *c; sf_nbrs *n; ~nb_guard() { sf_nbrs_free(c, n); } } nbg{ctx, nb};
-    SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, ref)); // fails when the reference cloud was uploaded without normals
-    SF_HIP(hipMemsetAsync(dout, 0, 40 * sizeof(double), ctx->stream)); // [7] and [37..39] belong to no pass
-    const dim3 grid(ICP_BLOCKS), block(256);
-    SF_LAUNCH(ctx, "i1_icp_sums", (k_icp_sums<0, 0>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, ref->rec, m, d_max,
-              (const double *)nullptr, partial);
-    SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, 7, dout, dmean);
-    SF_LAUNCH(ctx, "i2_gicp_sums", k_gicp_sums, grid, block, nb->qx, nb->qy, nb->qz, nb->idx, (const int32_t *)nb->qrow, ref->rec,
-              nrm_dev, sel_dev, (const double *)dRt, m, d_max, epsilon, partial);
-    SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, 29, dout + 8, (double *)nullptr);
-    SF_HIP(hipMemcpyAsync(sums, dout, 40 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream));
-    return SF_OK;
+    return icp_chain_plain("sf_icp_accumulate_gicp", ctx, ref, pts_dev, nrm_dev, sel_dev, m, Rt, d_max, 2, epsilon, sums);
 }
 
-// K17: the chain of the two calls above with a robust weight per kept pair (sums[48], layout in include/shotfpfh.h)
+// K17: a robust weight per kept pair (sums[48], layout in include/shotfpfh.h)
 extern "C" int sf_icp_accumulate_robust(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev, const int64_t *sel_dev,
                                         int64_t m, const double *Rt, double d_max, int mode, double epsilon, int loss, double scale,
                                         double *sums)
@@ -504,41 +381,5 @@ extern "C" int sf_icp_accumulate_robust(sf_ctx *ctx, sf_cloud *ref, const double
     SF_HIP(hipSetDevice(ctx->device));
     for (int i = 0; i < 48; ++i) sums[i] = 0.0;
     if (!m) return SF_OK;
-    if (ref->n < 1) { sf_set_error("sf_icp_accumulate_robust: empty reference cloud"); return SF_ERR_ARG; }
-    sf_pool_guard tmp(ctx);
-    double *dRt = nullptr, *moved = nullptr, *partial = nullptr, *dout = nullptr, *dmean = nullptr;
-    if (Rt) {
-        SF_CHECK(tmp.alloc(&dRt, 12));
-        SF_HIP(hipMemcpyAsync(dRt, Rt, 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    }
-    SF_CHECK(tmp.alloc(&moved, (size_t)m * 3));
-    SF_CHECK(tmp.alloc(&partial, (size_t)ICP_BLOCKS * ICP_NV));
-    SF_CHECK(tmp.alloc(&dout, 80));
-    SF_CHECK(tmp.alloc(&dmean, 8));
-    SF_LAUNCH(ctx, "i0_transform", k_transform, dim3((unsigned)sf_div_up(m, 256)), dim3(256), pts_dev, sel_dev, m,
-              (const double *)dRt, moved);
-    sf_nbrs *nb = sf_knn_search(ctx, ref, moved, m, 1, SF_IN_DEVICE);
-    if (!nb) return SF_ERR_HIP;
-    struct nb_guard { sf_ctx *c; sf_nbrs *n; ~nb_guard() { sf_nbrs_free(c, n); } } nbg{ctx, nb};
-    if (mode != 0) SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, ref)); // both passes read them: the weight comes from h or from M
-    SF_HIP(hipMemsetAsync(dout, 0, 48 * sizeof(double), ctx->stream)); // the slots of no pass, [47] among them
-    const dim3 grid(ICP_BLOCKS), block(256);
-    const int32_t *qrow = (const int32_t *)nb->qrow;
-    const double *no_mean = nullptr;
-#define SF_ROBUST_PASS(PASS, MODE, mean)                                                                                              \
-    SF_LAUNCH(ctx, "i3_robust_sums", (k_robust_sums<PASS, MODE>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, qrow, ref->rec, nrm_dev, \
-              sel_dev, (const double *)dRt, m, d_max, epsilon, loss, scale, mean, partial)
-    if (mode == 0) { SF_ROBUST_PASS(0, 0, no_mean); }
-    else if (mode == 1) { SF_ROBUST_PASS(0, 1, no_mean); }
-    else { SF_ROBUST_PASS(0, 2, no_mean); }
-    SF_LAUNCH(ctx, "i3_robust_final", k_robust_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, dout, dmean);
-    if (mode == 0) { SF_ROBUST_PASS(1, 0, (const double *)dmean); }
-    else if (mode == 1) { SF_ROBUST_PASS(1, 1, no_mean); }
-    else { SF_ROBUST_PASS(1, 2, no_mean); }
-#undef SF_ROBUST_PASS
-    SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, mode == 0 ? 10 : (mode == 1 ? 28 : 29),
-              dout + 8, (double *)nullptr);
-    SF_HIP(hipMemcpyAsync(sums, dout, 48 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream));
-    return SF_OK;
+    return icp_chain("sf_icp_accumulate_robust", ctx, ref, pts_dev, nrm_dev, sel_dev, m, Rt, d_max, mode, epsilon, loss, scale, sums);
 }

@@ -13,7 +13,7 @@ feed it, which fit they ask for and what they return.
 
 `icp_generalized` (K16) has no counterpart in the reference: generalized, or plane-to-plane, ICP (Segal, Haehnel, Thrun, RSS
 2009).  Every point carries the covariance C = I - (1 - epsilon) n n^T of its unit normal, a pair (a, b) is weighted by
-M = (C_b + R C_a R^T)^-1, and the device call (`sf_icp_accumulate_gicp`, the same chain with a third sums pass) returns the
+M = (C_b + R C_a R^T)^-1, and the device call (`sf_icp_accumulate_gicp`, the same chain in its third mode) returns the
 6x6 Gauss-Newton system of sum r^T M r; the host solves it and applies the exact exponential of the step (`_gicp_fit`).
 
 `icp_robust` (K17) runs any of the three with a robust loss: the device call (`sf_icp_accumulate_robust`) weights every pair inside
@@ -184,35 +184,20 @@ class _Registration:
                 _ffi.check(self.engine.lib.sf_h2d(self.engine.h, self.rows.ptr, rows.ctypes.data_as(C.c_void_p), m * 8), "sf_h2d")
             sel = self.rows.ptr
         rt = None if moved_by is None else np.ascontiguousarray(moved_by.as_row12())
+        if mode == _GICP and self.normals is None:
+            raise ValueError("generalized ICP needs the normals of the working points")
+        raw = np.zeros(40 if loss is None else 48)
+        head = (self.engine.h, self.ref.h, self.points.ptr)
+        rows_and_motion = (sel, m, None if rt is None else rt.ctypes.data_as(C.c_void_p), float(d_max))
+        out = raw.ctypes.data_as(C.c_void_p)
         if loss is not None:
-            if mode == _GICP and self.normals is None:
-                raise ValueError("generalized ICP needs the normals of the working points")
-            raw = np.zeros(48)
-            _ffi.check(
-                self.engine.lib.sf_icp_accumulate_robust(self.engine.h, self.ref.h, self.points.ptr,
-                                                         self.normals.ptr if mode == _GICP else None, sel, m,
-                                                         None if rt is None else rt.ctypes.data_as(C.c_void_p), float(d_max), int(mode),
-                                                         float(epsilon), int(loss), float(scale), raw.ctypes.data_as(C.c_void_p)),
-                "sf_icp_accumulate_robust",
-            )
-            return _PairSums(raw, mode)
-        raw = np.zeros(40)
-        if mode == _GICP:
-            if self.normals is None:
-                raise ValueError("generalized ICP needs the normals of the working points")
-            _ffi.check(
-                self.engine.lib.sf_icp_accumulate_gicp(self.engine.h, self.ref.h, self.points.ptr, self.normals.ptr, sel, m,
-                                                       None if rt is None else rt.ctypes.data_as(C.c_void_p), float(d_max),
-                                                       float(epsilon), raw.ctypes.data_as(C.c_void_p)),
-                "sf_icp_accumulate_gicp",
-            )
-            return _PairSums(raw, mode)
-        _ffi.check(
-            self.engine.lib.sf_icp_accumulate(self.engine.h, self.ref.h, self.points.ptr, sel, m,
-                                              None if rt is None else rt.ctypes.data_as(C.c_void_p), float(d_max), mode,
-                                              raw.ctypes.data_as(C.c_void_p)),
-            "sf_icp_accumulate",
-        )
+            name, args = "sf_icp_accumulate_robust", (*head, self.normals.ptr if mode == _GICP else None, *rows_and_motion, int(mode),
+                                                      float(epsilon), int(loss), float(scale), out)
+        elif mode == _GICP:  # without a loss the plain entry points and their 40 numbers
+            name, args = "sf_icp_accumulate_gicp", (*head, self.normals.ptr, *rows_and_motion, float(epsilon), out)
+        else:
+            name, args = "sf_icp_accumulate", (*head, *rows_and_motion, mode, out)
+        _ffi.check(getattr(self.engine.lib, name)(*args), name)
         return _PairSums(raw, mode)
 
     def move(self, transform: RigidTransform) -> None:

@@ -1,5 +1,5 @@
 """Generalized (plane-to-plane) ICP (Segal, Haehnel, Thrun, RSS 2009), stated in plain NumPy (float64).  What
-shot_fpfh_amd.icp.icp_generalized and K16 (k_gicp_sums, csrc/icp.hip) are held to -- not a test file, and the product does not
+shot_fpfh_amd.icp.icp_generalized and K16 (k_icp_sums<1, 2>, csrc/icp.hip) are held to -- not a test file, and the product does not
 import it.
 
 A point with unit normal n has the covariance C = I - (1 - eps) n n^T (V diag(eps, 1, 1) V^T of PCL and Open3D; a zero normal

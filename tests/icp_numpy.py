@@ -11,8 +11,8 @@ One pass at (R, t), for scan point a:
     mode 1 (plane)        g = [py nz - pz ny, pz nx - px nz, px ny - py nx, nx, ny, nz], h = (dx nx + dy ny) + dz nz:
                           [8..28] g_a g_b (a <= b, row by row), [29..34] g_a h, [35] |h|
     every other slot is zero: [7], [18..39] in mode 0, [36..39] in mode 1
-and the sums over the kept pairs.  The device centres mode 0 with the centroids IT formed (k_icp_final: sum / count in float64,
-from its own pass A sums), which come back in the first seven numbers; handed to `terms` as means = raw[1:7] / raw[0] -- the same
+and the sums over the kept pairs.  The device centres mode 0 with the centroids IT formed (k_icp_means: with every weight 1.0, as in
+this call, sum / count in float64 from its own pass A sums), which come back in the first seven numbers; handed to `terms` as means = raw[1:7] / raw[0] -- the same
 IEEE division -- every term is the same number on both sides.  Without `means` the centroids are the math.fsum ones, rounded once.
 
 Every expression is written out operation by operation, left to right, as the kernel forms it: NumPy rounds each once (no fused
@@ -105,7 +105,7 @@ def sums(a, ref, nref, R, t, d_max, mode, means=None, tree=None):
 
 
 def device_means(raw):
-    """the centroids k_icp_final leaves for pass B, from the numbers the call returns: sum / count, zero without a pair"""
+    """the centroids k_icp_means leaves for pass B when every weight is 1.0, from the numbers the call returns: sum / count, zero without a pair"""
     raw = np.asarray(raw, dtype=np.float64)
     return raw[1:7] / raw[0] if raw[0] > 0 else np.zeros(6)
 

@@ -1,4 +1,4 @@
-"""ICP with a robust loss (K17), stated in plain NumPy (float64).  What sf_icp_accumulate_robust (k_robust_sums, k_robust_final,
+"""ICP with a robust loss (K17), stated in plain NumPy (float64).  What sf_icp_accumulate_robust (k_icp_sums, k_icp_means,
 csrc/icp.hip) and shot_fpfh_amd.icp.icp_robust are held to -- not a test file, and the product does not import it.
 
 One pass at (R, t) with the loss's scale k keeps the pairs of tests/icp_numpy.py / tests/gicp_numpy.py (the `d_max` gate first, and
@@ -18,7 +18,7 @@ every operation rounded once, left to right, as the kernel forms it.  The 48 ter
             centred with the WEIGHTED centroids given (`means`); [8..34] in modes 1 and 2.  The residual slots stay as they are:
             [17] d2 (mode 0), [35] |h| (mode 1) or the Mahalanobis term (mode 2), [36] d2 (mode 2)
     [40..42] w p  [43..45] w q  [46] w r2  [47] 0
-The device centres mode 0 with the weighted centroids IT formed (k_robust_final: sum w p / sum w in float64), which come back in
+The device centres mode 0 with the weighted centroids IT formed (k_icp_means: sum w p / sum w in float64), which come back in
 [40..45] and [7]; handed to `terms` as means = `device_means(raw)` -- the same IEEE division -- every term is the same number on
 both sides and what is left to differ is the order of the additions.
 """
@@ -134,7 +134,7 @@ def sums(mode, loss, k, a, na, ref, nref, R, t, d_max, eps=1e-3, means=None, tre
 
 
 def device_means(raw):
-    """the weighted centroids k_robust_final leaves for pass B, from the numbers the call returns"""
+    """the weighted centroids k_icp_means leaves for pass B, from the numbers the call returns"""
     raw = np.asarray(raw, dtype=np.float64)
     return raw[40:46] / raw[7] if raw[7] > 0 else np.zeros(6)
 

@@ -1,4 +1,4 @@
-"""Generalized ICP on the MI355X (K16: k_gicp_sums, sf_icp_accumulate_gicp, csrc/icp.hip) against the NumPy statement of the
+"""Generalized ICP on the MI355X (K16: k_icp_sums<1, 2>, sf_icp_accumulate_gicp, csrc/icp.hip) against the NumPy statement of the
 definition (tests/gicp_numpy.py).
 
 The check is split where the definition leaves rounding to the implementation.  ONE pass is held to the math.fsum value of each
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 U = 2.0**-53
 D_MAX = 0.05
-# Roundings that enter one term as k_gicp_sums forms it from the loaded coordinates, for the longest chain, the column of r^T M r:
+# Roundings that enter one term as k_icp_sums<1, 2> forms it from the loaded coordinates, for the longest chain, the column of r^T M r:
 # p = ((R0 x + R1 y) + R2 z) + t, 6 per component (18); m = (R0 nx + R1 ny) + R2 nz, 5 per component (15); c = 1 - eps (1);
 # S: three diagonal entries 2 - c (nb nb + m m) of 5 and three off-diagonal ones of 4 (the negation is exact) (27); the adjugate,
 # six entries of two products and a difference (18); det = (S00 a00 + S01 a01) + S02 a02 (5); 1 / det (1); M = adj inv (6);

@@ -1,10 +1,11 @@
-"""ICP with a robust loss on the MI355X (K17: k_robust_sums, k_robust_final, sf_icp_accumulate_robust, csrc/icp.hip;
+"""ICP with a robust loss on the MI355X (K17: k_icp_sums, k_icp_means, sf_icp_accumulate_robust, csrc/icp.hip;
 shot_fpfh_amd.icp.icp_robust) against the NumPy statement (tests/icp_robust_numpy.py).
 
 The check is split as for its siblings (tests/test_hip_icp_sums.py, tests/test_hip_gicp.py).  ONE pass is held to the math.fsum value
 of each of its 48 numbers within C k 2^-53 sum|term| with an equal pair count, the slots of no pass to exactly 0.0; with loss none
-(and with Huber above every residual) the call is held to today's entry points bit for bit; the whole run is held to ten times the
-statement's own sensitivity to the order of its sums, with an exact iteration count and convergence flag.
+(and with Huber above every residual) the call is held to the plain entry points bit for bit, and those to the numbers recorded in
+tests/golden/icp_plain_sums.npz; the whole run is held to ten times the statement's own sensitivity to the order of its sums, with
+an exact iteration count and convergence flag.
 
 The input sets and the `measure_*` functions are plain functions: tests/test_icp_robust_host.py asserts the conditions the tests
 below place on their inputs without a device, and tools/icp_robust_parity.py writes profiles/icp_robust_parity.md from the same
@@ -62,7 +63,7 @@ def eng():
 # ---- the device side -----------------------------------------------------------------------------------------------------------------
 class _Resident:
     """Scan (with normals) and reference resident on the device; `sums` is one sf_icp_accumulate_robust call as
-    `_Registration.pairs` makes it, `plain` today's call of the same mode."""
+    `_Registration.pairs` makes it, `plain` the plain call of the same mode (sf_icp_accumulate, sf_icp_accumulate_gicp)."""
 
     def __init__(self, eng, scan, na, ref, nref=None):
         from shot_fpfh_amd.icp import _Registration
@@ -214,7 +215,7 @@ def test_one_pass_equals_fsum_within_the_rounding_bound(eng, mode, loss, m):
     print(f"mode {mode}, loss {loss}, m = {m}: worst ratio {worst:.3g} of {C_ROUNDINGS[mode]}")
 
 
-# ---- 2. loss none is today's call ----------------------------------------------------------------------------------------------------
+# ---- 2. loss none is the plain call ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", MODE_IDS)
 def test_loss_none_and_huber_above_every_residual_return_todays_numbers_bit_for_bit(eng, mode):
     s = one_pass_set()
@@ -232,6 +233,70 @@ def test_loss_none_and_huber_above_every_residual_return_todays_numbers_bit_for_
                     assert got[7] == got[0] and np.array_equal(got[40:46], got[1:7]) and got[47] == 0.0
                     if mode == S.POINT:
                         assert got[46] == got[17]  # sum 1 * d2
+
+
+# ---- 2b. the plain calls return the numbers recorded before the unweighted sums kernels were deleted ----------------------------------
+PLAIN_GOLDEN = "icp_plain_sums.npz"  # written by tools/gen_golden_icp_plain.py, inputs included
+PLAIN_GOLDEN_KEPT = ((134, 37), (397, 106), (120, 34))  # kept pairs per (state, all rows / selection)
+
+
+def plain_golden_cases(g):
+    """(state, rows index, R, t, rows) of the fixture's six cases; state 0 is the call without a transform"""
+    for si in range(3):
+        R, t = (None, None) if si == 0 else (g["rotations"][si], g["translations"][si])
+        for ri, rows in enumerate((None, g["selection"])):
+            yield si, ri, R, t, rows
+
+
+def plain_golden_input_conditions(g):
+    """What the golden test asks of its inputs, without a device: unit normals, three blocks of scan rows, a selection with repeats
+    that ends inside a wave, no case whose kept set is a matter of rounding, and the kept counts -- from under a wave to several,
+    never under 30.  Returns the counts per (state, rows)."""
+    from scipy.spatial import cKDTree
+
+    ref, scan, ids, d_max = g["ref"], g["scan"], g["selection"], float(g["d_max"])
+    assert ref.shape == g["ref_normals"].shape == (500, 3) and scan.shape == g["scan_normals"].shape == (600, 3)
+    assert ids.shape == (150,) and ids.min() >= 0 and ids.max() < 600 and np.unique(ids).size < 150 and 150 % 64
+    assert 2 * 256 < scan.shape[0] <= 3 * 256
+    for nrm in (g["ref_normals"], g["scan_normals"]):
+        assert np.all(np.abs(np.linalg.norm(nrm, axis=1) - 1.0) <= 8 * U)  # a handful of roundings: the division, the squares, their sum, the root
+    assert np.array_equal(g["rotations"][0], np.eye(3)) and not g["translations"][0].any()
+    assert d_max == 0.05 and float(g["epsilon"]) == 1e-3
+    s = dict(tree=cKDTree(ref))
+    kept = [[0, 0] for _ in range(3)]
+    for si, ri, R, t, rows in plain_golden_cases(g):
+        a = scan if rows is None else scan[rows]
+        assert_unambiguous(s, a, R, t, d_max, ("golden", si, ri))
+        kept[si][ri] = I.kept_pairs(a, ref, R, t, d_max, s["tree"])[0].shape[0]
+    assert kept == [list(x) for x in PLAIN_GOLDEN_KEPT] and min(min(x) for x in kept) >= 30
+    assert min(min(x) for x in kept) < 64 < 4 * 64 < max(max(x) for x in kept)
+    return kept
+
+
+def plain_golden_sums(eng, g, modes=MODE_IDS):
+    """sums[mode, state, rows] of the plain entry points (sf_icp_accumulate, sf_icp_accumulate_gicp) on the fixture's inputs, from
+    a `_Registration` of its own"""
+    out = np.zeros((len(modes), 3, 2, 40))
+    with _Resident(eng, g["scan"], g["scan_normals"], g["ref"], g["ref_normals"]) as dev:
+        for mi, mode in enumerate(modes):
+            for si, ri, R, t, rows in plain_golden_cases(g):
+                out[mi, si, ri] = dev.plain(mode, R, t, float(g["d_max"]), rows=rows, eps=float(g["epsilon"]))
+    return out
+
+
+@pytest.mark.parametrize("mode", MODE_IDS)
+def test_plain_calls_return_the_recorded_numbers_bit_for_bit(eng, mode):
+    """tests/golden/icp_plain_sums.npz holds the 40 numbers of the plain calls as the MI355X returned them from the unweighted sums
+    kernels the library had before the weighted family became its only one: 600 scan rows (three blocks) and a selection of 150
+    (partial waves) against 500 reference points, three states.  Any change of an operation, of its order or of the order of the
+    additions moves a bit here."""
+    from conftest import load_golden
+
+    g = load_golden(PLAIN_GOLDEN)
+    got = plain_golden_sums(eng, g, [mode])[0]
+    want = g["sums"][mode]
+    assert got[..., 0].tolist() == [list(x) for x in PLAIN_GOLDEN_KEPT]
+    assert np.array_equal(got, want), np.argwhere(got != want)
 
 
 # ---- 3. weight edge cases on the exact lattice ---------------------------------------------------------------------------------------

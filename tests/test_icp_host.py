@@ -275,9 +275,9 @@ def test_pairs_checks_rows_before_any_device_call():
 
 # ---- a CPU transcription of k_icp_sums: the bound passes the kernel as written and fails it when it is subtly wrong ----------------
 def transcribed_call(a, ref, nref, R, t, d_max, mode, tree, wrong=None):
-    """sf_icp_accumulate as csrc/icp.hip performs it, in NumPy: the terms of k_icp_sums per pair, then ITS order of additions --
+    """sf_icp_accumulate as csrc/icp.hip performs it, in NumPy: the terms of k_icp_sums per pair (every weight 1.0), then ITS order of additions --
     thread i + 65 536 j serially, the xor butterfly over the 64 lanes of a wave, ((w0 + w1) + w2) + w3 per block, the 256 block
-    partials one after the other, the centroids of k_icp_final in between.  `wrong` breaks one thing the way a slip in the kernel
+    partials one after the other, the centroids of k_icp_means in between.  `wrong` breaks one thing the way a slip in the kernel
     would: "sign" (px nz - pz nx for g[1]), "uncentred" (products of uncentred factors, k pbar qbar^T taken off at the end),
     "strict" (`<` for `<=` in the distance test)."""
     p = G.move(R, t, np.asarray(a, dtype=np.float64))

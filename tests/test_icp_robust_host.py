@@ -168,9 +168,9 @@ def test_weighted_right_hand_side_is_minus_half_the_gradient_of_the_cost(mode, l
 
 # ---- 4. a CPU transcription of the kernel's order of additions ---------------------------------------------------------------------------
 def transcribed_call(mode, loss, k, a, na, ref, nref, R, t, d_max, tree, eps=1e-3, wrong=None):
-    """sf_icp_accumulate_robust as csrc/icp.hip performs it, in NumPy: per pair the terms of k_robust_sums, then ITS order of
+    """sf_icp_accumulate_robust as csrc/icp.hip performs it, in NumPy: per pair the terms of k_icp_sums, then ITS order of
     additions -- thread i + 65 536 j serially, the xor butterfly over the 64 lanes of a wave, ((w0 + w1) + w2) + w3 per block, the
-    256 block partials one after the other, the weighted centroids of k_robust_final between the passes.  `wrong` breaks one thing
+    256 block partials one after the other, the weighted centroids of k_icp_means between the passes.  `wrong` breaks one thing
     the way a slip in the kernel would: "pass_a" (the weight in pass B but not in pass A: [7], [40..46] and the centroids
     unweighted), "k" (s = r2 / k for r2 / (k k)), "no_sqrt" (Huber's a = r2), "no_cutoff" (Tukey's (1 - s)^2 beyond s = 1)."""
     p = G.move(R, t, np.asarray(a, dtype=np.float64))
@@ -400,6 +400,19 @@ def test_lattice_weights_are_what_the_gpu_test_expects():
         for loss in (hub, tuk):
             w = float(S.weight(loss, d2, k)[0])
             assert math.fsum([w] * 512) == 512 * w  # the sum of 512 equal weights is exact
+
+
+def test_plain_golden_inputs():
+    """tests/golden/icp_plain_sums.npz as stored: its inputs meet the conditions the golden test places on them, and the recorded
+    counts -- the one number of the 40 a CPU can state exactly -- are the kept pairs of every case."""
+    from conftest import load_golden
+
+    g = load_golden(H.PLAIN_GOLDEN)
+    kept = H.plain_golden_input_conditions(g)
+    assert g["sums"].shape == (3, 3, 2, 40) and g["sums"].dtype == np.float64 and np.all(np.isfinite(g["sums"]))
+    assert g["sums"][..., 0].tolist() == [kept] * 3 and not g["sums"][..., 7].any()
+    for mode in H.MODE_IDS:
+        assert not g["sums"][mode][..., [c for c in S.UNUSED[mode] if c < 40]].any()
 
 
 def test_whole_run_inputs():

@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import gicp_numpy as G  # noqa: E402 -- the surface and the true motion of the parity table
 
-SUMS = ("i1_icp_sums", "i1_icp_final", "i2_gicp_sums")
+SUMS = ("i1_icp_sums", "i1_icp_means", "i1_icp_final")
 
 
 def main() -> int:

@@ -66,7 +66,7 @@ def main() -> int:
            f"Written by `tools/icp_robust_parity.py` on an MI355X ({eng.lib.sf_version().decode()}) from the measurements of",
            "`tests/test_hip_icp_robust.py` and `tests/test_icp_robust_host.py`.", "",
            "## One pass", "",
-           "One `sf_icp_accumulate_robust` call (`k_robust_sums`, `k_robust_final`) against the `math.fsum` value of each of its 48 sums as",
+           "One `sf_icp_accumulate_robust` call (`k_icp_sums`, `k_icp_means`) against the `math.fsum` value of each of its 48 sums as",
            "`tests/icp_robust_numpy.py` states them; mode 0 is centred on both sides with the weighted centroids the device formed.  An",
            "entry is the worst |sum - fsum| / (k 2^-53 sum|term|) over the 48 slots, the five losses and the three states (identity, true",
            f"motion, 0.3 rad away) at d_max = {H.D_MAX}, scale {H.K_ONE[S.POINT]} (mode 2: {H.K_ONE[S.GICP]}); the pair counts are equal in every case.",
