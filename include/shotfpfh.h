@@ -615,6 +615,31 @@ int sf_icp_accumulate_robust(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, 
                              const int64_t *sel_dev, int64_t m, const double *Rt, double d_max, int mode /* 0, 1, 2 */, double epsilon,
                              int loss /* 0 .. 4 */, double scale, double *sums /* 48 */);
 
+/* ---- the exact k-th smallest of doubles on the device, K18 (no counterpart in the reference) --------
+ * sf_select_kth: the rank-th smallest (1-based, 1 <= rank <= n) of keys_dev[0..n) (doubles on the device), by radix selection on
+ * the bit patterns: six histogram passes over the keys, no host wait in between, integer atomics only -- a call repeats bit for bit.
+ * The order is that of the patterns with the sign bit cleared, np.partition's on non-negative keys: -0.0 orders as zero, +inf
+ * above every finite value, the NaNs last.  out[4] (host):
+ *   [0] the value (a zero comes back as +0.0), [1] how many keys order below it, [2] how many order at or below it, [3] 0.
+ * SF_ERR_ARG names the offending argument in sf_last_error(): n < 1, a rank outside 1 .. n, a null pointer. */
+int sf_select_kth(sf_ctx *ctx, const double *keys_dev, int64_t n, int64_t rank, double *out /* 4 */);
+
+/* ---- trimmed ICP for all three modes, K18 (Chetverikov, Stepanov, Krsek 2002/2005; no counterpart in the reference) --------
+ * sf_icp_accumulate_robust's chain over the best-fitting share of the pairs only.  With n0 the pairs inside d_max (the gate is
+ * applied first and is unchanged) and r2 the mode's squared residual as above (mode 2's clamped term may be -0.0: it orders as zero):
+ *   rank = min(n0, max(1, (int64) ceil(trim * (double) n0))),   cut = the rank-th smallest r2 (sf_select_kth's order),
+ * a pair is USED iff it is inside d_max and r2 <= cut -- every tie at the cut is used, so the used set does not depend on the
+ * order of the pairs and may exceed the rank.  Both sums passes and both folds run over the used pairs; a robust weight is taken
+ * over them from the same r2.  Between the search and pass A the chain gains a key pass and the selection; rank and cut are formed
+ * and read on the device, and the call still has one host wait, at its end.  trim in (0, 1].
+ * sums[48] (host): sf_icp_accumulate_robust's layout with [0] the USED pair count, and
+ *   [37] n0, [38] the rank, [47] the cut.
+ * With trim == 1.0 no selection is launched: [0..36] and [40..46] are sf_icp_accumulate_robust's bit for bit, [37] = [38] = [0]
+ * and [47] = 0.  With no pair inside d_max everything is zero.  SF_ERR_ARG names the offending argument in sf_last_error(). */
+int sf_icp_accumulate_trimmed(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev /* NULL unless mode 2 */,
+                              const int64_t *sel_dev, int64_t m, const double *Rt, double d_max, int mode /* 0, 1, 2 */, double epsilon,
+                              int loss /* 0 .. 4 */, double scale, double trim /* in (0, 1] */, double *sums /* 48 */);
+
 /* ---- multi-GPU: RCCL over xGMI (no counterpart in the reference) --------------------------
  * One process per GPU.  Rank 0 calls sf_comm_unique_id, ships the 128 bytes to the other ranks by
  * any host channel, then every rank calls sf_comm_init.  sf_comm_allgather gathers

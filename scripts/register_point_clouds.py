@@ -73,6 +73,11 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="--icp-loss: the loss's scale in the residual's unit, a few sigma of the noise")
     p.add_argument("--icp-loss-scale-start", type=float, default=None, metavar="K0",
                    help="--icp-loss: the scale of the first iteration, divided by 1.4 per iteration down to K (default: --icp-dmax)")
+    p.add_argument("--icp-overlap", type=float, default=None, metavar="X",
+                   help="trimmed ICP: fit only the best-fitting share X, in (0, 1], of the pairs within --icp-dmax -- roughly how much "
+                        "of the scan the reference also sees (combines with --icp-loss)")
+    p.add_argument("--icp-overlap-anneal", type=int, default=10, metavar="N",
+                   help="--icp-overlap: the share comes down from 1 to X over the first N iterations (0: X throughout)")
     p.add_argument("--icp-dmax", type=float, default=0.5), p.add_argument("--icp-voxel", type=float, default=0.2)
     p.add_argument("--icp-max-iter", type=int, default=50), p.add_argument("--icp-rms", type=float, default=1e-3)
     p.add_argument("--metric-threshold", type=float, default=0.1)
@@ -82,6 +87,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--icp-loss needs --icp-loss-scale")
     if args.icp_loss is None and (args.icp_loss_scale is not None or args.icp_loss_scale_start is not None):
         p.error("--icp-loss-scale and --icp-loss-scale-start need --icp-loss")
+    if args.icp_overlap is not None and not 0.0 < args.icp_overlap <= 1.0:
+        p.error("--icp-overlap must lie in (0, 1]")
+    if args.icp_overlap_anneal < 0:
+        p.error("--icp-overlap-anneal must not be negative")
     return args
 
 
@@ -119,7 +128,9 @@ def main(argv=None) -> int:
                                                        max_iter=args.icp_max_iter, rms_threshold=args.icp_rms,
                                                        disable_progress_bar=True, gicp_neighbors=args.gicp_neighbors,
                                                        gicp_epsilon=args.gicp_epsilon, robust_loss=args.icp_loss,
-                                                       robust_scale=args.icp_loss_scale, robust_scale_start=args.icp_loss_scale_start)
+                                                       robust_scale=args.icp_loss_scale, robust_scale_start=args.icp_loss_scale_start,
+                                                       trim_overlap=args.icp_overlap,
+                                                       trim_anneal_iterations=args.icp_overlap_anneal)
         logging.info(f"ICP rms {rms:.3e}, converged: {bool(converged)}\n{transformation}")
         if args.write:
             outputs.append((f"{args.write}_icp.ply", transformation))

@@ -22,10 +22,14 @@
 //     system of sum r^T M r is left for the host (sf_icp_accumulate_gicp);
 //   K17, robust losses for all three modes (no counterpart in the reference): every kept pair has a weight psi(r) / r of its
 //     residual (Huber, Cauchy, Geman-McClure, Tukey), and the weighted sums are left for the host (sf_icp_accumulate_robust).
+//   K18, trimmed ICP for all three modes (no counterpart in the reference): a key pass writes every pair's squared residual, the radix
+//     selection of select.hip finds the order statistic that bounds the best-fitting share of them, and both sums passes leave out the
+//     pairs beyond that cut (sf_icp_accumulate_trimmed).  The residual is formed by ONE function, icp_pair_residual, for all of them.
 // The two plain entry points are the chain with loss none: every weight is 1.0, w * term is the term, and they return the first 40
 // of its 48 numbers with [7] (sum w) cleared.
 #include "common.h"
 #include "device_util.h"
+#include "select.h"
 
 extern "C" sf_nbrs *sf_knn_search(sf_ctx *ctx, sf_cloud *c, const double *queries, int64_t m, int k, int flags);
 extern "C" void sf_nbrs_free(sf_ctx *ctx, sf_nbrs *nb);
@@ -109,6 +113,90 @@ __device__ inline double robust_weight(int loss, double r2, double k, double kk)
     return loss == 2 ? c : c * c;
 }
 
+// One pair of the chain: slot i's moved scan point p, its nearest reference point (x, y, z) with normal n, d = q - p, d2, and the
+// mode's squared residual r2 with what PASS 1 needs beside it (h; the Mahalanobis term, M and u = M d).  Formed HERE and nowhere else:
+// the key pass of the trimmed chain (K18) and both sums passes call this one function, so their r2 agree bit for bit.
+struct icp_pair {
+    double px, py, pz, x, y, z, nx, ny, nz, dx, dy, dz, d2, h, maha, r2, M[3][3], u[3];
+};
+
+// false: the pair is outside d_max (r2 and what follows d2 are then not formed)
+template <int MODE>
+__device__ inline bool icp_pair_residual(int64_t i, const double *__restrict__ qx, const double *__restrict__ qy,
+                                         const double *__restrict__ qz, const int32_t *__restrict__ idx,
+                                         const int32_t *__restrict__ qrow, const double *__restrict__ rec,
+                                         const double *__restrict__ nrm, const int64_t *__restrict__ sel, bool turned,
+                                         const double (&R)[9], double c, double d_max, icp_pair &P)
+{
+    const double px = qx[i], py = qy[i], pz = qz[i];
+    double x, y, z, nx = 0, ny = 0, nz = 0;
+    if (MODE == 0) sf_load_xyz(rec, idx[i], x, y, z);
+    else sf_load_pn(rec, idx[i], x, y, z, nx, ny, nz);
+    const double dx = x - px, dy = y - py, dz = z - pz;
+    const double d2 = (dx * dx + dy * dy) + dz * dz;
+    if (!(sqrt(d2) <= d_max)) return false; // KDTree.query returns sqrt(d2); `distances <= d_max` (icp.py:64, 112, 164)
+    P.px = px; P.py = py; P.pz = pz; P.x = x; P.y = y; P.z = z; P.nx = nx; P.ny = ny; P.nz = nz;
+    P.dx = dx; P.dy = dy; P.dz = dz; P.d2 = d2;
+    P.r2 = d2; P.h = 0.0; P.maha = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        P.u[a] = 0.0;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) P.M[a][b] = 0.0;
+    }
+    if (MODE == 1) {
+        P.h = (dx * nx + dy * ny) + dz * nz;
+        P.r2 = P.h * P.h;
+    }
+    if (MODE == 2) {
+        const int64_t row = qrow ? (int64_t)qrow[i] : i;
+        const int64_t j = sel ? sel[row] : row;
+        const double ax = nrm[3 * j], ay = nrm[3 * j + 1], az = nrm[3 * j + 2];
+        double m0 = ax, m1 = ay, m2 = az;
+        if (turned) {
+            m0 = (ax * R[0] + ay * R[1]) + az * R[2];
+            m1 = (ax * R[3] + ay * R[4]) + az * R[5];
+            m2 = (ax * R[6] + ay * R[7]) + az * R[8];
+        }
+        const double s00 = 2.0 - c * (nx * nx + m0 * m0), s11 = 2.0 - c * (ny * ny + m1 * m1), s22 = 2.0 - c * (nz * nz + m2 * m2);
+        const double s01 = -(c * (nx * ny + m0 * m1)), s02 = -(c * (nx * nz + m0 * m2)), s12 = -(c * (ny * nz + m1 * m2));
+        const double a00 = s11 * s22 - s12 * s12, a01 = s02 * s12 - s01 * s22, a02 = s01 * s12 - s02 * s11;
+        const double a11 = s00 * s22 - s02 * s02, a12 = s01 * s02 - s00 * s12, a22 = s00 * s11 - s01 * s01;
+        const double det = (s00 * a00 + s01 * a01) + s02 * a02;
+        const double inv = 1.0 / det;
+        P.M[0][0] = a00 * inv; P.M[0][1] = P.M[1][0] = a01 * inv; P.M[0][2] = P.M[2][0] = a02 * inv;
+        P.M[1][1] = a11 * inv; P.M[1][2] = P.M[2][1] = a12 * inv; P.M[2][2] = a22 * inv;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) P.u[b] = (P.M[b][0] * dx + P.M[b][1] * dy) + P.M[b][2] * dz;
+        P.maha = (dx * P.u[0] + dy * P.u[1]) + dz * P.u[2];
+        P.r2 = P.maha < 0.0 ? 0.0 : P.maha;
+    }
+    return true;
+}
+
+// The key pass of the trimmed chain (K18): one key per slot for the selection (select.hip), r2's bit pattern for a pair inside d_max
+// and the all-ones pattern, which orders last, for a slot outside it.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_icp_keys(const double *__restrict__ qx, const double *__restrict__ qy,
+                                                  const double *__restrict__ qz, const int32_t *__restrict__ idx,
+                                                  const int32_t *__restrict__ qrow, const double *__restrict__ rec,
+                                                  const double *__restrict__ nrm, const int64_t *__restrict__ sel,
+                                                  const double *__restrict__ Rt, int64_t m, double d_max, double epsilon,
+                                                  uint64_t *__restrict__ keys)
+{
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (MODE == 2 && Rt) {
+#pragma unroll
+        for (int v = 0; v < 9; ++v) R[v] = Rt[v];
+    }
+    const double c = 1.0 - epsilon;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        icp_pair P;
+        const bool kept = icp_pair_residual<MODE>(i, qx, qy, qz, idx, qrow, rec, nrm, sel, Rt != nullptr, R, c, d_max, P);
+        keys[i] = kept ? (uint64_t)__double_as_longlong(P.r2) : ~0ull;
+    }
+}
+
 // Both passes of the three modes, with a weight w per kept pair; every line one rounding per operation, left to right, which
 // tests/icp_numpy.py, tests/gicp_numpy.py and tests/icp_robust_numpy.py repeat operation by operation.
 //   PASS 0 (15): inlier count, sum of inlier points p, sum of their neighbours q (7), then w, w p (3), w q (3), w r2
@@ -126,9 +214,10 @@ __device__ inline double robust_weight(int loss, double r2, double k, double kk)
 //     H   = J^T M J = [[T, Q], [Q^T, M]] (upper triangle, 21),  g = J^T M r = [p x u; u] (6),  r.u,  |r|^2  with J = [-[p]x, I]
 //           A zero normal makes its dyad vanish (C = I); the sign of a normal cancels in the dyad.
 // The pair's squared residual r2 is d2 (MODE 0), h h (MODE 1) or the Mahalanobis term (r0 u0 + r1 u1) + r2 u2 clamped at 0 (MODE 2),
-// and both passes form w from it by the same operations, so they get the same bits.  PASS 1 multiplies every fit term by w (one
-// more rounding); the residual sums the host reports as rms stay unweighted: d2 (MODE 0: [9], MODE 2: [28]), |h| (MODE 1: [27]),
-// the Mahalanobis term as formed (MODE 2: [27]).
+// formed by icp_pair_residual above, and both passes form w from it by the same operations, so they get the same bits.  PASS 1
+// multiplies every fit term by w (one more rounding); the residual sums the host reports as rms stay unweighted: d2 (MODE 0: [9],
+// MODE 2: [28]), |h| (MODE 1: [27]), the Mahalanobis term as formed (MODE 2: [27]).
+// Given `cut` (K18, the trimmed chain) both passes leave out the pairs with r2 above cut[0], a number the selection left on the device.
 // With w = 1 (loss none, or Huber with k above every residual) w * term is the term, bit for bit: the plain entry points.
 template <int PASS, int MODE>
 __global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx, const double *__restrict__ qy,
@@ -137,7 +226,7 @@ __global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx,
                                                   const double *__restrict__ nrm, const int64_t *__restrict__ sel,
                                                   const double *__restrict__ Rt, int64_t m, double d_max, double epsilon, int loss,
                                                   double k, const double *__restrict__ mean /* 6, PASS 1 MODE 0 */,
-                                                  double *__restrict__ partial)
+                                                  const double *__restrict__ cut /* null: no trimming */, double *__restrict__ partial)
 {
     constexpr int NV = PASS == 0 ? 15 : (MODE == 0 ? 10 : (MODE == 1 ? 28 : 29));
     double acc[NV];
@@ -155,42 +244,16 @@ __global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx,
         for (int v = 0; v < 9; ++v) R[v] = Rt[v];
     }
     const double c = 1.0 - epsilon;
+    const bool trimmed = cut != nullptr;
+    const double r2_max = trimmed ? cut[0] : 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-        const double px = qx[i], py = qy[i], pz = qz[i];
-        double x, y, z, nx = 0, ny = 0, nz = 0;
-        if (MODE == 0) sf_load_xyz(rec, idx[i], x, y, z);
-        else sf_load_pn(rec, idx[i], x, y, z, nx, ny, nz);
-        const double dx = x - px, dy = y - py, dz = z - pz;
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
-        if (!(sqrt(d2) <= d_max)) continue; // KDTree.query returns sqrt(d2); `distances <= d_max` (icp.py:64, 112, 164)
-        double r2 = d2, h = 0.0, maha = 0.0, M[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, u[3] = {0, 0, 0};
-        if (MODE == 1) {
-            h = (dx * nx + dy * ny) + dz * nz;
-            r2 = h * h;
-        }
-        if (MODE == 2) {
-            const int64_t row = qrow ? (int64_t)qrow[i] : i;
-            const int64_t j = sel ? sel[row] : row;
-            const double ax = nrm[3 * j], ay = nrm[3 * j + 1], az = nrm[3 * j + 2];
-            double m0 = ax, m1 = ay, m2 = az;
-            if (Rt) {
-                m0 = (ax * R[0] + ay * R[1]) + az * R[2];
-                m1 = (ax * R[3] + ay * R[4]) + az * R[5];
-                m2 = (ax * R[6] + ay * R[7]) + az * R[8];
-            }
-            const double s00 = 2.0 - c * (nx * nx + m0 * m0), s11 = 2.0 - c * (ny * ny + m1 * m1), s22 = 2.0 - c * (nz * nz + m2 * m2);
-            const double s01 = -(c * (nx * ny + m0 * m1)), s02 = -(c * (nx * nz + m0 * m2)), s12 = -(c * (ny * nz + m1 * m2));
-            const double a00 = s11 * s22 - s12 * s12, a01 = s02 * s12 - s01 * s22, a02 = s01 * s12 - s02 * s11;
-            const double a11 = s00 * s22 - s02 * s02, a12 = s01 * s02 - s00 * s12, a22 = s00 * s11 - s01 * s01;
-            const double det = (s00 * a00 + s01 * a01) + s02 * a02;
-            const double inv = 1.0 / det;
-            M[0][0] = a00 * inv; M[0][1] = M[1][0] = a01 * inv; M[0][2] = M[2][0] = a02 * inv;
-            M[1][1] = a11 * inv; M[1][2] = M[2][1] = a12 * inv; M[2][2] = a22 * inv;
-#pragma unroll
-            for (int b = 0; b < 3; ++b) u[b] = (M[b][0] * dx + M[b][1] * dy) + M[b][2] * dz;
-            maha = (dx * u[0] + dy * u[1]) + dz * u[2];
-            r2 = maha < 0.0 ? 0.0 : maha;
-        }
+        icp_pair P;
+        if (!icp_pair_residual<MODE>(i, qx, qy, qz, idx, qrow, rec, nrm, sel, Rt != nullptr, R, c, d_max, P)) continue;
+        if (trimmed && !(P.r2 <= r2_max)) continue; // K18: the pairs beyond the cut are not used; ties at the cut are
+        const double px = P.px, py = P.py, pz = P.pz, x = P.x, y = P.y, z = P.z, nx = P.nx, ny = P.ny, nz = P.nz;
+        const double d2 = P.d2, h = P.h, maha = P.maha, r2 = P.r2;
+        const double(&M)[3][3] = P.M;
+        const double(&u)[3] = P.u;
         const double w = robust_weight(loss, r2, k, kk);
         if constexpr (PASS == 0) {
             acc[0] += 1.0;
@@ -283,8 +346,11 @@ extern "C" int sf_transform_points(sf_ctx *ctx, double *pts_dev, int64_t n, cons
 // The chain of the three entry points, which have checked their arguments, set the device and returned for m == 0: move the rows,
 // find their nearest reference points, both sums passes with their folds, and the 48 numbers (layout in include/shotfpfh.h) back
 // in `sums`.  `who` names the entry point in the empty-reference error.
+// K18: with trim < 1 a key pass and the selection (select.hip) come between the search and pass A, queued like the rest; the cut stays
+// on the device, where both sums passes read it, and n0, the rank and the cut come back behind the 48 numbers in the same copy.
 static int icp_chain(const char *who, sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev, const int64_t *sel_dev,
-                     int64_t m, const double *Rt, double d_max, int mode, double epsilon, int loss, double scale, double *sums)
+                     int64_t m, const double *Rt, double d_max, int mode, double epsilon, int loss, double scale, double *sums,
+                     double trim = 1.0)
 {
     if (ref->n < 1) { sf_set_error("%s: empty reference cloud", who); return SF_ERR_ARG; }
     sf_pool_guard tmp(ctx);
@@ -308,10 +374,24 @@ static int icp_chain(const char *who, sf_ctx *ctx, sf_cloud *ref, const double *
     // the k-NN lists are in PROCESSING order (queries sorted by cell): sums do not care, and qx / qy / qz follow it
     const dim3 grid(ICP_BLOCKS), block(256);
     const int32_t *qrow = (const int32_t *)nb->qrow;
-    const double *no_mean = nullptr;
+    const double *no_mean = nullptr, *cut = nullptr;
+    const bool trimmed = trim < 1.0;
+    if (trimmed) {
+        uint64_t *keys = nullptr;
+        SF_CHECK(tmp.alloc(&keys, (size_t)m));
+#define SF_ICP_KEYS(MODE)                                                                                                            \
+    SF_LAUNCH(ctx, "i2_icp_keys", (k_icp_keys<MODE>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, qrow, ref->rec, nrm_dev, sel_dev, \
+              (const double *)dRt, m, d_max, epsilon, keys)
+        if (mode == 0) { SF_ICP_KEYS(0); }
+        else if (mode == 1) { SF_ICP_KEYS(1); }
+        else { SF_ICP_KEYS(2); }
+#undef SF_ICP_KEYS
+        SF_CHECK(sf_select_launch(ctx, keys, m, 0, trim, dout + 48)); // [48] the cut, [52] n0, [53] the rank
+        cut = dout + 48;
+    }
 #define SF_ICP_PASS(PASS, MODE, mean)                                                                                                \
     SF_LAUNCH(ctx, "i1_icp_sums", (k_icp_sums<PASS, MODE>), grid, block, nb->qx, nb->qy, nb->qz, nb->idx, qrow, ref->rec, nrm_dev,    \
-              sel_dev, (const double *)dRt, m, d_max, epsilon, loss, scale, mean, partial)
+              sel_dev, (const double *)dRt, m, d_max, epsilon, loss, scale, mean, cut, partial)
     if (mode == 0) { SF_ICP_PASS(0, 0, no_mean); }
     else if (mode == 1) { SF_ICP_PASS(0, 1, no_mean); }
     else { SF_ICP_PASS(0, 2, no_mean); }
@@ -322,8 +402,11 @@ static int icp_chain(const char *who, sf_ctx *ctx, sf_cloud *ref, const double *
 #undef SF_ICP_PASS
     SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, mode == 0 ? 10 : (mode == 1 ? 28 : 29),
               dout + 8, (double *)nullptr);
-    SF_HIP(hipMemcpyAsync(sums, dout, 48 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    double all[56];
+    SF_HIP(hipMemcpyAsync(all, dout, (trimmed ? 56 : 48) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 48; ++i) sums[i] = all[i];
+    if (trimmed) { sums[37] = all[52]; sums[38] = all[53]; sums[47] = all[48]; }
     return SF_OK;
 }
 
@@ -382,4 +465,30 @@ extern "C" int sf_icp_accumulate_robust(sf_ctx *ctx, sf_cloud *ref, const double
     for (int i = 0; i < 48; ++i) sums[i] = 0.0;
     if (!m) return SF_OK;
     return icp_chain("sf_icp_accumulate_robust", ctx, ref, pts_dev, nrm_dev, sel_dev, m, Rt, d_max, mode, epsilon, loss, scale, sums);
+}
+
+// K18: trimmed ICP, the chain over the best-fitting share of the pairs inside d_max (sums[48], layout in include/shotfpfh.h)
+extern "C" int sf_icp_accumulate_trimmed(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev, const int64_t *sel_dev,
+                                         int64_t m, const double *Rt, double d_max, int mode, double epsilon, int loss, double scale,
+                                         double trim, double *sums)
+{
+    const char *bad = nullptr;
+    if (!ctx) bad = "ctx";
+    else if (!ref) bad = "ref";
+    else if (!pts_dev) bad = "pts_dev";
+    else if (!sums) bad = "sums";
+    else if (m < 0) bad = "m (negative)";
+    else if (mode < 0 || mode > 2) bad = "mode (0 point to point, 1 point to plane, 2 generalized)";
+    else if (mode == 2 && !nrm_dev) bad = "nrm_dev (mode 2 needs the scan's normals)";
+    else if (mode == 2 && !(epsilon > 0.0 && epsilon <= 1.0)) bad = "epsilon (must lie in (0, 1])";
+    else if (loss < 0 || loss > 4) bad = "loss (0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey)";
+    else if (!(scale > 0.0 && scale < INFINITY)) bad = "scale (must be positive and finite)";
+    else if (!(trim > 0.0 && trim <= 1.0)) bad = "trim (must lie in (0, 1])";
+    if (bad) { sf_set_error("sf_icp_accumulate_trimmed: bad argument %s", bad); return SF_ERR_ARG; }
+    SF_HIP(hipSetDevice(ctx->device));
+    for (int i = 0; i < 48; ++i) sums[i] = 0.0;
+    if (!m) return SF_OK;
+    SF_CHECK(icp_chain("sf_icp_accumulate_trimmed", ctx, ref, pts_dev, nrm_dev, sel_dev, m, Rt, d_max, mode, epsilon, loss, scale, sums, trim));
+    if (trim == 1.0) sums[37] = sums[38] = sums[0]; // no selection: every pair inside d_max is used, and the cut stays 0
+    return SF_OK;
 }

@@ -21,6 +21,11 @@ M = (C_b + R C_a R^T)^-1, and the device call (`sf_icp_accumulate_gicp`, the sam
 same small systems and anneals the loss's scale from `scale_start` down to `scale`, the graduated scheme of
 `fast_global_registration`.  From a coarse start a fixed small scale is no better than no loss at all, so the annealing is part of it.
 
+`icp_trimmed` (K18) runs any of the three, with or without a loss, as trimmed ICP (Chetverikov, Stepanov, Krsek 2002/2005): the device
+call (`sf_icp_accumulate_trimmed`) finds the exact order statistic of the residuals of the pairs inside `d_max` that bounds their
+best-fitting share (a radix selection, csrc/select.hip) and sums over the pairs up to it only.  The share comes down from 1 to
+`overlap` over the first iterations: a fixed share from a coarse start is worse than no trimming, the same lesson as the scale's.
+
 Deviation, on purpose: the reference's `icp_point_to_point` computes its RMS from `ref[neighbors]` (all queried points,
 shape (n, 1, 3)) instead of `ref[inliers_neighbors]` (icp.py:122-124); the broadcast yields an array, and formatting it for
 the progress bar raises TypeError on the first iteration, so that function cannot run there at all.  Here the RMS is taken
@@ -49,6 +54,7 @@ __all__ = [
     "icp_point_to_plane",
     "icp_generalized",
     "icp_robust",
+    "icp_trimmed",
     "compute_point_to_point_error",
     "nearest_within",
 ]
@@ -83,6 +89,8 @@ class _PairSums:
             self.sum_w = float(raw[7])                # sum w
             self.sum_wp, self.sum_wq = raw[40:43], raw[43:46]
             self.sum_wr2 = float(raw[46])             # sum w r2 (r2: the mode's squared residual)
+            # a trimmed pass (sf_icp_accumulate_trimmed): `count` is the USED pairs; zero otherwise
+            self.inside, self.rank, self.cut = int(raw[37]), int(raw[38]), float(raw[47])
         self.count = int(raw[0])
         self.sum_p, self.sum_q = raw[1:4], raw[4:7]
         if mode == _POINT:
@@ -169,9 +177,10 @@ class _Registration:
             self.normals = self.engine.empty((max(self.n, 1), 3)).from_host(nrm if self.n else np.zeros((1, 3)))
 
     def pairs(self, mode: int, d_max: float, moved_by: Optional[RigidTransform] = None, rows=None,
-              epsilon: float = 1e-3, loss: Optional[int] = None, scale: float = 1.0) -> _PairSums:
+              epsilon: float = 1e-3, loss: Optional[int] = None, scale: float = 1.0, trim: float = 1.0) -> _PairSums:
         """Inlier-pair sums of the working points (all of them, or the given `rows`) after `moved_by`; with a `loss` (0 .. 4,
-        `LOSSES`) the 48 weighted sums of sf_icp_accumulate_robust at `scale`."""
+        `LOSSES`) the 48 weighted sums of sf_icp_accumulate_robust at `scale`; with a `trim` below 1 the 48 sums of
+        sf_icp_accumulate_trimmed over that share of the pairs (a trim of 1.0 is the call without one)."""
         m, sel = self.n, None
         if rows is not None:
             rows = _checked_rows(rows, self.n)
@@ -186,11 +195,15 @@ class _Registration:
         rt = None if moved_by is None else np.ascontiguousarray(moved_by.as_row12())
         if mode == _GICP and self.normals is None:
             raise ValueError("generalized ICP needs the normals of the working points")
-        raw = np.zeros(40 if loss is None else 48)
+        trimmed = float(trim) != 1.0
+        raw = np.zeros(40 if loss is None and not trimmed else 48)
         head = (self.engine.h, self.ref.h, self.points.ptr)
         rows_and_motion = (sel, m, None if rt is None else rt.ctypes.data_as(C.c_void_p), float(d_max))
         out = raw.ctypes.data_as(C.c_void_p)
-        if loss is not None:
+        if trimmed:
+            name, args = "sf_icp_accumulate_trimmed", (*head, self.normals.ptr if mode == _GICP else None, *rows_and_motion, int(mode),
+                                                       float(epsilon), int(loss or 0), float(scale), float(trim), out)
+        elif loss is not None:
             name, args = "sf_icp_accumulate_robust", (*head, self.normals.ptr if mode == _GICP else None, *rows_and_motion, int(mode),
                                                       float(epsilon), int(loss), float(scale), out)
         elif mode == _GICP:  # without a loss the plain entry points and their 40 numbers
@@ -382,16 +395,28 @@ def annealed_scale(scale: float, scale_start: float, division_factor: float, ite
         return scale
 
 
+def trimmed_overlap(overlap: float, anneal_iterations: int, iteration: int) -> float:
+    """The share of the pairs iteration i of trimmed ICP uses: max(overlap, 1 - (1 - overlap) i / anneal_iterations), from 1 down to
+    `overlap` in `anneal_iterations` equal steps; `anneal_iterations=0` uses `overlap` throughout."""
+    if anneal_iterations <= 0:
+        return overlap
+    return max(overlap, 1.0 - (1.0 - overlap) * iteration / anneal_iterations)
+
+
 def _refine_robust(reg: _Registration, start: RigidTransform, mode: int, d_max: float, loss: int, scale: float, scale_start: float,
-                   division_factor: float, max_iter: int, rms_threshold: float, epsilon: float, step_tolerance: float):
+                   division_factor: float, max_iter: int, rms_threshold: float, epsilon: float, step_tolerance: float,
+                   overlap: float = 1.0, anneal_iterations: int = 0):
     """The loop of `_refine` with a weight per pair: the scale of iteration i is `annealed_scale(.., i)`, the residual reported is
-    the mode's unweighted one, and a small step stops the run only once the scale has come down to `scale`."""
+    the mode's unweighted one, and a small step stops the run only once the scale has come down to `scale`.  With an `overlap`
+    below 1 (K18) iteration i fits the share `trimmed_overlap(.., i)` of the pairs, the residual is over the pairs used, and a
+    small step stops the run only once the share, too, has come down to `overlap`."""
     total, rms, small_step = start, 0.0, False
     fit = {_POINT: _weighted_rigid_fit, _PLANE: _plane_fit, _GICP: _gicp_fit}[mode]
     try:
         for i in range(max_iter):
             k = annealed_scale(scale, scale_start, division_factor, i)
-            found = reg.pairs(mode, d_max, moved_by=total, epsilon=epsilon, loss=loss, scale=k)
+            share = trimmed_overlap(overlap, anneal_iterations, i)
+            found = reg.pairs(mode, d_max, moved_by=total, epsilon=epsilon, loss=loss, scale=k, trim=share)
             found.require_weight(k)
             step = fit(found)
             total = step @ total
@@ -401,7 +426,7 @@ def _refine_robust(reg: _Registration, start: RigidTransform, mode: int, d_max: 
             else:
                 rms = found.abs_h / found.count if mode == _PLANE else float(np.sqrt(found.sq_dist / found.count))
                 size = float(np.abs(found.step).max())
-            small_step = k == scale and size < step_tolerance
+            small_step = k == scale and share == overlap and size < step_tolerance
             if rms < rms_threshold:
                 logging.info("RMS threshold reached.")
                 break
@@ -474,6 +499,81 @@ def icp_robust(
     try:
         return _refine_robust(reg, transformation_init, kind, d_max, LOSSES[loss], float(scale), float(scale_start),
                               float(division_factor), max_iter, rms_threshold, epsilon, step_tolerance)
+    finally:
+        reg.close()
+
+
+def icp_trimmed(
+    scan: npt.NDArray[np.float64],
+    ref: npt.NDArray[np.float64],
+    transformation_init: RigidTransform,
+    d_max: float,
+    *,
+    overlap: float,
+    anneal_iterations: int = 10,
+    mode: str = "point_to_plane",
+    loss: str = "none",
+    scale: Optional[float] = None,
+    scale_start: Optional[float] = None,
+    division_factor: float = 1.4,
+    ref_normals: Optional[npt.NDArray[np.float64]] = None,
+    scan_normals: Optional[npt.NDArray[np.float64]] = None,
+    k_normals: int = 20,
+    epsilon: float = 1e-3,
+    voxel_size: float = 0.2,
+    max_iter: int = 50,
+    rms_threshold: float = 1e-2,
+    step_tolerance: float = 1e-9,
+) -> tuple[RigidTransform, float, bool]:
+    """Trimmed point-to-point, point-to-plane or generalized ICP, K18 (Chetverikov, Stepanov, Krsek 2002/2005): every iteration
+    fits only the best-fitting share of its pairs, those whose squared residual -- the mode's own, as in `icp_robust` -- is at most
+    the ceil(share * n0)-th smallest of the n0 pairs within `d_max`, ties at that value included.  `overlap` in (0, 1] is that
+    share: roughly how much of the scan the reference also sees.  It is a share of the pairs INSIDE `d_max`; with `d_max = inf`
+    every scan point has a pair and it is Chetverikov's share of the scan.  It needs no scale and no unit.
+    Iteration i uses max(overlap, 1 - (1 - overlap) i / anneal_iterations): from a coarse start what the reference does not have
+    may fit better than what it has, and a fixed share is then worse than no trimming; `anneal_iterations=0` switches the
+    annealing off.  An overestimated overlap buys little; point-to-point gains least from trimming (README, K18).
+    A `loss` other than "none" weights the pairs used as `icp_robust` does and needs its `scale`; the other arguments are
+    `icp_robust`'s.  Returns (transform, rms, converged) with the mode's own rms over the pairs USED by the last fit; converged
+    means rms < rms_threshold, or a step below `step_tolerance` once the share has reached `overlap` (and the scale `scale`).
+    `overlap=1.0` with loss "none" returns what the plain function of the mode returns."""
+    if mode not in _MODES:
+        raise ValueError(f"mode={mode!r}: expected one of {sorted(_MODES)}")
+    if loss not in LOSSES:
+        raise ValueError(f"loss={loss!r}: expected one of {sorted(LOSSES)}")
+    if overlap is None or not 0.0 < float(overlap) <= 1.0:
+        raise ValueError(f"overlap={overlap!r} must lie in (0, 1]")
+    if int(anneal_iterations) != anneal_iterations or anneal_iterations < 0:
+        raise ValueError(f"anneal_iterations={anneal_iterations!r} must be a non-negative integer (0 switches the annealing off)")
+    if loss == "none":
+        scale = scale_start = 1.0  # no weight looks at it
+    elif scale is None or not 0.0 < float(scale) < math.inf:
+        raise ValueError(f"scale={scale!r} must be positive and finite (loss={loss!r} needs one)")
+    scale_start = d_max if scale_start is None else scale_start
+    if not 0.0 < float(scale_start) < math.inf:
+        raise ValueError(f"scale_start={scale_start!r} must be positive and finite (it defaults to d_max)")
+    if not 1.0 < float(division_factor) < math.inf:
+        raise ValueError(f"division_factor={division_factor!r} must be greater than 1 (scale_start=scale switches the annealing off)")
+    if not 0.0 < epsilon <= 1.0:
+        raise ValueError(f"epsilon={epsilon} must lie in (0, 1]")
+    if not step_tolerance >= 0.0:
+        raise ValueError(f"step_tolerance={step_tolerance} must not be negative")
+    scan, ref = np.asarray(scan, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    for name, a in (("scan", scan), ("ref", ref)):
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name}: expected an (N, 3) array, got shape {a.shape}")
+    kind = _MODES[mode]
+    if kind == _PLANE and ref_normals is None:
+        raise ValueError("mode='point_to_plane' needs ref_normals")
+    if kind == _GICP:
+        scan_normals, ref_normals = _both_normals(scan, ref, scan_normals, ref_normals, k_normals)
+    keep = grid_subsampling(scan, voxel_size)
+    reg = _Registration(scan[keep], ref, ref_normals if kind != _POINT else None,
+                        scan_normals=scan_normals[keep] if kind == _GICP else None)
+    try:
+        return _refine_robust(reg, transformation_init, kind, d_max, LOSSES[loss], float(scale), float(scale_start),
+                              float(division_factor), max_iter, rms_threshold, epsilon, step_tolerance, float(overlap),
+                              int(anneal_iterations))
     finally:
         reg.close()
 

@@ -19,7 +19,7 @@ from . import keypoint_selection as _ks
 from .core import RigidTransform
 from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor
 from .helpers import write_ply
-from .icp import icp_generalized, icp_point_to_plane, icp_point_to_point, icp_robust, nearest_within
+from .icp import icp_generalized, icp_point_to_plane, icp_point_to_point, icp_robust, icp_trimmed, nearest_within
 from .matching import (
     basic_matching,
     double_matching_with_rejects,
@@ -264,11 +264,24 @@ class RegistrationPipeline:
                 d_max: float, voxel_size: float = 0.2, max_iter: int = 30, rms_threshold: float = 1e-2,
                 disable_progress_bar: bool = False, gicp_neighbors: int = 20,
                 gicp_epsilon: float = 1e-3, robust_loss: Optional[str] = None, robust_scale: Optional[float] = None,
-                robust_scale_start: Optional[float] = None) -> tuple[RigidTransform, float, bool]:
+                robust_scale_start: Optional[float] = None, trim_overlap: Optional[float] = None,
+                trim_anneal_iterations: int = 10) -> tuple[RigidTransform, float, bool]:
         """"generalized" (K16, no counterpart in the reference): plane-to-plane ICP with the pipeline's reference normals and
         scan normals from `gicp_neighbors` neighbours of the full scan (the scan's stored normals when it has them).
         `robust_loss` ("huber", "cauchy", "geman_mcclure", "tukey", "none"; K17) runs the chosen `icp_type` through `icp_robust` with
-        the loss's scale `robust_scale`, annealed from `robust_scale_start` (`d_max` unless given); None is the call of before."""
+        the loss's scale `robust_scale`, annealed from `robust_scale_start` (`d_max` unless given); None is the call of before.
+        `trim_overlap` (K18) runs it through `icp_trimmed`, fitting only that share of the pairs within `d_max`, annealed from 1 over
+        `trim_anneal_iterations` iterations; it combines with `robust_loss`.  None is the call of before."""
+        if trim_overlap is not None:
+            if robust_loss not in (None, "none") and robust_scale is None:
+                raise ValueError(f"robust_loss={robust_loss!r} needs robust_scale, the loss's scale in the residual's unit")
+            if robust_loss is None and (robust_scale is not None or robust_scale_start is not None):
+                raise ValueError("robust_scale and robust_scale_start need a robust_loss")
+            return icp_trimmed(self.scan, self.ref, transformation_init, d_max, overlap=trim_overlap,
+                               anneal_iterations=trim_anneal_iterations, mode=icp_type, loss=robust_loss or "none", scale=robust_scale,
+                               scale_start=robust_scale_start, ref_normals=self.ref_normals,
+                               scan_normals=self.scan_normals if icp_type == "generalized" else None, k_normals=gicp_neighbors,
+                               epsilon=gicp_epsilon, voxel_size=voxel_size, max_iter=max_iter, rms_threshold=rms_threshold)
         if robust_loss is not None:
             if robust_scale is None:
                 raise ValueError(f"robust_loss={robust_loss!r} needs robust_scale, the loss's scale in the residual's unit")
