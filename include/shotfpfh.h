@@ -162,6 +162,12 @@ int64_t sf_nbrs_max_count(const sf_nbrs *nbrs);
 int64_t sf_nbrs_max_count_all(const sf_nbrs *nbrs);
 int sf_nbrs_export(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, int64_t *offsets /* m+1 */,
                    int32_t *idx /* total */, double *dist /* nullable, total */);
+/* For tests and A/B runs.  sf_nbrs_export_raw: the list set as the search left it -- count and offset (m + 1 each) word for word,
+ * and, with idx non-NULL, the lists packed end to end in their stored order (cell-sorted positions).  sf_k2_debug_paths: with
+ * SF_K2_SHARED=2 in the environment the single sweep counts its waves by path; out[0] = waves that swept the union of their four
+ * queries' windows once, out[1] = waves that swept query by query, since the previous call. */
+int sf_nbrs_export_raw(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, int32_t *count, int64_t *offset, int32_t *idx);
+int sf_k2_debug_paths(sf_ctx *ctx, int64_t *out /* 2 */);
 void sf_nbrs_free(sf_ctx *ctx, sf_nbrs *nbrs);
 
 /* ---- PCA normals: compute_normals radius branch (pca_based_descriptors.py:15-59), K3 ----

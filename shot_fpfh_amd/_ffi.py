@@ -66,6 +66,8 @@ SIGNATURES = {
     "sf_nbrs_max_count": (_i64, [_vp]),
     "sf_nbrs_max_count_all": (_i64, [_vp]),
     "sf_nbrs_export": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_nbrs_export_raw": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_k2_debug_paths": (_int, [_vp, _vp]),
     "sf_nbrs_free": (None, [_vp, _vp]),
     "sf_normals": (_int, [_vp, _vp, _vp, _vp, _vp, _int]),
     "sf_normals_radius": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _f64, _vp, _vp, _int]),

@@ -52,7 +52,10 @@ namespace {
 // SEL: the launch serves the `m` queries named by qsel (processing slots) instead of queries 0 .. m - 1 -- the sample a
 // search sizes its slots from (MODE 0: counts go to the COMPACT array count[0 .. m)), and the queries whose lists overflowed
 // their slot (MODE 1: fill at offset[q], which by then points into the overflow area).
-template <int MODE, bool SEL>
+// SHARE (the single sweep of whole query sets, MODE 2 without SEL): a wave whose four queries have the same stencil rows sweeps
+// the union of their windows once and tests every candidate against all four (below); DBG counts the waves by path.
+__device__ unsigned long long sf_k2_paths[2]; // DBG: waves that took the shared sweep / the per-query sweeps
+template <int MODE, bool SEL, bool SHARE = false, bool DBG = false>
 __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const int32_t *__restrict__ cell_start,
                                                 const double *__restrict__ xs, const double *__restrict__ ys,
                                                 const double *__restrict__ zs, const double *__restrict__ qx,
@@ -82,10 +85,12 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
     // gives the runs' first pair slots, the table goes to LDS -- because the scalar unit is shared by the whole CU.
     __shared__ int4 runs[SF_K2_WPB][4][12];
 #if SF_K2_STAGE
-    __shared__ int stages[MODE != 0 ? SF_K2_WPB : 1][256];
+    __shared__ int stages[MODE != 0 ? SF_K2_WPB : 1][SHARE ? 4 : 1][256];
 #endif
+    static_assert(!SHARE || (MODE == 2 && !SEL && SF_K2_STAGE), "the shared sweep serves the single sweep into slots");
     int4(*const tabs)[12] = runs[threadIdx.x >> 6];
     int first_slot = 0; // lane r < 9 of a row: first pair slot of run r; lane 9: the total
+    bool share = false; // (wave-uniform) one sweep over the union of the four queries' windows
     {
         const int r = sl < 9 ? sl : 8;
         const int cz = z0 + r / 3, cy = y0 + r % 3;
@@ -119,6 +124,27 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
             e = cell_start[row + sf_cell_coord(pxr + w, 0.0, g.inv_cell_x, g.dim[0]) + 1];
         }
         if (!ok) { s = 0; e = 0; }
+        if (SHARE) {
+            // The four queries are consecutive in cell-sorted order: except at row ends they have the same stencil rows, a few
+            // fine x cells apart, and their windows overlap almost entirely.  With identical (y0, y1, z0, z1) run r is the same
+            // row of cells for all four, and the wave sweeps, once, the UNION of the four windows per row: from the smallest s to
+            // the largest e over the queries whose own run is not empty (a row no query reaches stays empty).  Every 16-lane
+            // row then builds, and the sweep reads, that one table.
+            // No per-query window test follows: by the derivation of w above (slack included) every point of the row within r
+            // of query q lies inside q's OWN window, so a candidate of the union outside it fails q's distance test -- the
+            // test alone decides, on the same expression, and each list is the per-query sweep's entry for entry.
+            const bool same = y0 == sf_uniform(y0) && y1 == sf_uniform(y1) && z0 == sf_uniform(z0) && z1 == sf_uniform(z1);
+            share = nq == 4 && __ballot(same) == ~0ull;
+            if (share) {
+                int us = e > s ? s : 0x7fffffff, ue = e > s ? e : 0;
+                us = min(us, __shfl_xor(us, 16));
+                ue = max(ue, __shfl_xor(ue, 16));
+                us = min(us, __shfl_xor(us, 32));
+                ue = max(ue, __shfl_xor(ue, 32));
+                s = ue ? us : 0;
+                e = ue;
+            }
+        }
         const int base = s & ~1; // pairs start at an EVEN position: every 16-byte load is naturally aligned
         const int npairs = (e - base + 1) >> 1;
         // inclusive scan of npairs inside the 16-lane row (row_shr DPP steps), then exclusive = inclusive - own
@@ -131,6 +157,82 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
         if (sl < 12) tabs[rw][sl] = make_int4(base - 2 * first_slot, s, e, first_slot); // j = .x + 2 * slot; .w: first slot
     }
     __builtin_amdgcn_wave_barrier(); // the tables are written and read by this wave only
+    if (DBG && lane == 0) atomicAdd(&sf_k2_paths[share ? 0 : 1], 1ull);
+#if SF_K2_STAGE
+    if (SHARE && share) {
+        // ---- the shared sweep: per step ONE run look-up, ONE j, ONE pair of bounds masks and the three loads; then, per query,
+        // the distance test as below and the query's own compaction -- running total (a scalar), ballot pair, ring, flush.
+        // The bounds masks are the UNION's: they keep the alignment padding of a run (a candidate of the neighbouring row, which
+        // that row's own run also brings) out of every list.
+        const int4 *const tab = tabs[0];
+        const int b4 = __builtin_amdgcn_readlane(first_slot, 4), b8 = __builtin_amdgcn_readlane(first_slot, 8);
+        const int nslots = __builtin_amdgcn_readlane(first_slot, 9);
+        double px[4], py[4], pz[4];
+        int total[4], flushed[4];
+#pragma unroll
+        for (int qi = 0; qi < 4; ++qi) {
+            px[qi] = sf_read_lane(pxv, 16 * qi);
+            py[qi] = sf_read_lane(pyv, 16 * qi);
+            pz[qi] = sf_read_lane(pzv, 16 * qi);
+            total[qi] = 0;
+            flushed[qi] = 0;
+        }
+        int32_t *const out0 = idx + q0 * (int64_t)cap; // query q0 + qi owns [qi * cap, (qi + 1) * cap) from here
+        for (int f0 = 0; f0 < nslots; f0 += 64) {
+            const int f = f0 + lane;
+            int r = f >= b4 ? 4 : 0; // (the look-up of the per-query sweep, on the union's table)
+            r += f >= tab[r + 2].w ? 2 : 0;
+            r += f >= tab[r + 1].w ? 1 : 0;
+            r = f >= b8 ? 8 : r;
+            const int4 t = tab[r];
+            const bool live = f < nslots;
+            const int j = live ? t.x + 2 * f : 0;
+            const bool in0 = live & (j >= t.y), in1 = live & (j + 1 < t.z);
+            const double2 X = *reinterpret_cast<const double2 *>(xs + j);
+            const double2 Y = *reinterpret_cast<const double2 *>(ys + j);
+            const double2 Z = *reinterpret_cast<const double2 *>(zs + j);
+            const unsigned long long i0 = __builtin_amdgcn_ballot_w64(in0), i1 = __builtin_amdgcn_ballot_w64(in1);
+#pragma unroll
+            for (int qi = 0; qi < 4; ++qi) {
+                const double dxa = X.x - px[qi], dya = Y.x - py[qi], dza = Z.x - pz[qi];
+                const double dxb = X.y - px[qi], dyb = Y.y - py[qi], dzb = Z.y - pz[qi];
+                const double d2a = (dxa * dxa + dya * dya) + dza * dza, d2b = (dxb * dxb + dyb * dyb) + dzb * dzb;
+                const bool hit0 = in0 & (d2a <= r2);
+                const bool hit1 = in1 & (d2b <= r2);
+                // (the ballot of a bare comparison IS the lane mask the comparison leaves, and the bounds join it on the scalar
+                // unit; the ballot of hit0 itself goes through a vector select and a second comparison)
+                const unsigned long long m0 = __builtin_amdgcn_ballot_w64(d2a <= r2) & i0, m1 = __builtin_amdgcn_ballot_w64(d2b <= r2) & i1;
+                int *const stage = stages[threadIdx.x >> 6][qi];
+                const int pos = total[qi] + sf_prefix_count(m0) + sf_prefix_count(m1);
+                const int pos1 = pos + (hit0 ? 1 : 0);
+                if (hit0 && pos < cap) stage[pos & 255] = j;
+                if (hit1 && pos1 < cap) stage[pos1 & 255] = j + 1;
+                total[qi] += __popcll(m0) + __popcll(m1);
+                const int have = total[qi] < cap ? total[qi] : cap; // (at most 63 + 128 positions pending: see below)
+                while (have - flushed[qi] >= 64) {
+                    SF_LIST_STORE(out0 + qi * (int64_t)cap + flushed[qi] + lane, stage[(flushed[qi] + lane) & 255]);
+                    flushed[qi] += 64;
+                }
+            }
+        }
+#pragma unroll
+        for (int qi = 0; qi < 4; ++qi) {
+            const int *const stage = stages[threadIdx.x >> 6][qi];
+            const int have = total[qi] < cap ? total[qi] : cap;
+            if (flushed[qi] + lane < have) SF_LIST_STORE(out0 + qi * (int64_t)cap + flushed[qi] + lane, stage[(flushed[qi] + lane) & 255]);
+            if (lane == 0) {
+                const int64_t q = q0 + qi;
+                count[q] = total[qi];
+                offset[q] = q * (int64_t)cap;
+                if (q == m - 1) {
+                    count[m] = 0;
+                    offset[m] = (q + 1) * (int64_t)cap;
+                }
+            }
+        }
+        return;
+    }
+#endif
     for (int qi = 0; qi < nq; ++qi) {
         const int64_t q = SEL ? (int64_t)sf_uniform(__shfl((int)qm, 16 * qi)) : q0 + qi;
         const int4 *const tab = tabs[qi];
@@ -149,7 +251,7 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
         // Hits go to a 256-entry ring in LDS first and leave for HBM 64 list positions at a time: a sweep step finds ~14 hits
         // of its 128 candidates, and 14 x 4 B stored past the L2 (`nt`) is a partial line each time -- the counters showed
         // 2.2 x the lists' bytes written.  Whole, aligned 256-byte runs instead (slots start on 128-byte boundaries).
-        int *const stage = stages[threadIdx.x >> 6];
+        int *const stage = stages[threadIdx.x >> 6][0];
         int flushed = 0; // list positions [0, flushed) are in HBM; a multiple of 64
 #endif
         for (int f0 = 0; f0 < nslots; f0 += 64) {
@@ -454,7 +556,7 @@ __global__ __launch_bounds__(256) void k_export_lists(const double *__restrict__
     const double px = qx[q], py = qy[q], pz = qz[q];
     for (int t = lane; t < k; t += 64) {
         const int j = idx[s + t];
-        out_idx[d + t] = perm[j];
+        out_idx[d + t] = perm ? perm[j] : j; // (no perm: cell-sorted positions, sf_nbrs_export_raw)
         if (out_dist) {
             const double dx = xs[j] - px, dy = ys[j] - py, dz = zs[j] - pz;
             out_dist[d + t] = sqrt((dx * dx + dy * dy) + dz * dz);
@@ -824,7 +926,12 @@ static int run_search(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb)
     if (rec) cap = rec->cap;
     SF_CHECK(sf_palloc(ctx, &nb->idx, (size_t)(cap * m) + 4)); // +4: consumers read indices 16 B at a time
     nb->cap = cap;
-    SF_LAUNCH(ctx, "k2_radius_slots", (k_radius<2, false>), grid, block, g, c->cell_start, c->xs, c->ys, c->zs, nb->qx, nb->qy,
+    // SF_K2_SHARED=0: every wave sweeps query by query (A/B runs, and what the tests hold the shared sweep's lists to); 2: the
+    // shared sweep's instantiation that also counts the waves of either path (sf_k2_debug_paths)
+    const char *const sh = getenv("SF_K2_SHARED");
+    const int shared = sh ? atoi(sh) : 1;
+    auto *const k_slots = shared == 2 ? k_radius<2, false, true, true> : shared ? k_radius<2, false, true> : k_radius<2, false>;
+    SF_LAUNCH(ctx, "k2_radius_slots", k_slots, grid, block, g, c->cell_start, c->xs, c->ys, c->zs, nb->qx, nb->qy,
               nb->qz, m, r2, (int)cap, nb->count, nb->offset, nb->idx, (const int32_t *)nullptr);
     int64_t ovf_total = 0;
     if (rec && !getenv("SF_K2_CHECK_RECORD")) { // no statistics pass, no read-back: the step's launches follow without a wait
@@ -1301,6 +1408,51 @@ extern "C" int sf_nbrs_export(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int64_t *of
             }
         }
     }
+    return SF_OK;
+}
+
+// The list set as the search left it: count and offset word for word, and (idx != NULL) the lists packed end to end in their
+// STORED order -- cell-sorted positions, ascending run by run as the sweep found them.  For tests that hold one sweep to another.
+extern "C" int sf_nbrs_export_raw(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int32_t *count, int64_t *offset, int32_t *idx)
+{
+    if (!ctx || !c || !nb || !count || !offset) { sf_set_error("sf_nbrs_export_raw: null argument"); return SF_ERR_ARG; }
+    if (nb->view) { sf_set_error("sf_nbrs_export_raw: not for a slice view"); return SF_ERR_ARG; }
+    SF_CHECK(sf_nbrs_on_grid(nb, c, "sf_nbrs_export_raw"));
+    SF_HIP(hipSetDevice(ctx->device));
+    const int64_t m = nb->m;
+    SF_HIP(hipMemcpyAsync(count, nb->count, (size_t)(m + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipMemcpyAsync(offset, nb->offset, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    if (!idx || !m || !nb->total) return SF_OK;
+    std::vector<int64_t> eoff((size_t)m + 1);
+    eoff[0] = 0;
+    for (int64_t q = 0; q < m; ++q) eoff[(size_t)q + 1] = eoff[(size_t)q] + count[q];
+    if (eoff[(size_t)m] != nb->total) { sf_set_error("sf_nbrs_export_raw: inconsistent counts"); return SF_ERR_STATE; }
+    sf_pool_guard tmp(ctx);
+    int64_t *d_eoff = nullptr;
+    int32_t *d_idx = nullptr;
+    SF_CHECK(tmp.alloc(&d_eoff, (size_t)m + 1));
+    SF_CHECK(tmp.alloc(&d_idx, (size_t)nb->total));
+    SF_HIP(hipMemcpyAsync(d_eoff, eoff.data(), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    SF_LAUNCH(ctx, "k2_export_lists", k_export_lists, dim3((unsigned)sf_div_up(m, 4)), dim3(256), c->xs, c->ys, c->zs, nb->qx, nb->qy,
+              nb->qz, nb->offset, nb->count, nb->idx, d_eoff, (const int32_t *)nullptr, m, d_idx, (double *)nullptr);
+    SF_HIP(hipMemcpyAsync(idx, d_idx, (size_t)nb->total * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    return SF_OK;
+}
+
+// Waves of the SF_K2_SHARED=2 launches since the last call that took the shared sweep (out[0]) and the per-query sweeps (out[1]).
+extern "C" int sf_k2_debug_paths(sf_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) { sf_set_error("sf_k2_debug_paths: null argument"); return SF_ERR_ARG; }
+    SF_HIP(hipSetDevice(ctx->device));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    unsigned long long h[2] = {0, 0};
+    const unsigned long long zero[2] = {0, 0};
+    SF_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(sf_k2_paths), sizeof(h)));
+    SF_HIP(hipMemcpyToSymbol(HIP_SYMBOL(sf_k2_paths), zero, sizeof(zero)));
+    out[0] = (int64_t)h[0];
+    out[1] = (int64_t)h[1];
     return SF_OK;
 }
 

@@ -778,6 +778,13 @@ class Engine:
         rank must then run the same searches in the same order."""
         _ffi.check(self.lib.sf_comm_collective_stats(self.h, int(bool(on))), "sf_comm_collective_stats")
 
+    def k2_debug_paths(self) -> tuple[int, int]:
+        """With SF_K2_SHARED=2 the single sweep of a radius search counts its waves by path: (waves that swept the union of
+        their four queries' windows once, waves that swept query by query) since the previous call."""
+        out = np.zeros(2, dtype=np.int64)
+        _ffi.check(self.lib.sf_k2_debug_paths(self.h, _ptr(out)), "sf_k2_debug_paths")
+        return int(out[0]), int(out[1])
+
     # ---- profiling ----------------------------------------------------------------------------------
     def profile(self, on: bool) -> None:
         _ffi.check(self.lib.sf_profile_enable(self.h, int(on)), "sf_profile_enable")
@@ -1065,6 +1072,16 @@ class Neighbors:
         if return_distance:
             return off, idx[: self.total], dist[: self.total]
         return off, idx[: self.total]
+
+    def export_raw(self):
+        """(count[m+1], offset[m+1], idx[total]) as the search left them on the device: idx holds the lists end to end in their
+        stored order, as cell-sorted positions (Cloud.perm() maps them to the caller's numbering).  For tests."""
+        cnt = np.zeros(self.m + 1, dtype=np.int32)
+        off = np.zeros(self.m + 1, dtype=np.int64)
+        idx = np.zeros(max(self.total, 1), dtype=np.int32)
+        _ffi.check(self.engine.lib.sf_nbrs_export_raw(self.engine.h, self.cloud.h, self.h, _ptr(cnt), _ptr(off), _ptr(idx)),
+                   "sf_nbrs_export_raw")
+        return cnt, off, idx[: max(self.total, 0)]
 
     def counts(self) -> np.ndarray:
         """Neighbourhood size of every query (len of each KDTree.query_radius list), without the lists."""
