@@ -25,6 +25,7 @@ static inline hipError_t sf_counted_stream_sync(hipStream_t s)
 #define hipStreamSynchronize(s) sf_counted_stream_sync(s)
 
 #define SF_WAVE 64
+constexpr double SF_DBL_MAX = 1.7976931348623157e308; // 0 <= x <= SF_DBL_MAX: finite and no NaN
 
 void sf_set_error(const char *fmt, ...);
 

@@ -18,14 +18,7 @@
 #include "common.h"
 #include "device_util.h"
 #include "horn4.h"
-
-// K9 (match.hip) and the back half of K11 (ransac.hip): what K15 ranks its fits with
-extern "C" int sf_ransac_score(sf_ctx *ctx, const double *a, const double *b, int64_t m, const double *Rt, int64_t n_draws,
-                               double thr, int64_t *inliers, int flags);
-int64_t sf_k11_blocks(int64_t n);
-int sf_k11_compact(sf_ctx *ctx, const unsigned char *status, const double *Rt_all, int64_t n, double *Rt_out, int64_t *map,
-                   int *block_count, int64_t *block_off, unsigned long long *tallies);
-int sf_k11_first_max(sf_ctx *ctx, const int64_t *counts, int64_t n, const int64_t *map, const double *Rt, int64_t *win, double *best_rt);
+#include "ransac.h" // the back half of K11, which with K9 (sf_ransac_score, match.hip) ranks K15's fits
 
 namespace {
 
@@ -33,7 +26,6 @@ constexpr int K13_BLOCK = 256;          // rows of a block, one per thread
 constexpr int K13_TILE = 128;           // columns staged through LDS at a time: 16 row blocks x 32 tiles at m = 4096, 2 blocks per CU
 constexpr int K13_TARGET_BLOCKS = 4096; // column slices are cut until the grid has about this many blocks (16 per CU)
 constexpr int K13_FOLD = 1024;          // threads of the single-block kernels
-constexpr double K13_DBL_MAX = 1.7976931348623157e308;
 
 // the device info block (int64)
 enum { IN_SEED = 0, IN_SEED_DEGREE = 1, IN_GROUP = 2, IN_STATUS = 3, IN_SIZE = 4 };
@@ -144,7 +136,7 @@ int k13_check(const char *who, bool pointers, int64_t m, double thr, double min_
 {
     if (!pointers || m < 0) { sf_set_error("%s: bad argument", who); return SF_ERR_ARG; }
     if (m > 0x7fffffffll) { sf_set_error("%s: %lld matches, at most 2^31 - 1", who, (long long)m); return SF_ERR_ARG; }
-    if (!(thr >= 0.0 && thr <= K13_DBL_MAX) || !(min_edge >= 0.0 && min_edge <= K13_DBL_MAX)) {
+    if (!(thr >= 0.0 && thr <= SF_DBL_MAX) || !(min_edge >= 0.0 && min_edge <= SF_DBL_MAX)) {
         sf_set_error("%s: distance_threshold %g and min_edge %g must be finite and not negative", who, thr, min_edge);
         return SF_ERR_ARG;
     }
@@ -494,25 +486,19 @@ __global__ __launch_bounds__(512) void k15_seed_rows(const unsigned char *__rest
 #undef K15_FRAG
 #undef K14_DMA16
 
-// NV sums over the block, the same total in every thread: lanes by the xor ladder, the four waves in wave order.
+// NV sums over the block, the same total in every thread (sf_block_sum4, device_util.h)
 template <int NV>
-__device__ __forceinline__ void k15_block_sums(double (&v)[NV], double (*sh)[9])
+__device__ __forceinline__ void k15_block_sums(double (&v)[NV], double (&sh)[4][9])
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __syncthreads(); // (the previous use of sh has been read)
+    sf_block_sum4_stage(v, sh);
 #pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        double x = v[q];
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        if (lane == 0) sh[wave][q] = x;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = ((sh[0][q] + sh[1][q]) + sh[2][q]) + sh[3][q];
+    for (int q = 0; q < NV; ++q) v[q] = sf_block_sum4_at(sh, q);
 }
 
-// grid: one block a seed.  status: 0 a transform, 1 fewer than three members, 2 no unique rotation (K11's rule and constants),
-// 3 no seed in this slot.  sums (nullable): sf_ransac_refit_sums's layout, [16] = 0.  member (nullable): n_seeds x m bytes.
+// grid: one block a seed.  status: 0 a transform, 1 fewer than three members, 2 no unique rotation (sf_horn::rigid_from_moments,
+// horn4.h: sf_horn::kabsch_rotation and the one rule K11's draws are held to), 3 no seed in this slot.
+// sums (nullable): sf_ransac_refit_sums's layout (ransac.h), RS_SSR = 0.  member (nullable): n_seeds x m bytes.
 __global__ __launch_bounds__(K15_FIT) void k15_fit(const double *__restrict__ a, const double *__restrict__ b, int64_t m, int64_t m_pad,
                                                    const int *__restrict__ seeds, const unsigned *__restrict__ rows, double share,
                                                    unsigned char *__restrict__ status, int *__restrict__ size, double *__restrict__ Rt,
@@ -545,9 +531,7 @@ __global__ __launch_bounds__(K15_FIT) void k15_fit(const double *__restrict__ a,
         const bool in = sd >= 0 && (j == sd || (r >= 1u && (double)r >= cut));
         if (mem) mem[j] = in ? 1 : 0;
         if (!in) continue;
-        v0[0] += 1.0;
-        v0[1] += a[3 * j]; v0[2] += a[3 * j + 1]; v0[3] += a[3 * j + 2];
-        v0[4] += b[3 * j]; v0[5] += b[3 * j + 1]; v0[6] += b[3 * j + 2];
+        sf_refit_add_pair(v0, a[3 * j], a[3 * j + 1], a[3 * j + 2], b[3 * j], b[3 * j + 1], b[3 * j + 2]);
     }
     k15_block_sums<7>(v0, sh);
     const double n = v0[0];
@@ -563,11 +547,7 @@ __global__ __launch_bounds__(K15_FIT) void k15_fit(const double *__restrict__ a,
         for (int64_t j = tid; j < m; j += K15_FIT) {
             const unsigned r = row[j];
             if (!(j == sd || (r >= 1u && (double)r >= cut))) continue;
-            const double ux = a[3 * j] - mean[0], uy = a[3 * j + 1] - mean[1], uz = a[3 * j + 2] - mean[2];
-            const double vx = b[3 * j] - mean[3], vy = b[3 * j + 1] - mean[4], vz = b[3 * j + 2] - mean[5];
-            v1[0] += ux * vx; v1[1] += ux * vy; v1[2] += ux * vz;
-            v1[3] += uy * vx; v1[4] += uy * vy; v1[5] += uy * vz;
-            v1[6] += uz * vx; v1[7] += uz * vy; v1[8] += uz * vz;
+            sf_refit_add_centred(v1, mean, a[3 * j], a[3 * j + 1], a[3 * j + 2], b[3 * j], b[3 * j + 1], b[3 * j + 2]);
         }
     k15_block_sums<9>(v1, sh);
     if (tid != 0) return;
@@ -575,33 +555,20 @@ __global__ __launch_bounds__(K15_FIT) void k15_fit(const double *__restrict__ a,
     double o[12];
 #pragma unroll
     for (int q = 0; q < 12; ++q) o[q] = 0.0;
-    if (st == 0) {
-        const sf_horn::rot3 R = sf_horn::kabsch_rotation(v1[0], v1[1], v1[2], v1[3], v1[4], v1[5], v1[6], v1[7], v1[8]);
-        const double t0 = mean[3] - ((R.r0 * mean[0] + R.r1 * mean[1]) + R.r2 * mean[2]);
-        const double t1 = mean[4] - ((R.r3 * mean[0] + R.r4 * mean[1]) + R.r5 * mean[2]);
-        const double t2 = mean[5] - ((R.r6 * mean[0] + R.r7 * mean[1]) + R.r8 * mean[2]);
-        const double mag = (((fabs(R.r0) + fabs(R.r1)) + (fabs(R.r2) + fabs(R.r3))) + ((fabs(R.r4) + fabs(R.r5)) + (fabs(R.r6) + fabs(R.r7)))) +
-                           ((fabs(R.r8) + fabs(t0)) + (fabs(t1) + fabs(t2)));
-        if (R.gap > 1e-6 * R.s1 && mag <= K13_DBL_MAX) { // K11's rule (ransac.hip)
-            o[0] = R.r0; o[1] = R.r1; o[2] = R.r2; o[3] = R.r3; o[4] = R.r4; o[5] = R.r5; o[6] = R.r6; o[7] = R.r7; o[8] = R.r8;
-            o[9] = t0; o[10] = t1; o[11] = t2;
-        } else {
-            st = 2;
-        }
-    }
+    if (st == 0 && !sf_horn::rigid_from_moments(mean, v1, o)) st = 2;
     status[s] = st;
     size[s] = (int)n;
 #pragma unroll
     for (int q = 0; q < 12; ++q) Rt[12 * (int64_t)s + q] = o[q];
     if (sums) {
-        double *out = sums + 24 * (int64_t)s;
-        out[0] = n;
+        double *out = sums + RS_SIZE * (int64_t)s;
+        out[RS_COUNT] = n;
 #pragma unroll
-        for (int q = 0; q < 6; ++q) { out[1 + q] = mean[q]; out[17 + q] = v0[1 + q]; }
+        for (int q = 0; q < 6; ++q) { out[RS_ABAR + q] = mean[q]; out[RS_SUM_A + q] = v0[1 + q]; } // a, then b
 #pragma unroll
-        for (int q = 0; q < 9; ++q) out[7 + q] = v1[q];
-        out[16] = 0.0;
-        out[23] = 0.0;
+        for (int q = 0; q < 9; ++q) out[RS_H + q] = v1[q];
+        out[RS_SSR] = 0.0;
+        out[RS_SPARE] = 0.0;
     }
 }
 

@@ -274,6 +274,32 @@ __device__ inline double sf_rcp_fast(double d) // 1/d for normal d, ~1 ulp
     return __builtin_fma(r, e, r);
 }
 
+// The block sum of the registration kernels (I1, K11, K12, K15): 256 threads, NV values each, ONE order of additions whatever the
+// kernel -- the xor ladder off = 32 .. 1 over the lanes of a wave, lane 0's value to sh[wave][v], a barrier, then the four waves in
+// wave order.  Every one of those kernels is specified to the rounding, and a run repeats bit for bit.  Which threads take a
+// total, and what they do with it, stays with the kernel.  MAX: the maximum in place of the sum (the ladder only).
+template <bool MAX = false, int NV, int W>
+__device__ __forceinline__ void sf_block_sum4_stage(const double (&acc)[NV], double (&sh)[4][W])
+{
+    static_assert(NV <= W, "a row of the stage holds every value");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        double x = acc[v];
+        for (int off = 32; off > 0; off >>= 1) {
+            const double y = __shfl_xor(x, off);
+            x = MAX ? fmax(x, y) : x + y;
+        }
+        if (lane == 0) sh[wave][v] = x;
+    }
+    __syncthreads();
+}
+template <int W>
+__device__ __forceinline__ double sf_block_sum4_at(const double (&sh)[4][W], int v)
+{
+    return ((sh[0][v] + sh[1][v]) + sh[2][v]) + sh[3][v];
+}
+
 __device__ inline int sf_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 __device__ inline long long sf_uniform64(long long v)

@@ -93,22 +93,12 @@ __global__ __launch_bounds__(K12_BLOCK) void k12_fgr_moments(const double *__res
             acc[1] = fmax(acc[1], nb);
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        double x = acc[v];
-        for (int off = 32; off > 0; off >>= 1) {
-            const double y = __shfl_xor(x, off);
-            x = PASS == 0 ? x + y : fmax(x, y);
-        }
-        if (lane == 0) sh[wave][v] = x;
-    }
-    __syncthreads();
+    sf_block_sum4_stage<PASS == 1>(acc, sh);
     if (threadIdx.x < K12_NV) {
         double x = 0.0;
         if (threadIdx.x < NV) {
             const int v = threadIdx.x;
-            x = PASS == 0 ? ((sh[0][v] + sh[1][v]) + sh[2][v]) + sh[3][v] : fmax(fmax(sh[0][v], sh[1][v]), fmax(sh[2][v], sh[3][v]));
+            x = PASS == 0 ? sf_block_sum4_at(sh, v) : fmax(fmax(sh[0][v], sh[1][v]), fmax(sh[2][v], sh[3][v]));
         }
         partial[(size_t)blockIdx.x * K12_NV + threadIdx.x] = x;
     }
@@ -129,7 +119,7 @@ __global__ __launch_bounds__(K12_FOLD) void k12_fgr_setup(const double *__restri
         if (threadIdx.x == ST_STATUS && sh[6] != 0.0) state[ST_STATUS] = 3.0;
     } else if (threadIdx.x == 0) {
         const double s = sqrt(fmax(sh[0], sh[1]));
-        const bool ok = s > 0.0 && s <= 1.7976931348623157e308;
+        const bool ok = s > 0.0 && s <= SF_DBL_MAX;
         state[ST_S] = ok ? s : 0.0;
         state[ST_R] = state[ST_R + 4] = state[ST_R + 8] = 1.0;
         state[ST_MU] = 1.0;
@@ -175,19 +165,12 @@ __global__ __launch_bounds__(K12_BLOCK) void k12_fgr_sums(const double *__restri
         acc[16] += w * rr + mu * (lm * lm);
         acc[17] += 1.0;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v < K12_NACC; ++v) {
-        double x = acc[v];
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        if (lane == 0) sh[wave][v] = x;
-    }
-    __syncthreads();
+    sf_block_sum4_stage(acc, sh);
     if (threadIdx.x < K12_NV) {
         const int src = k12_src[threadIdx.x];
         double x = 0.0;
         if (src >= 0) {
-            x = ((sh[0][src] + sh[1][src]) + sh[2][src]) + sh[3][src];
+            x = sf_block_sum4_at(sh, src);
             if (k12_neg[threadIdx.x]) x = -x;
         }
         partial[(size_t)blockIdx.x * K12_NV + threadIdx.x] = x;
@@ -227,7 +210,7 @@ __global__ __launch_bounds__(K12_FOLD) void k12_fgr_step(const double *__restric
         double dj = A[j][j];
 #pragma unroll
         for (int q = 0; q < j; ++q) dj = dj - (L[j][q] * L[j][q]) * d[q];
-        ok = ok && dj > K12_PIVOT_TOL * A[j][j] && dj <= 1.7976931348623157e308;
+        ok = ok && dj > K12_PIVOT_TOL * A[j][j] && dj <= SF_DBL_MAX;
         d[j] = ok ? dj : 1.0; // (keeps the arithmetic below finite; the result is not used)
 #pragma unroll
         for (int i = j + 1; i < 6; ++i) {
@@ -252,7 +235,7 @@ __global__ __launch_bounds__(K12_FOLD) void k12_fgr_step(const double *__restric
         xi[i] = v;
     }
     const double mag = ((fabs(xi[0]) + fabs(xi[1])) + (fabs(xi[2]) + fabs(xi[3]))) + (fabs(xi[4]) + fabs(xi[5]));
-    ok = ok && mag <= 1.7976931348623157e308;
+    ok = ok && mag <= SF_DBL_MAX;
     state[ST_E] = E;
     state[ST_W] = W;
     if (!ok) { state[ST_STATUS] = 1.0; return; } // degenerate: the transform of the previous iteration stays
@@ -342,7 +325,7 @@ extern "C" int sf_fgr(sf_ctx *ctx, const double *a_dev, const double *b_dev, int
     if (!ctx || !a_dev || !b_dev || !Rt || !info || m < 0) { sf_set_error("sf_fgr: bad argument"); return SF_ERR_ARG; }
     SF_CHECK(k12_check_rows("sf_fgr", m, sel_dev, k));
     if (iterations < 1 || decrease_every < 1 || !(division_factor > 1.0) ||
-        !(fabs(distance_threshold) <= 1.7976931348623157e308)) {
+        !(fabs(distance_threshold) <= SF_DBL_MAX)) {
         sf_set_error("sf_fgr: iterations %d >= 1, decrease_every %d >= 1, division_factor %g > 1 and a finite threshold are needed",
                      iterations, decrease_every, division_factor);
         return SF_ERR_ARG;

@@ -19,6 +19,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "common.h"
+
 namespace sf_horn {
 
 struct rot3 {
@@ -142,5 +144,23 @@ __host__ __device__ inline rot3 kabsch_rotation(double h00, double h01, double h
     return R;
 }
 #undef SF_HORN_ROT
+
+// The rigid motion of a Kabsch fit from its moments: mean = {abar, bbar}, H the centred cross-covariance (row-major) ->
+// o = {R row-major, t = bbar - R abar}.  false, and o as it was, when the rotation is not unique (gap <= 1e-6 s1: H = 0, collinear
+// points, non-finite input) or an entry is not finite (the sum of the twelve magnitudes is finite iff all of them are: no NaN and
+// no infinity ever reaches the scoring).  The one rule of K11's draws and K15's seeds.
+__host__ __device__ inline bool rigid_from_moments(const double (&mean)[6], const double (&H)[9], double (&o)[12])
+{
+    const rot3 R = kabsch_rotation(H[0], H[1], H[2], H[3], H[4], H[5], H[6], H[7], H[8]);
+    const double t0 = mean[3] - ((R.r0 * mean[0] + R.r1 * mean[1]) + R.r2 * mean[2]);
+    const double t1 = mean[4] - ((R.r3 * mean[0] + R.r4 * mean[1]) + R.r5 * mean[2]);
+    const double t2 = mean[5] - ((R.r6 * mean[0] + R.r7 * mean[1]) + R.r8 * mean[2]);
+    const double mag = (((fabs(R.r0) + fabs(R.r1)) + (fabs(R.r2) + fabs(R.r3))) + ((fabs(R.r4) + fabs(R.r5)) + (fabs(R.r6) + fabs(R.r7)))) +
+                       ((fabs(R.r8) + fabs(t0)) + (fabs(t1) + fabs(t2)));
+    if (!(R.gap > 1e-6 * R.s1 && mag <= SF_DBL_MAX)) return false;
+    o[0] = R.r0; o[1] = R.r1; o[2] = R.r2; o[3] = R.r3; o[4] = R.r4; o[5] = R.r5; o[6] = R.r6; o[7] = R.r7; o[8] = R.r8;
+    o[9] = t0; o[10] = t1; o[11] = t2;
+    return true;
+}
 
 } // namespace sf_horn

@@ -31,10 +31,6 @@
 #include "device_util.h"
 #include "select.h"
 
-extern "C" sf_nbrs *sf_knn_search(sf_ctx *ctx, sf_cloud *c, const double *queries, int64_t m, int k, int flags);
-extern "C" void sf_nbrs_free(sf_ctx *ctx, sf_nbrs *nb);
-int sf_cloud_ensure_sorted_normals(sf_ctx *ctx, sf_cloud *c);
-
 namespace {
 
 constexpr int ICP_BLOCKS = 256;
@@ -57,35 +53,14 @@ __global__ void k_transform(const double *__restrict__ pts, const int64_t *__res
     out[3 * i] = ox; out[3 * i + 1] = oy; out[3 * i + 2] = oz;
 }
 
-template <int NV>
-__device__ inline void block_fold(double (&acc)[NV], double *__restrict__ partial_row)
-{
-    __shared__ double sh[4][ICP_NV];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        double a = acc[v];
-        for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
-        if (lane == 0) sh[wave][v] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) partial_row[threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-}
-
-// fold the block partials in block order (PASS 1 of every mode); given `mean` it also leaves the centroids of slots 1 .. 6 over
-// slot 0, which no caller asks for since k_icp_means folds PASS 0
-__global__ __launch_bounds__(64) void k_icp_final(const double *__restrict__ partial, int nblocks, int nv, double *__restrict__ out,
-                                                  double *__restrict__ mean)
+// fold the block partials in block order (PASS 1 of every mode; k_icp_means folds PASS 0)
+__global__ __launch_bounds__(64) void k_icp_final(const double *__restrict__ partial, int nblocks, int nv, double *__restrict__ out)
 {
     const int v = threadIdx.x;
     double a = 0.0;
     if (v < nv)
         for (int b = 0; b < nblocks; ++b) a += partial[(size_t)b * ICP_NV + v];
     if (v < nv) out[v] = a;
-    if (mean) {
-        const double cnt = __shfl(a, 0);
-        if (v >= 1 && v <= 6) mean[v - 1] = cnt > 0.0 ? a / cnt : 0.0;
-    }
 }
 
 // ---- the weight of a kept pair (K17) ------------------------------------------------------------------------------------------
@@ -229,6 +204,7 @@ __global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx,
                                                   const double *__restrict__ cut /* null: no trimming */, double *__restrict__ partial)
 {
     constexpr int NV = PASS == 0 ? 15 : (MODE == 0 ? 10 : (MODE == 1 ? 28 : 29));
+    __shared__ double sh[4][ICP_NV];
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
@@ -308,7 +284,8 @@ __global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx,
             acc[28] += d2;
         }
     }
-    block_fold<NV>(acc, partial + (size_t)blockIdx.x * ICP_NV);
+    sf_block_sum4_stage(acc, sh);
+    if (threadIdx.x < NV) partial[(size_t)blockIdx.x * ICP_NV + threadIdx.x] = sf_block_sum4_at(sh, threadIdx.x);
 }
 
 // fold PASS 0's block partials in block order into sums[48]: [0..7] as they are, w p, w q, w r2 to [40..46]; and leave the
@@ -401,7 +378,7 @@ static int icp_chain(const char *who, sf_ctx *ctx, sf_cloud *ref, const double *
     else { SF_ICP_PASS(1, 2, no_mean); }
 #undef SF_ICP_PASS
     SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, mode == 0 ? 10 : (mode == 1 ? 28 : 29),
-              dout + 8, (double *)nullptr);
+              dout + 8);
     double all[56];
     SF_HIP(hipMemcpyAsync(all, dout, (trimmed ? 56 : 48) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));

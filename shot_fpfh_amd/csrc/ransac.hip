@@ -16,9 +16,7 @@
 #include "device_util.h"
 #include "horn4.h"
 #include "match.h"
-
-extern "C" int sf_ransac_score(sf_ctx *ctx, const double *a, const double *b, int64_t m, const double *Rt, int64_t n_draws,
-                               double thr, int64_t *inliers, int flags);
+#include "ransac.h"
 
 namespace {
 
@@ -79,19 +77,8 @@ __global__ __launch_bounds__(64) void k11_hypotheses(const double *__restrict__ 
                 h10 += py * qx; h11 += py * qy; h12 += py * qz;
                 h20 += pz * qx; h21 += pz * qy; h22 += pz * qz;
             }
-        const sf_horn::rot3 R = sf_horn::kabsch_rotation(h00, h01, h02, h10, h11, h12, h20, h21, h22);
-        const double t0 = mb0 - ((R.r0 * ma0 + R.r1 * ma1) + R.r2 * ma2);
-        const double t1 = mb1 - ((R.r3 * ma0 + R.r4 * ma1) + R.r5 * ma2);
-        const double t2 = mb2 - ((R.r6 * ma0 + R.r7 * ma1) + R.r8 * ma2);
-        // (the sum of magnitudes is finite iff all twelve are: no NaN and no infinity ever reaches the scoring)
-        const double mag = (((fabs(R.r0) + fabs(R.r1)) + (fabs(R.r2) + fabs(R.r3))) + ((fabs(R.r4) + fabs(R.r5)) + (fabs(R.r6) + fabs(R.r7)))) +
-                           ((fabs(R.r8) + fabs(t0)) + (fabs(t1) + fabs(t2)));
-        if (R.gap > 1e-6 * R.s1 && mag <= 1.7976931348623157e308) {
-            o[0] = R.r0; o[1] = R.r1; o[2] = R.r2; o[3] = R.r3; o[4] = R.r4; o[5] = R.r5; o[6] = R.r6; o[7] = R.r7; o[8] = R.r8;
-            o[9] = t0; o[10] = t1; o[11] = t2;
-        } else {
-            st = 2;
-        }
+        const double mean[6] = {ma0, ma1, ma2, mb0, mb1, mb2}, H[9] = {h00, h01, h02, h10, h11, h12, h20, h21, h22};
+        if (!sf_horn::rigid_from_moments(mean, H, o)) st = 2;
     }
     status[d] = st;
 #pragma unroll
@@ -205,8 +192,8 @@ __global__ __launch_bounds__(256) void k11_pair_sums(const double *__restrict__ 
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
     const double r0 = R[0], r1 = R[1], r2 = R[2], r3 = R[3], r4 = R[4], r5 = R[5], r6 = R[6], r7 = R[7], r8 = R[8];
     const double t0 = R[9], t1 = R[10], t2 = R[11];
-    double pm0 = 0, pm1 = 0, pm2 = 0, qm0 = 0, qm1 = 0, qm2 = 0;
-    if (PASS == 1) { pm0 = mean[0]; pm1 = mean[1]; pm2 = mean[2]; qm0 = mean[3]; qm1 = mean[4]; qm2 = mean[5]; }
+    double mu[6] = {0, 0, 0, 0, 0, 0};
+    if (PASS == 1) { mu[0] = mean[0]; mu[1] = mean[1]; mu[2] = mean[2]; mu[3] = mean[3]; mu[4] = mean[4]; mu[5] = mean[5]; }
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
         const double px = a[3 * i], py = a[3 * i + 1], pz = a[3 * i + 2];
         const double qx = b[3 * i], qy = b[3 * i + 1], qz = b[3 * i + 2];
@@ -216,28 +203,14 @@ __global__ __launch_bounds__(256) void k11_pair_sums(const double *__restrict__ 
         const double s = (e0 * e0 + e1 * e1) + e2 * e2;
         if (!(s <= lo || (s < hi && sqrt(s) <= thr))) continue;
         if (PASS == 0) {
-            acc[0] += 1.0;
-            acc[1] += px; acc[2] += py; acc[3] += pz;
-            acc[4] += qx; acc[5] += qy; acc[6] += qz;
+            sf_refit_add_pair(acc, px, py, pz, qx, qy, qz);
         } else {
-            const double ux = px - pm0, uy = py - pm1, uz = pz - pm2;
-            const double vx = qx - qm0, vy = qy - qm1, vz = qz - qm2;
-            acc[0] += ux * vx; acc[1] += ux * vy; acc[2] += ux * vz;
-            acc[3] += uy * vx; acc[4] += uy * vy; acc[5] += uy * vz;
-            acc[6] += uz * vx; acc[7] += uz * vy; acc[8] += uz * vz;
+            sf_refit_add_centred(acc, mu, px, py, pz, qx, qy, qz);
             acc[NV - 1] += s;
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        double x = acc[v];
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        if (lane == 0) sh[wave][v] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV)
-        partial[(size_t)blockIdx.x * K11_NV + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+    sf_block_sum4_stage(acc, sh);
+    if (threadIdx.x < NV) partial[(size_t)blockIdx.x * K11_NV + threadIdx.x] = sf_block_sum4_at(sh, threadIdx.x);
 }
 
 // the block partials folded in block order into sums[24] (layout: sf_ransac_refit_sums); pass 0 also leaves the centroids
@@ -249,10 +222,10 @@ __global__ __launch_bounds__(64) void k11_sums_final(const double *__restrict__ 
         for (int blk = 0; blk < nblocks; ++blk) x += partial[(size_t)blk * K11_NV + v];
     const double cnt = __shfl(x, 0);
     if (pass == 0) {
-        if (v == 0) { sums[0] = x; sums[23] = 0.0; }
-        if (v >= 1 && v < 7) { sums[16 + v] = x; sums[v] = cnt > 0.0 ? x / cnt : 0.0; }
+        if (v == 0) { sums[RS_COUNT] = x; sums[RS_SPARE] = 0.0; }
+        if (v >= 1 && v < 7) { sums[RS_SUM_A + v - 1] = x; sums[RS_ABAR + v - 1] = cnt > 0.0 ? x / cnt : 0.0; } // a, then b
     } else if (v < 10) {
-        sums[7 + v] = x;
+        sums[RS_H + v] = x; // the nine of H, then RS_SSR
     }
 }
 
@@ -274,7 +247,7 @@ int launch_hypotheses(sf_ctx *ctx, const char *who, const double *a, const doubl
 
 } // namespace
 
-// ---- the back half of K11, for the other estimators that rank fitted transforms (K15, consistency.hip) ------------------------------
+// ---- the back half of K11, for the other estimators that rank fitted transforms (K15, consistency.hip; ransac.h) -------------------
 // The status-0 rows of Rt_all compacted in order into Rt_out, map[slot] = their position; tallies (4, zeroed here) <- the number of
 // status 0 (after the scan), 1, 2, 3.  block_count / block_off: sf_k11_blocks(n) entries of scratch each.  Queued, no host wait.
 int64_t sf_k11_blocks(int64_t n) { return std::max<int64_t>(sf_div_up(n, K11_BLOCK), 1); }
@@ -317,13 +290,13 @@ extern "C" int sf_ransac_refit_sums(sf_ctx *ctx, const double *a_dev, const doub
 {
     if (!ctx || !a_dev || !b_dev || !Rt || !sums || m < 0) { sf_set_error("sf_ransac_refit_sums: bad argument"); return SF_ERR_ARG; }
     SF_HIP(hipSetDevice(ctx->device));
-    for (int i = 0; i < 24; ++i) sums[i] = 0.0;
+    for (int i = 0; i < RS_SIZE; ++i) sums[i] = 0.0;
     if (!m) return SF_OK;
     sf_pool_guard tmp(ctx);
     double *dRt = nullptr, *partial = nullptr, *dsums = nullptr;
     SF_CHECK(tmp.alloc(&dRt, 12));
     SF_CHECK(tmp.alloc(&partial, (size_t)K11_SUM_BLOCKS * K11_NV));
-    SF_CHECK(tmp.alloc(&dsums, 24));
+    SF_CHECK(tmp.alloc(&dsums, RS_SIZE));
     SF_HIP(hipMemcpyAsync(dRt, Rt, 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     double lo, hi;
     sf_ransac_band(thr, &lo, &hi);
@@ -332,9 +305,9 @@ extern "C" int sf_ransac_refit_sums(sf_ctx *ctx, const double *a_dev, const doub
               (const double *)nullptr, partial);
     SF_LAUNCH(ctx, "k11_sums_final", k11_sums_final, dim3(1), dim3(64), (const double *)partial, K11_SUM_BLOCKS, 0, dsums);
     SF_LAUNCH(ctx, "k11_pair_sums", k11_pair_sums<1>, grid, block, a_dev, b_dev, m, (const double *)dRt, thr, lo, hi,
-              (const double *)(dsums + 1), partial);
+              (const double *)(dsums + RS_ABAR), partial);
     SF_LAUNCH(ctx, "k11_sums_final", k11_sums_final, dim3(1), dim3(64), (const double *)partial, K11_SUM_BLOCKS, 1, dsums);
-    SF_HIP(hipMemcpyAsync(sums, dsums, 24 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipMemcpyAsync(sums, dsums, RS_SIZE * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream)); // Rt and sums are host buffers
     return SF_OK;
 }
