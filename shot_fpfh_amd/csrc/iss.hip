@@ -7,10 +7,10 @@
 //
 // Mapping: the covariances are K2 + K3's fused sweep (search.hip::k_radius_cov, unchanged, with its count output switched on);
 // k_iss_saliency is one eigen-solve per lane on top (eigh3.h; K4's note on one-thread solves applies, the stage is small);
-// k_iss_nms is K2's candidate sweep -- four queries per wave, run tables per 16-lane row, candidate pairs, the conservative
-// x window -- that reads the candidates' saliency next to their coordinates (a fourth coalesced 16-byte load: the array sits
-// in the cell-sorted order of xs / ys / zs) and keeps two wave-wide facts per query, the hit count and "some hit is strictly
-// larger".  No lists, no LDS ring: one int32 flag per point leaves the kernel.
+// k_iss_nms is the K2 family's candidate sweep (search_util.h) -- four queries per wave, run tables per 16-lane row, candidate
+// pairs, the conservative x window -- that reads the candidates' saliency next to their coordinates (a fourth coalesced
+// 16-byte load: the array sits in the cell-sorted order of xs / ys / zs) and keeps two wave-wide facts per query, the hit count
+// and "some hit is strictly larger".  No lists, no LDS ring: one int32 flag per point leaves the kernel.
 // What bounds it: the saliency pass is k_radius_cov (issue-bound sweep) + 1M eigen-solves; the suppression is the sweep of
 // K2's count pass with one more load per step and an early exit at the first larger hit.
 //
@@ -81,38 +81,9 @@ __global__ __launch_bounds__(64 * SF_ISS_WPB) void k_iss_nms(sf_grid_desc g, con
     stencil_bounds(pzv, g.lo[2], g.inv_cell, g.dim[2], z0, z1);
     __shared__ int4 runs[SF_ISS_WPB][4][12];
     int4(*const tabs)[12] = runs[threadIdx.x >> 6];
-    int first_slot = 0;
-    { // (the run tables of the four queries, all of them whatever their saliency: see search.hip::k_radius)
-        const int r = sl < 9 ? sl : 8;
-        const int cz = z0 + r / 3, cy = y0 + r % 3;
-        bool ok = sl < 9 && rw < nq && cz <= z1 && cy <= y1;
-        const int64_t row = ((int64_t)(ok ? cz : z0) * g.dim[1] + (ok ? cy : y0)) * g.dim[0];
-        const double pxr = pxv - g.lo[0], pyr = pyv - g.lo[1], pzr = pzv - g.lo[2];
-        const double by0 = (double)cy * g.cell, bz0 = (double)cz * g.cell;
-        const double slack_y = 1e-9 * g.cell + 1e-15 * (fabs(pyr) + by0 + g.cell);
-        const double slack_z = 1e-9 * g.cell + 1e-15 * (fabs(pzr) + bz0 + g.cell);
-        const double dy = fmax(fmax(by0 - pyr, pyr - (by0 + g.cell)) - slack_y, 0.0);
-        const double dz = fmax(fmax(bz0 - pzr, pzr - (bz0 + g.cell)) - slack_z, 0.0);
-        const double w2 = (r2 * (1.0 + 1e-9) - dy * dy) - dz * dz;
-        ok = ok && w2 >= 0.0;
-        const double w = sf_sqrt_fast(fmax(w2, 0.0)) * (1.0 + 1e-9) + 1e-9 * g.cell +
-                         1e-15 * (fabs(pxr) + (double)g.dim[0] * (g.cell / (double)g.xsub));
-        int s = 0, e = 0;
-        if (sl < 9) {
-            s = cell_start[row + sf_cell_coord(pxr - w, 0.0, g.inv_cell_x, g.dim[0])];
-            e = cell_start[row + sf_cell_coord(pxr + w, 0.0, g.inv_cell_x, g.dim[0]) + 1];
-        }
-        if (!ok) { s = 0; e = 0; }
-        const int base = s & ~1;
-        const int npairs = (e - base + 1) >> 1;
-        int inc = npairs;
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false); // row_shr:1
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false); // row_shr:2
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, false); // row_shr:4
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, false); // row_shr:8
-        first_slot = inc - npairs;
-        if (sl < 12) tabs[rw][sl] = make_int4(base - 2 * first_slot, s, e, first_slot);
-    }
+    int s, e; // (the run tables of the four queries, all of them whatever their saliency)
+    sf_k2_window(g, cell_start, pxv, pyv, pzv, r2, sl, rw < nq, y0, y1, z0, z1, s, e);
+    const int first_slot = sf_k2_store_runs(s, e, sl, tabs[rw]);
     __builtin_amdgcn_wave_barrier(); // the tables are written and read by this wave only
     for (int qi = 0; qi < nq; ++qi) {
         const int64_t q = q0 + qi;
@@ -128,24 +99,13 @@ __global__ __launch_bounds__(64 * SF_ISS_WPB) void k_iss_nms(sf_grid_desc g, con
             int total = 0;
             bool larger = false;
             for (int f0 = 0; f0 < nslots; f0 += 64) {
-                const int f = f0 + lane;
-                int r = f >= b4 ? 4 : 0;
-                r += f >= tab[r + 2].w ? 2 : 0;
-                r += f >= tab[r + 1].w ? 1 : 0;
-                r = f >= b8 ? 8 : r;
-                const int4 t = tab[r];
-                const bool live = f < nslots;
-                const int j = live ? t.x + 2 * f : 0; // idle lanes of the last step load pair 0 (always there)
-                const bool in0 = live & (j >= t.y), in1 = live & (j + 1 < t.z);
-                const double2 X = *reinterpret_cast<const double2 *>(xs + j);
-                const double2 Y = *reinterpret_cast<const double2 *>(ys + j);
-                const double2 Z = *reinterpret_cast<const double2 *>(zs + j);
-                const double2 S = *reinterpret_cast<const double2 *>(sal + j);
-                const double dxa = X.x - px, dya = Y.x - py, dza = Z.x - pz;
-                const double dxb = X.y - px, dyb = Y.y - py, dzb = Z.y - pz;
+                const sf_k2_pair c = sf_k2_load_pair(tab, b4, b8, nslots, f0 + lane, xs, ys, zs);
+                const double2 S = *reinterpret_cast<const double2 *>(sal + c.j);
+                const double dxa = c.X.x - px, dya = c.Y.x - py, dza = c.Z.x - pz;
+                const double dxb = c.X.y - px, dyb = c.Y.y - py, dzb = c.Z.y - pz;
                 const double d2a = (dxa * dxa + dya * dya) + dza * dza, d2b = (dxb * dxb + dyb * dyb) + dzb * dzb;
-                const bool hit0 = in0 & (d2a <= r2);
-                const bool hit1 = in1 & (d2b <= r2);
+                const bool hit0 = c.in0 & (d2a <= r2);
+                const bool hit1 = c.in1 & (d2b <= r2);
                 total += __popcll(__ballot(hit0)) + __popcll(__ballot(hit1));
                 if (__ballot((hit0 & (S.x > sq)) | (hit1 & (S.y > sq)))) { larger = true; break; } // (wave-uniform)
             }

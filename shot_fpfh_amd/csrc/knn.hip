@@ -115,13 +115,14 @@ __global__ __launch_bounds__(64) void k_knn(sf_grid_desc g, const int32_t *__res
 // --------------------------------------------------------------------------------------------------
 // k nearest neighbours for k <= 64 on K2's mapping (round 5; k_knn above -- one wave per query over the whole 27-cell stencil, the
 // k best pruned in LDS again and again -- took 3.7 ms per 1M queries at k = 30 against K2's 0.46 ms for lists of 110).
-// Set-up and sweep are k_radius's: four queries per wave, the run tables of all four built at once, runs clipped in x to what
-// the ball of radius R can reach, two candidates per lane and load.  The hits (d2 <= R^2) of a query go to an LDS list of
-// SF_KNN_CAP entries in scan order -- which is ascending POSITION order -- and ONE rank pass then orders them: entry e's rank
-// is the number of entries with a smaller d2 (every entry is broadcast from LDS once and compared by all lanes: two vector
-// instructions per entry and 64 lanes); entries of rank < k write themselves to slot `rank`.  Ties in d2 (duplicated points;
-// exact ties are otherwise one in millions) give equal ranks: a slot then stays empty, or k + 1 entries qualify -- both are
-// seen by one ballot, and the pass is repeated with the tie broken by position, KDTree.query's order here as in k_knn.
+// Set-up and sweep are the K2 family's (search_util.h): four queries per wave, the run tables of all four built at once, runs
+// clipped in x to what the ball of radius R can reach, two candidates per lane and load.  The hits (d2 <= R^2) of a query go
+// to an LDS list of SF_KNN_CAP entries in scan order -- which is ascending POSITION order -- and ONE rank pass then orders
+// them: entry e's rank is the number of entries with a smaller d2 (every entry is broadcast from LDS once and compared by all
+// lanes: two vector instructions per entry and 64 lanes); entries of rank < k write themselves to slot `rank`.  Ties in d2
+// (duplicated points; exact ties are otherwise one in millions) give equal ranks: a slot then stays empty, or k + 1 entries
+// qualify -- both are seen by one ballot, and the pass is repeated with the tie broken by position, KDTree.query's order here
+// as in k_knn.
 // Two cuts in front of the rank pass: (a) a list of more than 80 entries is first reduced to the entries at or below an UPPER
 // BOUND of the k-th smallest d2 -- the largest of the k smallest of a 64-entry subset (every stride-th entry, ranked among
 // themselves): 64 compare steps buy a rank pass over ~ k x length / 64 entries instead of `length` x 2 tiers; (b) a query with
@@ -177,38 +178,9 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_knn4(sf_grid_desc g, const i
     double *const kd = kd_all[threadIdx.x >> 6];
     int *const kj = kj_all[threadIdx.x >> 6];
     int *const ks = ks_all[threadIdx.x >> 6];
-    int first_slot = 0;
-    { // (the run tables: k_radius, which has the reasoning)
-        const int r = sl < 9 ? sl : 8;
-        const int cz = z0 + r / 3, cy = y0 + r % 3;
-        bool ok = sl < 9 && rw < nq && cz <= z1 && cy <= y1;
-        const int64_t row = ((int64_t)(ok ? cz : z0) * g.dim[1] + (ok ? cy : y0)) * g.dim[0];
-        const double pxr = pxv - g.lo[0], pyr = pyv - g.lo[1], pzr = pzv - g.lo[2];
-        const double by0 = (double)cy * g.cell, bz0 = (double)cz * g.cell;
-        const double slack_y = 1e-9 * g.cell + 1e-15 * (fabs(pyr) + by0 + g.cell);
-        const double slack_z = 1e-9 * g.cell + 1e-15 * (fabs(pzr) + bz0 + g.cell);
-        const double dy = fmax(fmax(by0 - pyr, pyr - (by0 + g.cell)) - slack_y, 0.0);
-        const double dz = fmax(fmax(bz0 - pzr, pzr - (bz0 + g.cell)) - slack_z, 0.0);
-        const double w2 = (r2 * (1.0 + 1e-9) - dy * dy) - dz * dz;
-        ok = ok && w2 >= 0.0;
-        const double w = sf_sqrt_fast(fmax(w2, 0.0)) * (1.0 + 1e-9) + 1e-9 * g.cell +
-                         1e-15 * (fabs(pxr) + (double)g.dim[0] * (g.cell / (double)g.xsub));
-        int s = 0, e = 0;
-        if (sl < 9) {
-            s = cell_start[row + sf_cell_coord(pxr - w, 0.0, g.inv_cell_x, g.dim[0])];
-            e = cell_start[row + sf_cell_coord(pxr + w, 0.0, g.inv_cell_x, g.dim[0]) + 1];
-        }
-        if (!ok) { s = 0; e = 0; }
-        const int base = s & ~1;
-        const int npairs = (e - base + 1) >> 1;
-        int inc = npairs;
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, false);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, false);
-        first_slot = inc - npairs;
-        if (sl < 12) tabs[rw][sl] = make_int4(base - 2 * first_slot, s, e, first_slot);
-    }
+    int s, e;
+    sf_k2_window(g, cell_start, pxv, pyv, pzv, r2, sl, rw < nq, y0, y1, z0, z1, s, e);
+    const int first_slot = sf_k2_store_runs(s, e, sl, tabs[rw]);
     __builtin_amdgcn_wave_barrier();
     for (int qi = 0; qi < nq; ++qi) {
         const int64_t q = SEL ? (int64_t)sf_uniform(__shfl((int)qm, 16 * qi)) : q0 + qi;
@@ -221,28 +193,16 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_knn4(sf_grid_desc g, const i
         auto sweep = [&](double thr2) -> int {
             int total = 0;
             for (int f0 = 0; f0 < nslots; f0 += 64) {
-                const int f = f0 + lane;
-                int r = f >= b4 ? 4 : 0;
-                r += f >= tab[r + 2].w ? 2 : 0;
-                r += f >= tab[r + 1].w ? 1 : 0;
-                r = f >= b8 ? 8 : r;
-                const int4 t = tab[r];
-                const bool live = f < nslots;
-                const int j = live ? t.x + 2 * f : 0;
-                const bool in0 = live & (j >= t.y), in1 = live & (j + 1 < t.z);
-                const double2 X = *reinterpret_cast<const double2 *>(xs + j);
-                const double2 Y = *reinterpret_cast<const double2 *>(ys + j);
-                const double2 Z = *reinterpret_cast<const double2 *>(zs + j);
-                const double dxa = X.x - px, dya = Y.x - py, dza = Z.x - pz;
-                const double dxb = X.y - px, dyb = Y.y - py, dzb = Z.y - pz;
+                const sf_k2_pair c = sf_k2_load_pair(tab, b4, b8, nslots, f0 + lane, xs, ys, zs);
+                const double dxa = c.X.x - px, dya = c.Y.x - py, dza = c.Z.x - pz;
+                const double dxb = c.X.y - px, dyb = c.Y.y - py, dzb = c.Z.y - pz;
                 const double d2a = (dxa * dxa + dya * dya) + dza * dza, d2b = (dxb * dxb + dyb * dyb) + dzb * dzb;
-                const bool hit0 = in0 & (d2a <= thr2);
-                const bool hit1 = in1 & (d2b <= thr2);
+                const bool hit0 = c.in0 & (d2a <= thr2);
+                const bool hit1 = c.in1 & (d2b <= thr2);
                 const unsigned long long m0 = __ballot(hit0), m1 = __ballot(hit1);
-                const int pos = total + sf_prefix_count(m0) + sf_prefix_count(m1);
-                const int pos1 = pos + (hit0 ? 1 : 0);
-                if (hit0 && pos < SF_KNN_CAP) { kd[pos] = d2a; kj[pos] = j; }
-                if (hit1 && pos1 < SF_KNN_CAP) { kd[pos1] = d2b; kj[pos1] = j + 1; }
+                const int2 pos = sf_k2_hit_pos(total, m0, m1, hit0);
+                if (hit0 && pos.x < SF_KNN_CAP) { kd[pos.x] = d2a; kj[pos.x] = c.j; }
+                if (hit1 && pos.y < SF_KNN_CAP) { kd[pos.y] = d2b; kj[pos.y] = c.j + 1; }
                 total += __popcll(m0) + __popcll(m1);
             }
             __builtin_amdgcn_wave_barrier(); // (the list is written and read by this wave only; its LDS operations stay in order)

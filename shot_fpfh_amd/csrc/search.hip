@@ -38,17 +38,7 @@ sf_grid_desc sf_make_grid_desc(const sf_cloud *c)
 
 namespace {
 
-// MODE 0: count only.  MODE 1: fill at the exact CSR offsets of a previous count + scan.
-// MODE 2: optimistic single pass -- query q owns the fixed slot [q*cap, (q+1)*cap) of idx; hits beyond cap
-//         are counted but not stored, and the host falls back to the exact two-pass scheme if any list
-//         overflowed (HBM is plentiful: slots cost cap*4 B per query).
-#ifndef SF_K2_STAGE
-#define SF_K2_STAGE 1 // list entries leave through an LDS ring, 64 positions (256 aligned bytes) per store
-#endif
-#ifndef SF_K2_WPB
-#define SF_K2_WPB 8 // waves per workgroup, four queries each (0.521 / 0.516 / 0.498 / 0.489 ms at C3 for 1 / 2 / 4 / 8)
-#endif
-
+// MODE: search_util.h.
 // SEL: the launch serves the `m` queries named by qsel (processing slots) instead of queries 0 .. m - 1 -- the sample a
 // search sizes its slots from (MODE 0: counts go to the COMPACT array count[0 .. m)), and the queries whose lists overflowed
 // their slot (MODE 1: fill at offset[q], which by then points into the overflow area).
@@ -79,86 +69,40 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
     int y0, y1, z0, z1;
     stencil_bounds(pyv, g.lo[1], g.inv_cell, g.dim[1], y0, y1);
     stencil_bounds(pzv, g.lo[2], g.inv_cell, g.dim[2], z0, z1);
-    // The stencil is up to 9 runs of consecutive positions, one per (cz, cy) row of cells.  The runs are laid end to
-    // end in units of candidate PAIRS (a pair = one even-aligned 16-byte load) and every step of a sweep takes the next
-    // 64 pairs, whichever runs they fall in.  Everything a lane needs to find its pair is vector work -- a DPP scan
-    // gives the runs' first pair slots, the table goes to LDS -- because the scalar unit is shared by the whole CU.
     __shared__ int4 runs[SF_K2_WPB][4][12];
-#if SF_K2_STAGE
+    // Hits go to a 256-entry ring in LDS first and leave for HBM 64 list positions at a time: a sweep step finds ~14 hits
+    // of its 128 candidates, and 14 x 4 B stored past the L2 (`nt`) is a partial line each time -- the counters showed
+    // 2.2 x the lists' bytes written.  Whole, aligned 256-byte runs instead (slots start on 128-byte boundaries).
     __shared__ int stages[MODE != 0 ? SF_K2_WPB : 1][SHARE ? 4 : 1][256];
-#endif
-    static_assert(!SHARE || (MODE == 2 && !SEL && SF_K2_STAGE), "the shared sweep serves the single sweep into slots");
+    static_assert(!SHARE || (MODE == 2 && !SEL), "the shared sweep serves the single sweep into slots");
     int4(*const tabs)[12] = runs[threadIdx.x >> 6];
-    int first_slot = 0; // lane r < 9 of a row: first pair slot of run r; lane 9: the total
     bool share = false; // (wave-uniform) one sweep over the union of the four queries' windows
-    {
-        const int r = sl < 9 ? sl : 8;
-        const int cz = z0 + r / 3, cy = y0 + r % 3;
-        bool ok = sl < 9 && rw < nq && cz <= z1 && cy <= y1;
-        const int64_t row = ((int64_t)(ok ? cz : z0) * g.dim[1] + (ok ? cy : y0)) * g.dim[0];
-        // The row (cy, cz) of cells is the band [lo + c edge, lo + (c + 1) edge) in y and in z.  A point of it within r
-        // of the query is at least (dy, dz) away in those two axes -- the gaps between the query and the bands -- so
-        // its x lies within w = sqrt(r^2 - dy^2 - dz^2) of the query's: only the FINE x cells (xsub per edge) that
-        // [px - w, px + w] touches are swept, 12-14 edge-lengths of cells per query instead of 27.  The cell of a
-        // coordinate is a monotone function of it, so every point with px - w <= x <= px + w lies in a cell between
-        // the cells of the two ends; the gaps shrink and w grows by a slack that is far above any rounding involved (next
-        // paragraph), so the sweep can only be wider than necessary, never narrower.
-        // All of it in GRID-RELATIVE coordinates (p - lo, what the cell assignment itself uses): the rounding of a relative
-        // coordinate, of a band edge c * cell and of fl(1 / cell) is a few ulps of the grid's EXTENT, whereas band edges
-        // and px +- w formed in absolute coordinates would round by ulps of |lo| and |p| -- for a cloud in UTM-like
-        // coordinates (1e6 .. 1e7 with a cell of 1e-2) far more than any fixed fraction of the cell.  `slack` covers both: 1e-9
-        // of the cell plus 1e-15 of the relative coordinates involved.
-        const double pxr = pxv - g.lo[0], pyr = pyv - g.lo[1], pzr = pzv - g.lo[2];
-        const double by0 = (double)cy * g.cell, bz0 = (double)cz * g.cell;
-        const double slack_y = 1e-9 * g.cell + 1e-15 * (fabs(pyr) + by0 + g.cell);
-        const double slack_z = 1e-9 * g.cell + 1e-15 * (fabs(pzr) + bz0 + g.cell);
-        const double dy = fmax(fmax(by0 - pyr, pyr - (by0 + g.cell)) - slack_y, 0.0);
-        const double dz = fmax(fmax(bz0 - pzr, pzr - (bz0 + g.cell)) - slack_z, 0.0);
-        const double w2 = (r2 * (1.0 + 1e-9) - dy * dy) - dz * dz;
-        ok = ok && w2 >= 0.0;
-        const double w = sf_sqrt_fast(fmax(w2, 0.0)) * (1.0 + 1e-9) + 1e-9 * g.cell +
-                         1e-15 * (fabs(pxr) + (double)g.dim[0] * (g.cell / (double)g.xsub));
-        int s = 0, e = 0;
-        if (sl < 9) {
-            s = cell_start[row + sf_cell_coord(pxr - w, 0.0, g.inv_cell_x, g.dim[0])];
-            e = cell_start[row + sf_cell_coord(pxr + w, 0.0, g.inv_cell_x, g.dim[0]) + 1];
+    int s, e;
+    sf_k2_window(g, cell_start, pxv, pyv, pzv, r2, sl, rw < nq, y0, y1, z0, z1, s, e);
+    if (SHARE) {
+        // The four queries are consecutive in cell-sorted order: except at row ends they have the same stencil rows, a few
+        // fine x cells apart, and their windows overlap almost entirely.  With identical (y0, y1, z0, z1) run r is the same
+        // row of cells for all four, and the wave sweeps, once, the UNION of the four windows per row: from the smallest s to
+        // the largest e over the queries whose own run is not empty (a row no query reaches stays empty).  Every 16-lane
+        // row then builds, and the sweep reads, that one table.
+        // No per-query window test follows: by the derivation of w (sf_k2_window, slack included) every point of the row within
+        // r of query q lies inside q's OWN window, so a candidate of the union outside it fails q's distance test -- the
+        // test alone decides, on the same expression, and each list is the per-query sweep's entry for entry.
+        const bool same = y0 == sf_uniform(y0) && y1 == sf_uniform(y1) && z0 == sf_uniform(z0) && z1 == sf_uniform(z1);
+        share = nq == 4 && __ballot(same) == ~0ull;
+        if (share) {
+            int us = e > s ? s : 0x7fffffff, ue = e > s ? e : 0;
+            us = min(us, __shfl_xor(us, 16));
+            ue = max(ue, __shfl_xor(ue, 16));
+            us = min(us, __shfl_xor(us, 32));
+            ue = max(ue, __shfl_xor(ue, 32));
+            s = ue ? us : 0;
+            e = ue;
         }
-        if (!ok) { s = 0; e = 0; }
-        if (SHARE) {
-            // The four queries are consecutive in cell-sorted order: except at row ends they have the same stencil rows, a few
-            // fine x cells apart, and their windows overlap almost entirely.  With identical (y0, y1, z0, z1) run r is the same
-            // row of cells for all four, and the wave sweeps, once, the UNION of the four windows per row: from the smallest s to
-            // the largest e over the queries whose own run is not empty (a row no query reaches stays empty).  Every 16-lane
-            // row then builds, and the sweep reads, that one table.
-            // No per-query window test follows: by the derivation of w above (slack included) every point of the row within r
-            // of query q lies inside q's OWN window, so a candidate of the union outside it fails q's distance test -- the
-            // test alone decides, on the same expression, and each list is the per-query sweep's entry for entry.
-            const bool same = y0 == sf_uniform(y0) && y1 == sf_uniform(y1) && z0 == sf_uniform(z0) && z1 == sf_uniform(z1);
-            share = nq == 4 && __ballot(same) == ~0ull;
-            if (share) {
-                int us = e > s ? s : 0x7fffffff, ue = e > s ? e : 0;
-                us = min(us, __shfl_xor(us, 16));
-                ue = max(ue, __shfl_xor(ue, 16));
-                us = min(us, __shfl_xor(us, 32));
-                ue = max(ue, __shfl_xor(ue, 32));
-                s = ue ? us : 0;
-                e = ue;
-            }
-        }
-        const int base = s & ~1; // pairs start at an EVEN position: every 16-byte load is naturally aligned
-        const int npairs = (e - base + 1) >> 1;
-        // inclusive scan of npairs inside the 16-lane row (row_shr DPP steps), then exclusive = inclusive - own
-        int inc = npairs;
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false); // row_shr:1
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false); // row_shr:2
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, false); // row_shr:4
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, false); // row_shr:8
-        first_slot = inc - npairs;
-        if (sl < 12) tabs[rw][sl] = make_int4(base - 2 * first_slot, s, e, first_slot); // j = .x + 2 * slot; .w: first slot
     }
+    const int first_slot = sf_k2_store_runs(s, e, sl, tabs[rw]); // lane r < 9 of a row: first pair slot of run r; lane 9: the total
     __builtin_amdgcn_wave_barrier(); // the tables are written and read by this wave only
     if (DBG && lane == 0) atomicAdd(&sf_k2_paths[share ? 0 : 1], 1ull);
-#if SF_K2_STAGE
     if (SHARE && share) {
         // ---- the shared sweep: per step ONE run look-up, ONE j, ONE pair of bounds masks and the three loads; then, per query,
         // the distance test as below and the query's own compaction -- running total (a scalar), ballot pair, ring, flush.
@@ -179,34 +123,23 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
         }
         int32_t *const out0 = idx + q0 * (int64_t)cap; // query q0 + qi owns [qi * cap, (qi + 1) * cap) from here
         for (int f0 = 0; f0 < nslots; f0 += 64) {
-            const int f = f0 + lane;
-            int r = f >= b4 ? 4 : 0; // (the look-up of the per-query sweep, on the union's table)
-            r += f >= tab[r + 2].w ? 2 : 0;
-            r += f >= tab[r + 1].w ? 1 : 0;
-            r = f >= b8 ? 8 : r;
-            const int4 t = tab[r];
-            const bool live = f < nslots;
-            const int j = live ? t.x + 2 * f : 0;
-            const bool in0 = live & (j >= t.y), in1 = live & (j + 1 < t.z);
-            const double2 X = *reinterpret_cast<const double2 *>(xs + j);
-            const double2 Y = *reinterpret_cast<const double2 *>(ys + j);
-            const double2 Z = *reinterpret_cast<const double2 *>(zs + j);
-            const unsigned long long i0 = __builtin_amdgcn_ballot_w64(in0), i1 = __builtin_amdgcn_ballot_w64(in1);
+            const sf_k2_pair c = sf_k2_load_pair(tab, b4, b8, nslots, f0 + lane, xs, ys, zs); // (on the union's table)
+            const int j = c.j;
+            const unsigned long long i0 = __builtin_amdgcn_ballot_w64(c.in0), i1 = __builtin_amdgcn_ballot_w64(c.in1);
 #pragma unroll
             for (int qi = 0; qi < 4; ++qi) {
-                const double dxa = X.x - px[qi], dya = Y.x - py[qi], dza = Z.x - pz[qi];
-                const double dxb = X.y - px[qi], dyb = Y.y - py[qi], dzb = Z.y - pz[qi];
+                const double dxa = c.X.x - px[qi], dya = c.Y.x - py[qi], dza = c.Z.x - pz[qi];
+                const double dxb = c.X.y - px[qi], dyb = c.Y.y - py[qi], dzb = c.Z.y - pz[qi];
                 const double d2a = (dxa * dxa + dya * dya) + dza * dza, d2b = (dxb * dxb + dyb * dyb) + dzb * dzb;
-                const bool hit0 = in0 & (d2a <= r2);
-                const bool hit1 = in1 & (d2b <= r2);
+                const bool hit0 = c.in0 & (d2a <= r2);
+                const bool hit1 = c.in1 & (d2b <= r2);
                 // (the ballot of a bare comparison IS the lane mask the comparison leaves, and the bounds join it on the scalar
                 // unit; the ballot of hit0 itself goes through a vector select and a second comparison)
                 const unsigned long long m0 = __builtin_amdgcn_ballot_w64(d2a <= r2) & i0, m1 = __builtin_amdgcn_ballot_w64(d2b <= r2) & i1;
                 int *const stage = stages[threadIdx.x >> 6][qi];
-                const int pos = total[qi] + sf_prefix_count(m0) + sf_prefix_count(m1);
-                const int pos1 = pos + (hit0 ? 1 : 0);
-                if (hit0 && pos < cap) stage[pos & 255] = j;
-                if (hit1 && pos1 < cap) stage[pos1 & 255] = j + 1;
+                const int2 pos = sf_k2_hit_pos(total[qi], m0, m1, hit0);
+                if (hit0 && pos.x < cap) stage[pos.x & 255] = j;
+                if (hit1 && pos.y < cap) stage[pos.y & 255] = j + 1;
                 total[qi] += __popcll(m0) + __popcll(m1);
                 const int have = total[qi] < cap ? total[qi] : cap; // (at most 63 + 128 positions pending: see below)
                 while (have - flushed[qi] >= 64) {
@@ -232,7 +165,6 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
         }
         return;
     }
-#endif
     for (int qi = 0; qi < nq; ++qi) {
         const int64_t q = SEL ? (int64_t)sf_uniform(__shfl((int)qm, 16 * qi)) : q0 + qi;
         const int4 *const tab = tabs[qi];
@@ -247,50 +179,25 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
         int total = 0;
         const int64_t out = MODE == 1 ? offset[q] : q * (int64_t)cap;
         const int room = MODE == 2 ? cap : 0x7fffffff;
-#if SF_K2_STAGE
-        // Hits go to a 256-entry ring in LDS first and leave for HBM 64 list positions at a time: a sweep step finds ~14 hits
-        // of its 128 candidates, and 14 x 4 B stored past the L2 (`nt`) is a partial line each time -- the counters showed
-        // 2.2 x the lists' bytes written.  Whole, aligned 256-byte runs instead (slots start on 128-byte boundaries).
         int *const stage = stages[threadIdx.x >> 6][0];
         int flushed = 0; // list positions [0, flushed) are in HBM; a multiple of 64
-#endif
         for (int f0 = 0; f0 < nslots; f0 += 64) {
-            const int f = f0 + lane;
-            // run of slot f = last run whose first slot is <= f: a three-level binary search, the first level against a
-            // scalar, the other two against the first-slot column of the table in LDS (an LDS read costs the vector
-            // pipe one instruction; eight compare-and-add pairs cost it sixteen and more)
-            int r = f >= b4 ? 4 : 0;
-            r += f >= tab[r + 2].w ? 2 : 0;
-            r += f >= tab[r + 1].w ? 1 : 0;
-            r = f >= b8 ? 8 : r;
-            const int4 t = tab[r];
-            const bool live = f < nslots;
-            const int j = live ? t.x + 2 * f : 0; // idle lanes of the last step load pair 0 (always there)
-            const bool in0 = live & (j >= t.y), in1 = live & (j + 1 < t.z);
-            const double2 X = *reinterpret_cast<const double2 *>(xs + j);
-            const double2 Y = *reinterpret_cast<const double2 *>(ys + j);
-            const double2 Z = *reinterpret_cast<const double2 *>(zs + j);
-            const double dxa = X.x - px, dya = Y.x - py, dza = Z.x - pz;
-            const double dxb = X.y - px, dyb = Y.y - py, dzb = Z.y - pz;
+            const sf_k2_pair c = sf_k2_load_pair(tab, b4, b8, nslots, f0 + lane, xs, ys, zs);
+            const int j = c.j;
+            const double dxa = c.X.x - px, dya = c.Y.x - py, dza = c.Z.x - pz;
+            const double dxb = c.X.y - px, dyb = c.Y.y - py, dzb = c.Z.y - pz;
             // both distances are evaluated unconditionally (bitwise &): a short-circuit would let the compiler
             // sink half of each 16-byte load into a branch and split it into two 8-byte loads
             const double d2a = (dxa * dxa + dya * dya) + dza * dza, d2b = (dxb * dxb + dyb * dyb) + dzb * dzb;
-            const bool hit0 = in0 & (d2a <= r2);
-            const bool hit1 = in1 & (d2b <= r2);
+            const bool hit0 = c.in0 & (d2a <= r2);
+            const bool hit1 = c.in1 & (d2b <= r2);
             const unsigned long long m0 = __ballot(hit0), m1 = __ballot(hit1);
             if (MODE != 0) {
-                const int pos = total + sf_prefix_count(m0) + sf_prefix_count(m1);
-                const int pos1 = pos + (hit0 ? 1 : 0);
-#if SF_K2_STAGE
-                if (hit0 && pos < room) stage[pos & 255] = j;
-                if (hit1 && pos1 < room) stage[pos1 & 255] = j + 1;
-#else
-                if (hit0 && pos < room) SF_LIST_STORE(idx + out + pos, j);
-                if (hit1 && pos1 < room) SF_LIST_STORE(idx + out + pos1, j + 1);
-#endif
+                const int2 pos = sf_k2_hit_pos(total, m0, m1, hit0);
+                if (hit0 && pos.x < room) stage[pos.x & 255] = j;
+                if (hit1 && pos.y < room) stage[pos.y & 255] = j + 1;
             }
             total += __popcll(m0) + __popcll(m1);
-#if SF_K2_STAGE
             if (MODE != 0) { // (at most 63 + 128 positions are pending here: the ring of 256 never wraps onto them)
                 const int have = total < room ? total : room;
                 while (have - flushed >= 64) {
@@ -298,14 +205,11 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
                     flushed += 64;
                 }
             }
-#endif
         }
-#if SF_K2_STAGE
         if (MODE != 0) {
             const int have = total < room ? total : room;
             if (flushed + lane < have) SF_LIST_STORE(idx + out + flushed + lane, stage[(flushed + lane) & 255]);
         }
-#endif
         if (lane == 0) {
             if (MODE != 1) {
                 count[SEL ? q0 + qi : q] = total;
@@ -328,7 +232,7 @@ __global__ __launch_bounds__(64 * SF_K2_WPB) void k_radius(sf_grid_desc g, const
 // their gather ever touch HBM.  Lists of at most SF_K2C_LIST points sit in LDS whole (4.6 KB per wave); a longer one (wave-uniform,
 // per query) is swept twice more through the same LDS as a ring -- whenever 64 consecutive list positions are complete the
 // lanes consume them -- once for the barycentre, once for the moments: the streaming form of k_pca_cov, again bit for bit.
-// Set-up and sweep are k_radius's (four queries per wave, run tables per 16-lane row, candidate pairs).
+// Set-up and sweep are the K2 family's (search_util.h: four queries per wave, run tables per 16-lane row, candidate pairs).
 // --------------------------------------------------------------------------------------------------
 #ifndef SF_K2C_WPB
 #define SF_K2C_WPB 4
@@ -358,38 +262,9 @@ __global__ __launch_bounds__(64 * SF_K2C_WPB) __attribute__((amdgpu_waves_per_eu
     __shared__ sf_cov_list lists[SF_K2C_WPB];
     int4(*const tabs)[12] = runs[threadIdx.x >> 6];
     sf_cov_list &L = lists[threadIdx.x >> 6];
-    int first_slot = 0;
-    { // (the run tables: see k_radius)
-        const int r = sl < 9 ? sl : 8;
-        const int cz = z0 + r / 3, cy = y0 + r % 3;
-        bool ok = sl < 9 && rw < nq && cz <= z1 && cy <= y1;
-        const int64_t row = ((int64_t)(ok ? cz : z0) * g.dim[1] + (ok ? cy : y0)) * g.dim[0];
-        const double pxr = pxv - g.lo[0], pyr = pyv - g.lo[1], pzr = pzv - g.lo[2];
-        const double by0 = (double)cy * g.cell, bz0 = (double)cz * g.cell;
-        const double slack_y = 1e-9 * g.cell + 1e-15 * (fabs(pyr) + by0 + g.cell);
-        const double slack_z = 1e-9 * g.cell + 1e-15 * (fabs(pzr) + bz0 + g.cell);
-        const double dy = fmax(fmax(by0 - pyr, pyr - (by0 + g.cell)) - slack_y, 0.0);
-        const double dz = fmax(fmax(bz0 - pzr, pzr - (bz0 + g.cell)) - slack_z, 0.0);
-        const double w2 = (r2 * (1.0 + 1e-9) - dy * dy) - dz * dz;
-        ok = ok && w2 >= 0.0;
-        const double w = sf_sqrt_fast(fmax(w2, 0.0)) * (1.0 + 1e-9) + 1e-9 * g.cell +
-                         1e-15 * (fabs(pxr) + (double)g.dim[0] * (g.cell / (double)g.xsub));
-        int s = 0, e = 0;
-        if (sl < 9) {
-            s = cell_start[row + sf_cell_coord(pxr - w, 0.0, g.inv_cell_x, g.dim[0])];
-            e = cell_start[row + sf_cell_coord(pxr + w, 0.0, g.inv_cell_x, g.dim[0]) + 1];
-        }
-        if (!ok) { s = 0; e = 0; }
-        const int base = s & ~1;
-        const int npairs = (e - base + 1) >> 1;
-        int inc = npairs;
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, false);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, false);
-        first_slot = inc - npairs;
-        if (sl < 12) tabs[rw][sl] = make_int4(base - 2 * first_slot, s, e, first_slot);
-    }
+    int s, e;
+    sf_k2_window(g, cell_start, pxv, pyv, pzv, r2, sl, rw < nq, y0, y1, z0, z1, s, e);
+    const int first_slot = sf_k2_store_runs(s, e, sl, tabs[rw]);
     __builtin_amdgcn_wave_barrier();
 #define SF_K2C_LDS_SYNC()                                                                                            \
     do {                                                                                                            \
@@ -408,29 +283,17 @@ __global__ __launch_bounds__(64 * SF_K2C_WPB) __attribute__((amdgpu_waves_per_eu
         auto sweep = [&](int keep, bool wrap, auto &&after_step) -> int { // wrap: L is a ring (positions modulo its size)
             int total = 0;
             for (int f0 = 0; f0 < nslots; f0 += 64) {
-                const int f = f0 + lane;
-                int r = f >= b4 ? 4 : 0;
-                r += f >= tab[r + 2].w ? 2 : 0;
-                r += f >= tab[r + 1].w ? 1 : 0;
-                r = f >= b8 ? 8 : r;
-                const int4 t = tab[r];
-                const bool live = f < nslots;
-                const int j = live ? t.x + 2 * f : 0;
-                const bool in0 = live & (j >= t.y), in1 = live & (j + 1 < t.z);
-                const double2 X = *reinterpret_cast<const double2 *>(xs + j);
-                const double2 Y = *reinterpret_cast<const double2 *>(ys + j);
-                const double2 Z = *reinterpret_cast<const double2 *>(zs + j);
-                const double dxa = X.x - px, dya = Y.x - py, dza = Z.x - pz;
-                const double dxb = X.y - px, dyb = Y.y - py, dzb = Z.y - pz;
+                const sf_k2_pair c = sf_k2_load_pair(tab, b4, b8, nslots, f0 + lane, xs, ys, zs);
+                const double dxa = c.X.x - px, dya = c.Y.x - py, dza = c.Z.x - pz;
+                const double dxb = c.X.y - px, dyb = c.Y.y - py, dzb = c.Z.y - pz;
                 const double d2a = (dxa * dxa + dya * dya) + dza * dza, d2b = (dxb * dxb + dyb * dyb) + dzb * dzb;
-                const bool hit0 = in0 & (d2a <= r2);
-                const bool hit1 = in1 & (d2b <= r2);
+                const bool hit0 = c.in0 & (d2a <= r2);
+                const bool hit1 = c.in1 & (d2b <= r2);
                 const unsigned long long m0 = __ballot(hit0), m1 = __ballot(hit1);
-                const int pos = total + sf_prefix_count(m0) + sf_prefix_count(m1);
-                const int pos1 = pos + (hit0 ? 1 : 0);
-                const int s0 = wrap ? pos % SF_K2C_LIST : pos, s1 = wrap ? pos1 % SF_K2C_LIST : pos1;
-                if (hit0 && pos < keep) { L.x[s0] = dxa; L.y[s0] = dya; L.z[s0] = dza; }
-                if (hit1 && pos1 < keep) { L.x[s1] = dxb; L.y[s1] = dyb; L.z[s1] = dzb; }
+                const int2 pos = sf_k2_hit_pos(total, m0, m1, hit0);
+                const int s0 = wrap ? pos.x % SF_K2C_LIST : pos.x, s1 = wrap ? pos.y % SF_K2C_LIST : pos.y;
+                if (hit0 && pos.x < keep) { L.x[s0] = dxa; L.y[s0] = dya; L.z[s0] = dza; }
+                if (hit1 && pos.y < keep) { L.x[s1] = dxb; L.y[s1] = dyb; L.z[s1] = dzb; }
                 total += __popcll(m0) + __popcll(m1);
                 after_step(total);
             }

@@ -34,6 +34,10 @@ CLOUDS = {
     "clustered": (lambda: _family("clustered"), 0.05, 0.03),
     "uniform_rn_3rs": (lambda: synth_cloud(20000, 7)[0], 0.03, 0.09),  # r_n > r_s: the suppression needs another grid
     "uniform_rs_3rn": (lambda: synth_cloud(20000, 7)[0], 0.09, 0.03),  # r_s / r_n = 3: the saliency grid is too coarse to keep
+    # a wave serves four points: last waves of one, two and three points (35 947 above: three), balls of up to several hundred
+    "last_wave_of_1": (lambda: synth_cloud(2001, 7)[0], 0.4, 0.15),
+    "last_wave_of_2": (lambda: synth_cloud(2002, 7)[0], 0.15, 0.4),
+    "three_points": (lambda: synth_cloud(3, 7)[0], 2.0, 2.0),  # ... and a wave that is the whole launch
 }
 
 _cache = {}
@@ -92,6 +96,8 @@ def test_suppression_is_exact_on_the_devices_own_saliency(name, engine):
         # any score will do: many exact ties and negatives
         score = (np.arange(p.shape[0]) % 7 - 2).astype(np.float64)
         assert np.array_equal(cloud.iss_select(score, r_n), N.select(p, score, r_n))
+        assert np.array_equal(cloud.iss_select(score, r_n, min_neighbors=1), N.select(p, score, r_n, min_neighbors=1))
+        score = 1.0 + np.arange(p.shape[0]) % 5  # every point sweeps: no wave is skipped, ties everywhere
         assert np.array_equal(cloud.iss_select(score, r_n, min_neighbors=1), N.select(p, score, r_n, min_neighbors=1))
     finally:
         cloud.free()

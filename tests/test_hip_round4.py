@@ -338,11 +338,13 @@ def test_empty_block_takes_part_in_the_collective_statistics():
 
 
 # ---- compute_normals(radius) in one sweep --------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind", ["uniform", "surface", "blobs", "cap"])
+@pytest.mark.parametrize("kind", ["uniform", "surface", "blobs", "cap", "short_waves"])
 def test_fused_normals_sweep_is_bit_identical_to_search_plus_normals(eng, O, kind):
     """sf_normals_radius (hits reduced to the covariance in LDS, no lists) == sf_radius_search + sf_normals, bit for bit: the
     cloud's own points and coordinate queries, with and without pre_computed_normals, lists of up to 256 points (LDS list)
-    and longer ones (the ring: two more sweeps); and against the oracle."""
+    and longer ones (the ring: two more sweeps); and against the oracle.  short_waves: a wave serves four queries -- query
+    sets of 1, 2 and 3 (one short wave) and of 4 k + 1, 2, 3 (a short last wave), lists on both sides of the LDS list's size."""
+    blocks, query_sets = [(12000, 17000)], [(3000, 500)]  # positions [lo, hi) / (cloud points, points of the unit cube)
     if kind == "uniform":
         p, _, _ = synth_cloud(40000, 21)
         r = 0.06
@@ -352,38 +354,47 @@ def test_fused_normals_sweep_is_bit_identical_to_search_plus_normals(eng, O, kin
     elif kind == "blobs":
         p, _ = clustered(40000, seed=21)
         r = 0.016
-    else:
+    elif kind == "cap":
         p, _ = dense_cap(40000, seed=21)
         r = 0.025
+    else:
+        p, _, _ = synth_cloud(2001, 21)
+        r = 0.3
+        blocks = [(700, 701), (5, 7), (1200, 1203), (100, 105), (1998, 2001), (300, 307)]
+        query_sets = [(1, 0), (2, 0), (2, 1), (4, 1), (5, 1), (6, 1)]
     cloud = eng.cloud(p)
     nb = cloud.radius_search_self(r)
     cnt = nb.counts()
     if kind in ("blobs", "cap"):
         assert (cnt > 256).sum() > 100 and (cnt <= 256).sum() > 100
+    if kind == "short_waves":
+        assert (cnt > 192).sum() > 100 and (cnt <= 192).sum() > 100
     want = eng.empty((cloud.n, 3))
     nb.normals(out=want)
     got = eng.empty((cloud.n, 3))
     cloud.normals_radius_self(r, got)
     assert np.array_equal(got.to_host(), want.to_host())
     nb.free()
-    # a block of positions
-    part = eng.empty((5000, 3))
-    cloud.normals_radius_self(r, part, 12000, 17000)
-    assert np.array_equal(part.to_host(), want.to_host()[12000:17000])
+    for lo, hi in blocks:  # a block of positions
+        part = eng.empty((hi - lo, 3))
+        cloud.normals_radius_self(r, part, lo, hi)
+        assert np.array_equal(part.to_host(), want.to_host()[lo:hi])
+        part.free()
     # coordinate queries (off-cloud points among them), with pre_computed_normals
     rng = np.random.default_rng(2)
-    q = np.vstack([p[rng.choice(p.shape[0], 3000, replace=False)], rng.random((500, 3))])
-    pre = np.tile(np.array([[0.0, 0.0, 1.0]]), (q.shape[0], 1))
-    nbq = cloud.radius_search(q, r)
-    a = nbq.normals(pre)
-    b = cloud.normals_radius(q, r, pre)
-    has = nbq.counts() > 0
-    nbq.free()
-    assert np.array_equal(a[has], b[has])  # (queries without any neighbour: 0 / 0 on both paths)
-    ok = nbq_ok = has & (np.arange(q.shape[0]) < 3000)
-    wo = O.compute_normals(q[ok][:400], p, radius=r, pre_computed_normals=pre[ok][:400])
-    assert np.abs(b[ok][:400] - wo).max() < 1e-9
-    for obj in (want, got, part, cloud):
+    for n_cloud, n_cube in query_sets:
+        q = np.vstack([p[rng.choice(p.shape[0], n_cloud, replace=False)], rng.random((n_cube, 3))])
+        pre = np.tile(np.array([[0.0, 0.0, 1.0]]), (q.shape[0], 1))
+        nbq = cloud.radius_search(q, r)
+        a = nbq.normals(pre)
+        b = cloud.normals_radius(q, r, pre)
+        has = nbq.counts() > 0
+        nbq.free()
+        assert np.array_equal(a[has], b[has])  # (queries without any neighbour: 0 / 0 on both paths)
+        ok = has & (np.arange(q.shape[0]) < n_cloud)
+        wo = O.compute_normals(q[ok][:400], p, radius=r, pre_computed_normals=pre[ok][:400])
+        assert np.abs(b[ok][:400] - wo).max() < 1e-9
+    for obj in (want, got, cloud):
         obj.free()
 
 

@@ -96,36 +96,45 @@ def test_k2_lists_through_the_lds_ring(eng, O, monkeypatch, cap):
 
 # ---- k-NN on K2's mapping (k_knn4) ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("k", [1, 8, 30, 64])
-@pytest.mark.parametrize("kind", ["uniform", "blob", "duplicates", "surface"])
+@pytest.mark.parametrize("kind", ["uniform", "blob", "duplicates", "surface", "short_waves"])
 def test_knn_on_the_radius_search_mapping(eng, O, monkeypatch, kind, k):
     """k <= 64: four queries per wave, the points within R ranked in ONE pass (k_knn4), against brute force; normals computed from
     the lists against the oracle's.  Dense blob: queries with more than 256 points within R go to the one-wave-per-query kernel
-    at the same R; duplicated points: exact distance ties, broken by position; queries far outside the cloud: radius doublings."""
+    at the same R; duplicated points: exact distance ties, broken by position; queries far outside the cloud: radius doublings.
+    short_waves: query sets of 1, 2 and 3 (one short wave) and of 4 j + 1, 2, 3 (a short last wave), a dense spot among them."""
     from conftest import config1_cloud
     from shot_fpfh_amd.descriptors import compute_normals
 
     n, m = 30000, 4000
+    if kind == "short_waves":
+        n = 2000
     p, _, rng = synth_cloud(n, 61 + k)
-    if kind == "blob":
+    if kind in ("blob", "short_waves"):
         p[: n // 2] = 0.5 + 0.02 * (p[: n // 2] - 0.5)
     elif kind == "duplicates":
         p[1::3] = p[0:-1:3][: p[1::3].shape[0]]  # every third point sits on its predecessor
     elif kind == "surface":
         p, _ = config1_cloud(n, 61 + k)
-    q = np.vstack([p[rng.choice(n, m - 200, replace=False)], rng.random((200, 3)) * 3.0 - 1.0])
+    if kind == "short_waves":  # (half of a set from the dense spot, half from the background, one query outside the cloud)
+        query_sets = [np.vstack([p[: mq - mq // 2], p[n - mq // 2:]]) for mq in (1, 2, 3, 5, 6, 7)]
+        query_sets[-1][-1] = rng.random(3) * 3.0 - 1.0
+    else:
+        query_sets = [np.vstack([p[rng.choice(n, m - 200, replace=False)], rng.random((200, 3)) * 3.0 - 1.0])]
     cloud = eng.cloud(p)
     try:
-        nb = cloud.knn_search(q, k)
-        off, idx = nb.export()
+        for q in query_sets:
+            m = q.shape[0]
+            nb = cloud.knn_search(q, k)
+            off, idx = nb.export()
+            assert np.array_equal(off, np.arange(m + 1) * k)
+            sub = np.arange(0, m, 8 if m > 8 else 1)
+            off_o, idx_o = O.knn_lists(p, q[sub], k)
+            got, want = idx.reshape(m, k)[sub], np.sort(idx_o.reshape(sub.size, k), axis=1)
+            for i in np.flatnonzero(~(got == want).all(axis=1)):  # rows may differ only where the k-th and (k+1)-th are equidistant
+                d = np.sort(((p - q[sub[i]]) ** 2).sum(axis=1))
+                assert d[k - 1] == d[k], f"query {sub[i]}: different neighbour set without a distance tie"
     finally:
         cloud.free()
-    assert np.array_equal(off, np.arange(m + 1) * k)
-    sub = np.arange(0, m, 8)
-    off_o, idx_o = O.knn_lists(p, q[sub], k)
-    got, want = idx.reshape(m, k)[sub], np.sort(idx_o.reshape(sub.size, k), axis=1)
-    for i in np.flatnonzero(~(got == want).all(axis=1)):  # rows may differ only where the k-th and (k+1)-th are equidistant
-        d = np.sort(((p - q[sub[i]]) ** 2).sum(axis=1))
-        assert d[k - 1] == d[k], f"query {sub[i]}: different neighbour set without a distance tie"
     if k >= 8 and kind in ("uniform", "surface"):  # normals from these lists against the oracle's (k-NN branch of compute_normals)
         pre = np.tile(np.array([[0.3, -0.5, 0.8]]), (400, 1))
         a = compute_normals(q[:400], p, k=k, pre_computed_normals=pre)
