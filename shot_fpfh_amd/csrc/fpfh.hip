@@ -26,8 +26,9 @@
 
 namespace {
 
+#include "fpfh_mc.h"
 
-// K7.  The vector-memory pipe of a CU takes 16 cycles per wave instruction whatever the width per lane, so
+// K7 on the wider tables.  The vector-memory pipe of a CU takes 16 cycles per wave instruction whatever the width per lane, so
 // the neighbour rows are fetched 16 B per lane (dwordx4): a row of RB bytes occupies LPR = RB/16 lanes and
 // ONE load instruction brings in 64/LPR rows (4 rows of 125 uint16 bins).  Each lane accumulates the
 // 16/sizeof(CT) bins of its 16-byte piece (NP pieces when a row is longer than 1 KiB) in float64 and the
@@ -66,14 +67,7 @@ __global__ __launch_bounds__(256) void k_fpfh(const double *__restrict__ rec, co
     // weight of neighbour j: spfh[j] / d_j with spfh[j] = count_j / k_j ; d == 0 is masked out (fpfh.py:110-114)
     auto weight_of = [&](double x, double y, double z, int kj) -> double {
         const double cx = x - px, cy = y - py, cz = z - pz;
-        const double d2 = (cx * cx + cy * cy) + cz * cz;
-        // 1 / (k_j d_j) = rsqrt(d2 k_j^2): v_rsq_f64 and two Newton steps (~1 ulp; the weight is a continuous
-        // factor, no decision depends on its last bit) instead of sqrt + division (~35 instructions)
-        const double kd = (double)kj, xx = d2 * (kd * kd);
-        const double y0 = __builtin_amdgcn_rsq(xx);
-        const double y1 = __builtin_fma(0.5 * y0, __builtin_fma(-(xx * y0), y0, 1.0), y0);
-        const double y2 = __builtin_fma(0.5 * y1, __builtin_fma(-(xx * y1), y1, 1.0), y1);
-        return d2 > 0.0 ? y2 : 0.0;
+        return sf_fpfh_weight((cx * cx + cy * cy) + cz * cz, (double)kj, true); // 1 / (k_j d_j)
     };
     auto accumulate = [&](const uint4 &v, double ww, int u) {
         if (sizeof(CT) == 2) {
@@ -183,9 +177,7 @@ __global__ __launch_bounds__(256) void k_fpfh(const double *__restrict__ rec, co
     // divisions are shared out instead of being executed (predicated) by the whole wave for group 0 alone
     {
         const double kd = (double)k;
-        double inv_k = __builtin_amdgcn_rcp(kd); // 1 / k to ~1 ulp for the neighbour term (the SPFH term keeps its division)
-        inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
-        inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
+        const double inv_k = sf_fpfh_inv(kd); // for the neighbour term (the SPFH term keeps its division)
         const CT *own = counts + i * (int64_t)stride;
         double *o = out + q * (int64_t)nb3;
 #pragma unroll
@@ -204,8 +196,6 @@ __global__ __launch_bounds__(256) void k_fpfh(const double *__restrict__ rec, co
     }
 }
 
-#include "fpfh_mc.h"
-
 // The two matrix-core forms of K7 are separate kernels and the host picks one from its copy of the table-wide block mask.
 // Should that copy ever disagree with the device's, the keypoint's row is filled with NaN and word 2 of `live` raised
 // (sf_fpfh reports it at its next synchronisation) -- a wrong launch is loud, never an unwritten row.
@@ -214,6 +204,14 @@ __device__ inline void fpfh_mc_wrong_form(const unsigned *__restrict__ live, dou
     const int lane = threadIdx.x & 63;
     for (int b = lane; b < nb3; b += 64) out[q * nb3 + b] = __builtin_nan("");
     if (lane == 0) atomicOr(const_cast<unsigned *>(live) + 2, 1u);
+}
+
+// the (at most) two live blocks of a table-wide mask: a lone live block is paired with an empty one (as spfh_pack_row does)
+__device__ __forceinline__ void fpfh_mc_live_pair(unsigned mask, int &b0, int &b1)
+{
+    b0 = mask ? __ffs(mask) - 1 : 0;
+    const unsigned rest = mask & (mask - 1u);
+    b1 = rest ? __ffs(rest) - 1 : (b0 + 1) & 7;
 }
 
 // Occupancy: the full form keeps eight 4-register accumulators and wants 76 registers -- six waves per SIMD, no spill: 1.33 ms
@@ -237,8 +235,9 @@ __global__ __launch_bounds__(64 * SF_MC_WPB) __attribute__((amdgpu_waves_per_eu(
     __shared__ __attribute__((aligned(16))) unsigned rowbuf_all[SF_MC_WPB][32 * 32]; // 32 rows of 128 B
     __shared__ __attribute__((aligned(16))) unsigned char abuf_all[SF_MC_WPB][9 * 64];
     const int wv_id = threadIdx.x >> 6;
+    // (the query pick stays written out in the three kernels: behind a function the first MFMA block of 17 instantiations grew)
     int64_t q = sf_uniform64(sf_xcd_block() * SF_MC_WPB + wv_id);
-    if (sel) { // (the launch of the lists that need more chunks than the bulk: sf_dispatch::mid_sel)
+    if (sel) { // (a launch over a selection: sf_dispatch::mid_sel, tail_sel)
         if (q >= nsel) return;
         q = (int64_t)sf_uniform(sel[q]) - view_first;
         if (q < 0) return;
@@ -272,8 +271,9 @@ __global__ __launch_bounds__(64 * SF_MC_WPB) __attribute__((amdgpu_waves_per_eu(
     __shared__ __attribute__((aligned(16))) unsigned rowbuf_all[SF_MC_WPB][32 * 32]; // four steps of 32 rows x 32 B
     __shared__ __attribute__((aligned(16))) unsigned char abuf_all[SF_MC_WPB][9 * 64];
     const int wv_id = threadIdx.x >> 6;
+    // (the query pick stays written out in the three kernels: behind a function the first MFMA block of 17 instantiations grew)
     int64_t q = sf_uniform64(sf_xcd_block() * SF_MC_WPB + wv_id);
-    if (sel) {
+    if (sel) { // (a launch over a selection: sf_dispatch::mid_sel, tail_sel)
         if (q >= nsel) return;
         q = (int64_t)sf_uniform(sel[q]) - view_first;
         if (q < 0) return;
@@ -284,9 +284,8 @@ __global__ __launch_bounds__(64 * SF_MC_WPB) __attribute__((amdgpu_waves_per_eu(
         fpfh_mc_wrong_form(live, out, q, W.nb3);
         return;
     }
-    const int b0 = mask ? __ffs(mask) - 1 : 0;
-    const unsigned rest = mask & (mask - 1u);
-    const int b1 = rest ? __ffs(rest) - 1 : (b0 + 1) & 7; // (a lone live block is paired with an empty one)
+    int b0, b1;
+    fpfh_mc_live_pair(mask, b0, b1);
     // ... from the packed copy (32 bytes per row: four rows per cache line) when every row of it was written under this
     // very mask, else from the table itself
     if (sf_uniform(live[1]) == mask) {
@@ -316,8 +315,9 @@ __global__ __launch_bounds__(64 * SF_MC_WPB) void k_fpfh_mcl(const double *__res
     __shared__ __attribute__((aligned(16))) unsigned rowbuf_all[SF_MC_WPB][32 * 32];
     __shared__ __attribute__((aligned(16))) unsigned char abuf_all[SF_MC_WPB][9 * 64];
     const int wv_id = threadIdx.x >> 6;
+    // (the query pick stays written out in the three kernels: behind a function the first MFMA block of 17 instantiations grew)
     int64_t q = sf_uniform64(sf_xcd_block() * SF_MC_WPB + wv_id);
-    if (SEL) {
+    if (SEL) { // (a launch over a selection: sf_dispatch::mid_sel, tail_sel)
         if (q >= nsel) return;
         q = (int64_t)sf_uniform(sel[q]) - view_first;
         if (q < 0) return;
@@ -330,9 +330,8 @@ __global__ __launch_bounds__(64 * SF_MC_WPB) void k_fpfh_mcl(const double *__res
         return;
     }
     if (SPARSE) {
-        const int b0 = mask ? __ffs(mask) - 1 : 0;
-        const unsigned rest = mask & (mask - 1u);
-        const int b1 = rest ? __ffs(rest) - 1 : (b0 + 1) & 7; // (a lone live block is paired with an empty one)
+        int b0, b1;
+        fpfh_mc_live_pair(mask, b0, b1);
         if (sf_uniform(live[1]) == mask) {
             fpfh_mcl_body_sparse<true, SF_MCL_SC>(rec, offset, cnt, idx, nbrs_begin, kp_pos, W, counts, packed, packed_bytes, p4, out, q, b0, b1,
                                                   rowbuf_all[wv_id], abuf_all[wv_id], hi, limit);
@@ -496,6 +495,9 @@ static int launch_fpfh_mc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, co
 #define SF_MC_ARGS c->rec, nb->offset, nb->count, nb->idx, nb->self_begin, kp_pos, m, W, (const uint8_t *)sp->counts,       \
                    (unsigned)tb, (const double *)sp->p4, (const unsigned *)sp->live, (const uint8_t *)sp->packed,                \
                    (unsigned)((size_t)sp->rows_alloc * 32), dout, hi
+    // a launch in its HI instantiation (the table has rows of high bytes) or its plain one; a launch over every query
+#define SF_MC_BY_HI(LAUNCH, ...) if (hi) { LAUNCH(true, __VA_ARGS__); } else { LAUNCH(false, __VA_ARGS__); }
+#define SF_MC_NO_SEL (const int32_t *)nullptr, (int64_t)0
     if (cov) {
         // K7 with the frame moments: the sparse form, at most three chunks.  The few lists that need more chunks than the bulk
         // (sf_dispatch::mid_sel) take the THREE-chunk instantiation here -- none is longer -- where the plain launch uses four.
@@ -503,19 +505,16 @@ static int launch_fpfh_mc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, co
             sf_set_error("sf_fpfh_moments: these lists / this table do not take a K7 form that carries the frame moments");
             return SF_ERR_UNSUPPORTED;
         }
-#define SF_MCM_LAUNCH2(NAME, GRID, NKS, HI, LIMIT, SELP, NSEL)                                                        \
+#define SF_MCM_LAUNCH(HI, NAME, GRID, NKS, LIMIT, SELP, NSEL)                                                         \
         SF_LAUNCH(ctx, NAME, (k_fpfh_mc_sparse<NKS, HI, true>), GRID, block, SF_MC_ARGS, LIMIT, SELP, NSEL, d.view_first, nb->radius, cov)
-#define SF_MCM_LAUNCH(NAME, GRID, NKS, LIMIT, SELP, NSEL)                                                             \
-        if (hi) { SF_MCM_LAUNCH2(NAME, GRID, NKS, true, LIMIT, SELP, NSEL); } else { SF_MCM_LAUNCH2(NAME, GRID, NKS, false, LIMIT, SELP, NSEL); }
-        if (d.chunks <= 1) { SF_MCM_LAUNCH("k7_fpfh", grid, 1, d.limit, (const int32_t *)nullptr, (int64_t)0) }
-        else if (d.chunks == 2) { SF_MCM_LAUNCH("k7_fpfh", grid, 2, d.limit, (const int32_t *)nullptr, (int64_t)0) }
-        else { SF_MCM_LAUNCH("k7_fpfh", grid, 3, d.limit, (const int32_t *)nullptr, (int64_t)0) }
+        if (d.chunks <= 1) { SF_MC_BY_HI(SF_MCM_LAUNCH, "k7_fpfh", grid, 1, d.limit, SF_MC_NO_SEL) }
+        else if (d.chunks == 2) { SF_MC_BY_HI(SF_MCM_LAUNCH, "k7_fpfh", grid, 2, d.limit, SF_MC_NO_SEL) }
+        else { SF_MC_BY_HI(SF_MCM_LAUNCH, "k7_fpfh", grid, 3, d.limit, SF_MC_NO_SEL) }
         if (d.n_mid) {
             const dim3 grid_mid(sf_xcd_grid(sf_div_up(d.n_mid, SF_MC_WPB)));
-            SF_MCM_LAUNCH("k7_fpfh_mid", grid_mid, 3, 255, d.mid_sel, d.n_mid)
+            SF_MC_BY_HI(SF_MCM_LAUNCH, "k7_fpfh_mid", grid_mid, 3, 255, d.mid_sel, d.n_mid)
         }
 #undef SF_MCM_LAUNCH
-#undef SF_MCM_LAUNCH2
         return SF_OK;
     }
     // Which form runs is decided here, on the table-wide block mask -- read back once per K6 (8 bytes; the one host
@@ -534,27 +533,21 @@ static int launch_fpfh_mc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, co
         }
     }
     const bool sparse = __builtin_popcount(sp->host_live[0] & 0xffu) <= 2;
-#define SF_MC_LAUNCH2(NAME, GRID, NKS, HI, LIMIT, SELP, NSEL)                                                         \
+#define SF_MC_LAUNCH(HI, NAME, GRID, NKS, LIMIT, SELP, NSEL)                                                          \
     if (sparse) { SF_LAUNCH(ctx, NAME, (k_fpfh_mc_sparse<NKS, HI>), GRID, block, SF_MC_ARGS, LIMIT, SELP, NSEL, d.view_first, 0.0, (double *)nullptr); } \
     else if (padc) { SF_LAUNCH(ctx, NAME, (k_fpfh_mc<4, true, true>), GRID, block, SF_MC_ARGS, LIMIT, SELP, NSEL, d.view_first); } \
     else { SF_LAUNCH(ctx, NAME, (k_fpfh_mc<NKS, true>), GRID, block, SF_MC_ARGS, LIMIT, SELP, NSEL, d.view_first); }
-#define SF_MC_LAUNCH(NKS)                                                                                            \
-    if (hi) { SF_MC_LAUNCH2("k7_fpfh", grid, NKS, true, d.limit, (const int32_t *)nullptr, (int64_t)0) }             \
-    else { SF_MC_LAUNCH2("k7_fpfh", grid, NKS, false, d.limit, (const int32_t *)nullptr, (int64_t)0) }
-    if (d.chunks <= 1) { SF_MC_LAUNCH(1); }
-    else if (d.chunks == 2) { SF_MC_LAUNCH(2); }
-    else if (d.chunks == 3) { SF_MC_LAUNCH(3); }
-    else { SF_MC_LAUNCH(4); }
+    if (d.chunks <= 1) { SF_MC_BY_HI(SF_MC_LAUNCH, "k7_fpfh", grid, 1, d.limit, SF_MC_NO_SEL) }
+    else if (d.chunks == 2) { SF_MC_BY_HI(SF_MC_LAUNCH, "k7_fpfh", grid, 2, d.limit, SF_MC_NO_SEL) }
+    else if (d.chunks == 3) { SF_MC_BY_HI(SF_MC_LAUNCH, "k7_fpfh", grid, 3, d.limit, SF_MC_NO_SEL) }
+    else { SF_MC_BY_HI(SF_MC_LAUNCH, "k7_fpfh", grid, 4, d.limit, SF_MC_NO_SEL) }
     if (d.n_mid) { // the few lists that need more chunks than the bulk: the same form, four chunks
         const dim3 grid_mid(sf_xcd_grid(sf_div_up(d.n_mid, SF_MC_WPB)));
-        if (hi) { SF_MC_LAUNCH2("k7_fpfh_mid", grid_mid, 4, true, 255, d.mid_sel, d.n_mid) }
-        else { SF_MC_LAUNCH2("k7_fpfh_mid", grid_mid, 4, false, 255, d.mid_sel, d.n_mid) }
+        SF_MC_BY_HI(SF_MC_LAUNCH, "k7_fpfh_mid", grid_mid, 4, 255, d.mid_sel, d.n_mid)
     }
 #undef SF_MC_LAUNCH
-#undef SF_MC_LAUNCH2
     if (any_tail) {
-        // the lists above 255 points, on the matrix cores too (k_fpfh_mcl; the vector-ALU form it replaced in round 5 -- 3.4 x the
-        // cost per pair, kept for a round as a cross-check -- is gone: tests/test_hip_round5.py holds the long form to the CPU restatement)
+        // the lists above 255 points, on the matrix cores too (k_fpfh_mcl; tests/test_hip_round5.py holds it to the CPU restatement)
 #define SF_MCL_LAUNCH(SEL, GRID, SELP, NSEL, VF)                                                                       \
         if (sparse) { SF_LAUNCH(ctx, "k7_fpfh_tail", (k_fpfh_mcl<SEL, true>), dim3(sf_xcd_grid(sf_div_up(GRID, SF_MC_WPB))), block, SF_MC_ARGS, long_limit, SELP, NSEL, VF); } \
         else if (padc) { SF_LAUNCH(ctx, "k7_fpfh_tail", (k_fpfh_mcl<SEL, false, true>), dim3(sf_xcd_grid(sf_div_up(GRID, SF_MC_WPB))), block, SF_MC_ARGS, long_limit, SELP, NSEL, VF); } \
@@ -566,6 +559,8 @@ static int launch_fpfh_mc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, co
         }
 #undef SF_MCL_LAUNCH
     }
+#undef SF_MC_NO_SEL
+#undef SF_MC_BY_HI
 #undef SF_MC_ARGS
     return SF_OK;
 }

@@ -1,5 +1,5 @@
-// fpfh_mc.h -- body of K7 on the int8 matrix cores, as a device function: used by k_fpfh_mc (fpfh.hip) and by the
-// kernel that runs K5 and K7 side by side on the same CUs (descriptors.hip).
+// fpfh_mc.h -- K7 on the int8 matrix cores, as device functions: the pieces its forms share, each defined once, and the four
+// bodies the kernels of fpfh.hip call (k_fpfh_mc, k_fpfh_mc_sparse, k_fpfh_mcl).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,7 +8,7 @@
 #include "device_util.h"
 
 // --------------------------------------------------------------------------------------------------
-// K7 on the matrix cores (uint8 table: at most 128 bins, neighbourhoods of at most 255 points).
+// K7 on the matrix cores (uint8 table: at most 128 bins).
 //
 // fpfh[q][b] - spfh[q][b] = (1/k_q) sum_j w_j c_jb is, per keypoint, the product of a 1 x k row of weights with
 // the k x 128 matrix of its neighbours' integer bin counts.  Done on the vector ALU it costs three instructions
@@ -26,8 +26,23 @@
 // operand of the MFMA for bins 16 bb .. 16 bb + 15 -- lane (a, kb): bin 16 bb + a of neighbours 8 kb .. 8 kb + 7, one
 // per byte -- is exactly what ONE transposing read (ds_read_b64_tr_b8: 8 rows x 16 bytes per 16-lane group,
 // delivered column-major) returns, so no byte shuffling is left to the vector pipe.
+//
+// Four bodies, one arithmetic: fpfh_mc_body (whole rows) and fpfh_mc_body_sparse (at most two live 16-bin blocks) hold a list of
+// at most 255 points in registers, fpfh_mcl_body and fpfh_mcl_body_sparse walk a longer one twice.  A body keeps to itself its
+// SCHEDULE -- which steps are requested up front, which vmcnt it waits on, where the limbs are written, one pass or two, the
+// integer limb pairs of the short forms against the float64 ones of the long forms, own / k through the reciprocal or by
+// division -- and the pieces of text that cost registers or lengthened an MFMA block as functions (profiles/k7_family_isa.md): its
+// keypoint prologue (the own-count loads must stay in front of the first DMA statement, whose "memory" clobber pins them), its
+// lane map, the loop of a whole-row step with its padding column, and in fpfh_mc_body the row epilogue.  Everything else is one of the functions below, and the rows of the four
+// forms are equal bit for bit because of it: the additions of each recombination are ordered in ONE place.
 // --------------------------------------------------------------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v2i_t __attribute__((ext_vector_type(2)));
+typedef __amdgpu_buffer_rsrc_t fpfh_mc_rsrc_t;
+#ifndef SF_MC_WPB
+#define SF_MC_WPB 4 // waves (= keypoints in flight) per workgroup: 4.6 KB of LDS each
+#endif
+#define SF_MC_BPAD ((long)0x8080808080808080ull) // eight neighbours' padding bin as a B operand: -128 each
 
 // Which bins of the descriptor the table's 128 columns are: column c = bin win_lo + c for c < win_len; the other bins of the
 // nb3 are structurally empty (sf_spfh::win_lo) and the keypoint's row gets zeros there.  win_lo = 0, win_len = nb3 for tables
@@ -64,18 +79,94 @@ __device__ __forceinline__ void fpfh_mc_store_row(double *__restrict__ o, int n,
     else if (b_ok) sf_store_stream(o + e + 1, b);
 }
 
+// The row epilogue (of every form but fpfh_mc_body, which has it as text): zeros outside the window, then the lane's two bins o0, o1 (values r0, r1) -- staged through
+// `rowbuf` (free once the last step's reads have returned; fpfh_mc_store_row brings its own fences) or by the two plain stores.
+__device__ __forceinline__ void fpfh_mc_finish_row(double *__restrict__ out, int64_t q, const sf_bin_window &W, int o0, int o1,
+                                                   double r0, double r1, unsigned *rowbuf, int lane)
+{
+    double *o = out + q * (int64_t)W.nb3;
+    fpfh_mc_zero_outside(o, W, lane);
+    o += W.win_lo;
+    if (W.win_len == W.nb3 && W.win_len <= 126) { // (wave-uniform)
+        fpfh_mc_store_row(o, W.win_len, o0, r0, o1, r1, reinterpret_cast<double *>(rowbuf), lane);
+    } else {
+        if (o0 < W.win_len) sf_store_stream(o + o0, r0);
+        if (o1 < W.win_len) sf_store_stream(o + o1, r1);
+    }
+}
+
+// ---- scalar pieces ------------------------------------------------------------------------------------------------
+// weight of a neighbour, 1 / (k_j d_j) = rsqrt(d2 k_j^2): v_rsq_f64 and two Newton steps (~1 ulp; the weight is a continuous
+// factor, no decision depends on its last bit) instead of sqrt + division (~35 instructions).  0 past the end of the list
+// (!on) and at distance 0 (fpfh.py:110-114).
+__device__ __forceinline__ double sf_fpfh_weight(double d2, double kd, bool on)
+{
+    const double xx = d2 * (kd * kd);
+    const double y0 = __builtin_amdgcn_rsq(xx);
+    const double y1 = __builtin_fma(0.5 * y0, __builtin_fma(-(xx * y0), y0, 1.0), y0);
+    const double y2 = __builtin_fma(0.5 * y1, __builtin_fma(-(xx * y1), y1, 1.0), y1);
+    return (on && d2 > 0.0) ? y2 : 0.0;
+}
+
+// 1 / k to ~1 ulp: v_rcp_f64 and two Newton steps
+__device__ __forceinline__ double sf_fpfh_inv(double kd)
+{
+    double inv_k = __builtin_amdgcn_rcp(kd);
+    inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
+    return __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
+}
+
+// fixed point: W = floor(w 2^S) < 2^62 with S = 61 - floor(log2 of the wave's largest weight) (wmax: the lane's largest)
+__device__ __forceinline__ int fpfh_mc_exponent(double wmax)
+{
+    wmax = sf_wave_max_nonneg(wmax);
+    const int e2 = wmax > 0.0 ? (int)((__double2hiint(wmax) >> 20) & 0x7ff) - 1023 : 0;
+    return 61 - e2;
+}
+
+// what the limb sums of lane group g = kb are worth: limbs 4 g, 4 g + 1 as a pair 2^(32 g - S), limbs 4 g + 2, 4 g + 3 2^16 more
+__device__ __forceinline__ void fpfh_mc_scales(int kb, int S, double &f0, double &f2)
+{
+    f0 = ldexp(1.0, 32 * kb - S); // 2^(8 (4 g) - S)
+    f2 = f0 * 65536.0;
+}
+
+// count / k (the keypoint's own SPFH term, fpfh.py:88-90) of the short forms, through the reciprocal already at hand and one
+// residual step -- the closing step of a division: correctly rounded for these small integers at a tenth of the instructions.
+// `own`: the table's byte (count ^ 128).  (The long forms, whose counts pass 255, divide.)
+__device__ __forceinline__ double fpfh_mc_own_term(unsigned own, double kd, double inv_k)
+{
+    const double c = (double)(own ^ 128u);
+    const double s = c * inv_k;
+    return __builtin_fma(__builtin_fma(-s, kd, c), inv_k, s);
+}
+
+// ---- LDS-DMA and the transposing read -------------------------------------------------------------------------------
 // Staged rows: 128 B each, no padding -- the image is written by LDS-DMA (buffer_load_dwordx4 ... lds: a wave
 // instruction writes its 64 lanes' 16-byte chunks back to back), so the bank spread comes from the SOURCE side:
 // slot s of row r holds chunk s ^ f(r), f(r) = (r >> 1) & 7.  A transposing read of one 32-lane half (8 rows x 16
 // bytes of block g and of block g + 1, same chunk) then touches all 64 banks once.
-typedef int v2i_t __attribute__((ext_vector_type(2)));
-#ifndef SF_MC_WPB
-#define SF_MC_WPB 4 // waves (= keypoints in flight) per workgroup: 4.6 KB of LDS each
-#endif
+// THE DMA statement: every lane's 16 bytes at byte `voff` of the buffer go to LDS, the wave's 64 pieces back to back from
+// `lds_addr` on (wave-uniform; m0 is saved and restored around it).  Its "memory" clobber keeps loads and stores on their side.
+__device__ __forceinline__ void sf_lds_dma16(unsigned voff, fpfh_mc_rsrc_t rsrc, unsigned lds_addr)
+{
+    unsigned keep_;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                 "buffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep_)
+                 : "v"(voff), "s"(rsrc), "s"(lds_addr)
+                 : "memory");
+}
 
-// (sf_lane_swap, the exchange of the recombinations below: device_util.h)
+// ONE transposing read: in its 16-lane group lane 2 q + p supplies the address of bytes 8 p .. 8 p + 7 of "row" q and receives
+// column (lane & 15) of those eight 16-byte rows, one per byte -- an int8 MFMA operand as it is.
+__device__ __forceinline__ long fpfh_mc_tr_read(const unsigned char *p)
+{
+    const v2i_t t = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i_t *)p);
+    return (long)(((unsigned long long)(unsigned)t[1] << 32) | (unsigned)t[0]);
+}
 
-// ---- pieces shared by the full and the sparse-block form ---------------------------------------------------------
+// ---- the list and its weights ---------------------------------------------------------
 // the lane's entries of the keypoint's neighbour list, chunk by chunk (lane t of chunk c <-> neighbour 64 c + t; -1 past the
 // end).  The kernel is instantiated for the longest list of the launch; the chunks past THIS keypoint's list -- the last
 // one for nine keypoints in ten -- are skipped wave-uniformly: no index load, no gather, no weight.
@@ -90,9 +181,8 @@ __device__ __forceinline__ void fpfh_mc_list(const int32_t *__restrict__ idx, in
     }
 }
 
-// weights 1 / (k_j d_j) of all neighbours from their 32-byte records {x, y, z, k} (one rsqrt + two Newton steps each; d == 0
-// is masked out, fpfh.py:110-114), the fixed-point exponent S = 61 - floor(log2 of the largest), and jv clamped to valid
-// rows for the gathers that follow
+// weights of all neighbours from their 32-byte records {x, y, z, k} (sf_fpfh_weight), the fixed-point exponent
+// (fpfh_mc_exponent), and jv clamped to valid rows for the gathers that follow
 // HI: lm[c] = the lanes of chunk c whose neighbour has more than 255 neighbours of its own (its bins are lo + 256 hi: the
 // table of high bytes, fpfh_mc_hi)
 // MOM: the pass also forms the weighted covariance of the keypoint's SHOT frame (shot.py:27-35: w = r - ||c||, the keypoint
@@ -134,11 +224,8 @@ __device__ __forceinline__ int fpfh_mc_weights(const double *__restrict__ p4, do
                 a11 = __builtin_fma(cx, wx, a11); a21 = __builtin_fma(cy, wx, a21); a31 = __builtin_fma(cz, wx, a31);
                 a22 = __builtin_fma(cy, wy, a22); a32 = __builtin_fma(cz, wy, a32); a33 = __builtin_fma(cz, wz, a33);
             }
-            const double kd = gk[c], xx = d2 * (kd * kd);
-            const double y0 = __builtin_amdgcn_rsq(xx);
-            const double y1 = __builtin_fma(0.5 * y0, __builtin_fma(-(xx * y0), y0, 1.0), y0);
-            const double y2 = __builtin_fma(0.5 * y1, __builtin_fma(-(xx * y1), y1, 1.0), y1);
-            wv[c] = (jv[c] >= 0 && d2 > 0.0) ? y2 : 0.0;
+            const double kd = gk[c];
+            wv[c] = sf_fpfh_weight(d2, kd, jv[c] >= 0);
             wmax = fmax(wmax, wv[c]);
             if (HI) lm[c] = __ballot(wv[c] > 0.0 && kd > 255.0);
         } else if (HI) {
@@ -152,10 +239,7 @@ __device__ __forceinline__ int fpfh_mc_weights(const double *__restrict__ p4, do
         const double iw = sf_rcp_fast(sf_read_lane(tot, 0));
         mom_out = tot * iw; // lanes 8 e, e = 1 .. 6: c11 c21 c31 c22 c32 c33 (the caller stores them)
     }
-    wmax = sf_wave_max_nonneg(wmax);
-    // fixed point: W = floor(w 2^S) < 2^62 with S = 61 - floor(log2 wmax)
-    const int e2 = wmax > 0.0 ? (int)((__double2hiint(wmax) >> 20) & 0x7ff) - 1023 : 0;
-    return 61 - e2;
+    return fpfh_mc_exponent(wmax);
 }
 
 // The part of sum_j w_j c_jb that the byte table does not hold: 256 sum_{j long} w_j hi_jb for the two bins this lane
@@ -220,9 +304,104 @@ __device__ __forceinline__ void fpfh_mc_limbs(unsigned char *abuf, int lane, dou
 // receives column a of those eight 16-byte rows.
 __device__ __forceinline__ long fpfh_mc_a_operand(const unsigned char *abuf, int a, int kb, int st)
 {
-    const unsigned char *ap = (a & 1) ? abuf + 512 : abuf + 8 * (32 * (st & 1) + 8 * kb + (a >> 1));
-    const v2i_t t = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i_t *)ap);
-    return (long)(((unsigned long long)(unsigned)t[1] << 32) | (unsigned)t[0]);
+    return fpfh_mc_tr_read((a & 1) ? abuf + 512 : abuf + 8 * (32 * (st & 1) + 8 * kb + (a >> 1)));
+}
+
+// ---- recombination: lane (a, g) holds rows (limbs) 4g .. 4g+3 of column a of an accumulator --------------------------
+// A lane's four limb rows of one bin, SHORT lists: combined in INTEGER arithmetic first: |R| <= 128 * 128 * 255 < 2^22, so
+// (R[r+1] << 8) + R[r] and the same combination of the padding column stay below 2^30.01, and their difference --
+// (sum_j d_j c_jb of limb r + 1) 2^8 + (that of limb r), each at most 128 * 255 * 255 -- is below 2^31: it fits an
+// int32 exactly (two's-complement wrap-around of an intermediate is harmless).  Two shift-adds and a subtraction per
+// pair of limbs instead of a subtraction, a conversion and a float64 FMA per limb.
+__device__ __forceinline__ double fpfh_mc_part(const v4i &acc, const v4i &pad, double f0, double f2)
+{
+    const int e01 = ((acc[1] << 8) + acc[0]) - ((pad[1] << 8) + pad[0]);
+    const int e23 = ((acc[3] << 8) + acc[2]) - ((pad[3] << 8) + pad[2]);
+    return __builtin_fma((double)e23, f2, (double)e01 * f0);
+}
+
+// ... LONG lists: the limb pairs formed in float64 (the integer shift-adds would overflow; on a short list the two give the
+// same bits)
+__device__ __forceinline__ double fpfh_mcl_pair(int hi_limb, int lo_limb, int pad_hi, int pad_lo)
+{
+    return __builtin_fma((double)hi_limb - (double)pad_hi, 256.0, (double)lo_limb - (double)pad_lo); // exact: < 2^41
+}
+__device__ __forceinline__ double fpfh_mcl_part(const v4i &acc, const v4i &pad, double f0, double f2)
+{
+    return __builtin_fma(fpfh_mcl_pair(acc[3], acc[2], pad[3], pad[2]), f2, fpfh_mcl_pair(acc[1], acc[0], pad[1], pad[0]) * f0);
+}
+
+// Sum over the four limb groups g = kb of the FULL form, transposing as we go: after the exchange with lane ^ 32 a lane keeps
+// only the blocks bb = 4 (kb >> 1) + {0..3}, after the one with lane ^ 16 only bb = 4 (kb >> 1) + 2 (kb & 1) + {0, 1} -- the two
+// bins it writes (v0, v1).  gfx950's lane-swap instructions do the exchange AND the selection in one go, without the LDS
+// (sf_lane_swap): a + b is "my half's block plus the partner's" in both halves.  The order of the additions -- g + (g ^ 2)
+// first, then the two halves of that -- is the contract every form keeps.
+__device__ __forceinline__ void fpfh_mc_reduce_full(const double (&part)[8], double &v0, double &v1)
+{
+    double keep[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        double a_ = part[u], b_ = part[4 + u];
+        sf_lane_swap<32>(a_, b_);
+        keep[u] = a_ + b_;
+    }
+    double a0 = keep[0], b0_ = keep[2], a1 = keep[1], b1_ = keep[3];
+    sf_lane_swap<16>(a0, b0_);
+    sf_lane_swap<16>(a1, b1_);
+    v0 = a0 + b0_;
+    v1 = a1 + b1_;
+}
+
+// The same sum of the TWO-BLOCK form, in the SAME order, so that the rounding, hence every bit of the row, is the full form's:
+// after the 32-swap the lower half of the wave holds block b0's pair sums and the upper half block b1's, after the 16-swap both
+// rows of a half hold the total; every lane needs both totals for the row it helps write, the other half's through one more
+// 32-swap.  v0, v1: the sums of the lane's bins of blocks bb0, bb0 + 1 -- a dead block's are exactly 0.
+__device__ __forceinline__ void fpfh_mc_reduce_pair(double part0, double part1, int bb0, int b0, int b1, double &v0, double &v1)
+{
+    sf_lane_swap<32>(part0, part1);
+    double v = part0 + part1; // lanes 0..31: block b0, groups (g, g + 2) ; lanes 32..63: block b1
+    double w = v;
+    sf_lane_swap<16>(v, w);
+    const double tot = v + w; // all four groups; lanes 0..31: bin 16 b0 + a, lanes 32..63: bin 16 b1 + a
+    double tot0 = tot, tot1 = tot;
+    sf_lane_swap<32>(tot0, tot1); // (after the swap tot0 is block b0's total in both halves, tot1 block b1's)
+    v0 = bb0 == b0 ? tot0 : (bb0 == b1 ? tot1 : 0.0);
+    v1 = bb0 + 1 == b0 ? tot0 : (bb0 + 1 == b1 ? tot1 : 0.0);
+}
+
+// The two callers of the DMA statement, as MACROS: they expand in a body next to its jv[], rsrc, lds_rows and lane maps.  (As
+// __forceinline__ functions they cost k_fpfh_mc<3> and <4> 24 and 39 spilled registers and k_fpfh_mc_sparse<3> and <4> two to
+// four registers, as does a function around the loop of a whole-row step: profiles/k7_family_isa.md.)
+// They take from the body that expands them: jv[], lane, rsrc, lds_rows, and dma_chunk (ROWS) or d_row, dma_chunk16, ROW_BYTES
+// (PAIR).  ST must be a constant after unrolling: jv[] stays in registers.  CLAMP: the list entries may still be -1 (short forms).
+// Whole rows: the 32 rows of step ST (neighbours 32 ST .. + 31 = lanes 32 (ST & 1) .. of chunk ST >> 1), 4 instructions of
+// 64 x 16 bytes, 4 KB.
+#define SF_MC_DMA_ROWS(ST, CLAMP)                                                                                    \
+    {                                                                                                               \
+        _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                             \
+            const int jr0 = __shfl(jv[(ST) >> 1], 32 * ((ST) & 1) + 8 * u + (lane >> 3));                           \
+            const int jr = (CLAMP) && jr0 < 0 ? 0 : jr0; /* idle slots of the last step fetch row 0 */              \
+            sf_lds_dma16((unsigned)jr * 128u + 16u * (unsigned)(dma_chunk ^ ((u & 1) << 2)), rsrc, lds_rows + 1024u * u); \
+        }                                                                                                           \
+    }
+// Two live chunks: ONE instruction for the 32 rows of step ST, into quarter ST & 3 of the row buffer (NCH: chunks jv[] holds).
+#define SF_MC_DMA_PAIR(ST, NCH, CLAMP)                                                                               \
+    {                                                                                                               \
+        const int jr0 = __shfl(jv[((ST) >> 1) < (NCH) ? ((ST) >> 1) : 0], 32 * ((ST) & 1) + d_row);                 \
+        const int jr = (CLAMP) && jr0 < 0 ? 0 : jr0;                                                                \
+        sf_lds_dma16((unsigned)jr * ROW_BYTES + dma_chunk16, rsrc, lds_rows + 1024u * (unsigned)((ST) & 3));        \
+    }
+
+// acc += A x B on the matrix core: B a transposing read (fpfh_mc_tr_read) or the constant padding operand
+__device__ __forceinline__ v4i fpfh_mc_mfma(long A, long B, v4i acc) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(A, B, acc, 0, 0, 0); }
+
+// The two live chunks of the step's quarter at `rb`: two reads, three MFMAs (blocks b0, b1, and the padding column).
+__device__ __forceinline__ void fpfh_mc_step_pair(long A, const unsigned char *rb, int rd0, int rd1, v4i &acc0, v4i &acc1, v4i &accp)
+{
+    const long B0 = fpfh_mc_tr_read(rb + rd0), B1 = fpfh_mc_tr_read(rb + rd1);
+    accp = fpfh_mc_mfma(A, SF_MC_BPAD, accp);
+    acc0 = fpfh_mc_mfma(A, B0, acc0);
+    acc1 = fpfh_mc_mfma(A, B1, acc1);
 }
 
 // PADC: the padding column that removes the -128 bias comes from an MFMA against a constant operand (as in the sparse form)
@@ -248,39 +427,23 @@ __device__ __forceinline__ void fpfh_mc_body(const double *__restrict__ rec, con
     // (the keypoint's own counts of the two bins this lane writes, requested with the list: see the sparse form)
     const unsigned own0 = counts[i * 128 + 16 * (4 * (kb >> 1) + 2 * (kb & 1)) + a], own1 = counts[i * 128 + 16 * (4 * (kb >> 1) + 2 * (kb & 1)) + a + 16];
     if (lane == 0) *reinterpret_cast<unsigned long long *>(abuf + 512) = 0ull; // the "limbs 8 .. 15" every A operand reads
-    // A step covers 32 neighbours (v_mfma_i32_16x16x32_i8: 8 k per 16-lane group).  Transposing reads: in its group
-    // (k block kb) lane 2 q + p supplies the address of row 8 kb + q, bytes 8 p .. + 7 of chunk bb (slot bb ^ f(row),
-    // f(row) = (row >> 1) & 7), and receives bin 16 bb + a of those eight rows -- exactly its B operand.
+    // Lane map of the full form (own text in both full bodies: as a function it lengthened their MFMA blocks).  Reads: in its
+    // group (k block kb) lane 2 q + p supplies the address of row 8 kb + q, bytes 8 p .. + 7 of chunk bb (slot bb ^ f(row),
+    // f(row) = (row >> 1) & 7), and receives bin 16 bb + a of those eight rows -- exactly its B operand.  DMA: lane l of
+    // instruction u fills slot l & 7 of row 8 u + (l >> 3) with chunk (l & 7) ^ f(row): dma_chunk, ^ 4 for u = 1, 3.
     const int frow = ((a >> 2) & 3) | ((kb & 1) << 2);
     const int rd_base = (8 * kb + (a >> 1)) * 128 + 8 * (a & 1); // bytes
     int xoff[8];
 #pragma unroll
     for (int bb = 0; bb < 8; ++bb) xoff[bb] = rd_base + 16 * (bb ^ frow);
-    // DMA: lane l of instruction u fills slot l & 7 of row 8 u + (l >> 3) with chunk (l & 7) ^ f(row)
-    const int dma_chunk = (lane & 7) ^ ((lane >> 4) & 3); // ^ 4 for the rows 8 .. 15 and 24 .. 31 (u = 1, 3)
+    const int dma_chunk = (lane & 7) ^ ((lane >> 4) & 3);
     const unsigned lds_rows = (unsigned)__builtin_amdgcn_readfirstlane(
         (int)(unsigned)(size_t)(__attribute__((address_space(3))) unsigned *)rowbuf);
-    // ---- stage the 32 rows of step ST (neighbours 32 ST .. + 31 = lanes 32 (ST & 1) .. of chunk ST >> 1) in LDS:
-    //      4 DMA instructions of 64 x 16 bytes ----
-#define SF_MC_DMA(ST)                                                                                               \
-    {                                                                                                               \
-        _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                             \
-            const int jr0 = __shfl(jv[(ST) >> 1], 32 * ((ST) & 1) + 8 * u + (lane >> 3));                           \
-            const int jr = jr0 < 0 ? 0 : jr0; /* idle slots of the last step fetch row 0 */                         \
-            const unsigned voff = (unsigned)jr * 128u + 16u * (unsigned)(dma_chunk ^ ((u & 1) << 2));              \
-            unsigned keep_;                                                                                         \
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"                                     \
-                         "buffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"                              \
-                         : "=&s"(keep_)                                                                             \
-                         : "v"(voff), "s"(rsrc), "s"(lds_rows + 1024u * u)                                          \
-                         : "memory");                                                                               \
-        }                                                                                                           \
-    }
     int jv[NKS];
     double wv[NKS];
     unsigned long long lm[NKS];
     fpfh_mc_list<NKS>(idx, s, k, lane, jv);
-    SF_MC_DMA(0) // in flight while the weights are computed
+    SF_MC_DMA_ROWS(0, true) // in flight while the weights are computed
     double mom_unused = 0.0;
     const int S = fpfh_mc_weights<NKS, HI>(p4, px, py, pz, k, jv, wv, lm, 0.0, mom_unused);
 
@@ -292,76 +455,41 @@ __device__ __forceinline__ void fpfh_mc_body(const double *__restrict__ rec, con
 #pragma unroll
     for (int st = 0; st < 2 * NKS; ++st) {
         if (st * 32 < k) { // wave-uniform
-            if (st > 0) SF_MC_DMA(st) // (step 0 was issued before the weights were computed)
+            if (st > 0) SF_MC_DMA_ROWS(st, true) // (step 0 was issued before the weights were computed)
             if ((st & 1) == 0) fpfh_mc_limbs(abuf, lane, wv[st >> 1], S); // the two steps of a chunk use the lower / upper 32 columns
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the DMA pieces have landed
             __builtin_amdgcn_wave_barrier(); // both buffers are private to the wave; LDS operations of a wave stay in order
             const long A = fpfh_mc_a_operand(abuf, a, kb, st); // row a = limb a (rows 8 .. 15: zero)
             const unsigned char *rb = reinterpret_cast<const unsigned char *>(rowbuf);
 #pragma unroll
-            for (int bb = 0; bb < 8; ++bb) {
-                const v2i_t t = __builtin_amdgcn_ds_read_tr8_b64_v2i32(
-                    (__attribute__((address_space(3))) v2i_t *)(rb + xoff[bb]));
-                const long B = (long)(((unsigned long long)(unsigned)t[1] << 32) | (unsigned)t[0]);
-                acc[bb] = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, B, acc[bb], 0, 0, 0);
-            }
-            if (PADC) accp = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, (long)0x8080808080808080ull, accp, 0, 0, 0);
+            for (int bb = 0; bb < 8; ++bb) acc[bb] = fpfh_mc_mfma(A, fpfh_mc_tr_read(rb + xoff[bb]), acc[bb]);
+            if (PADC) accp = fpfh_mc_mfma(A, SF_MC_BPAD, accp);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // reads done before the next step's DMA overwrites the rows
             __builtin_amdgcn_wave_barrier();
         }
     }
     // ---- recombination: lane (a, g) holds rows (limbs) 4g .. 4g+3 of column a of acc[bb]; bin = 16 bb + a ----
-    int rpad[4];
+    int rp[4]; // the padding column: the constant operand's, or column 15 of bb = 7 (bin 127) of the table
 #pragma unroll
-    for (int r = 0; r < 4; ++r) rpad[r] = PADC ? accp[r] : __builtin_amdgcn_update_dpp(0, acc[7][r], 0x150 + 15, 0xf, 0xf, false); // column 15 of bb = 7: bin 127
-    // A lane's four limb rows are combined in INTEGER arithmetic first: |R| <= 128 * 128 * 255 < 2^22, so
-    // (R[r+1] << 8) + R[r] and the same combination of the padding column stay below 2^30.01, and their difference --
-    // (sum_j d_j c_jb of limb r + 1) 2^8 + (that of limb r), each at most 128 * 255 * 255 -- is below 2^31: it fits an
-    // int32 exactly (two's-complement wrap-around of an intermediate is harmless).  Two shift-adds and a subtraction per
-    // pair of limbs instead of a subtraction, a conversion and a float64 FMA per limb.
-    const int pad01 = (rpad[1] << 8) + rpad[0], pad23 = (rpad[3] << 8) + rpad[2];
-    const double p0 = ldexp(1.0, 32 * kb - S); // 2^(8 (4 g) - S)
-    const double f0 = p0, f2 = p0 * 65536.0;
-    const double kd = (double)k;
-    double inv_k = __builtin_amdgcn_rcp(kd);
-    inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
-    inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
+    for (int r = 0; r < 4; ++r) rp[r] = PADC ? accp[r] : __builtin_amdgcn_update_dpp(0, acc[7][r], 0x150 + 15, 0xf, 0xf, false);
+    const v4i rpad = v4i{rp[0], rp[1], rp[2], rp[3]};
+    double f0, f2;
+    fpfh_mc_scales(kb, S, f0, f2);
+    const double kd = (double)k, inv_k = sf_fpfh_inv(kd);
     // partial sums over this lane's four limbs, for its eight bins
     double part[8];
 #pragma unroll
-    for (int bb = 0; bb < 8; ++bb) {
-        const int e01 = ((acc[bb][1] << 8) + acc[bb][0]) - pad01;
-        const int e23 = ((acc[bb][3] << 8) + acc[bb][2]) - pad23;
-        part[bb] = __builtin_fma((double)e23, f2, (double)e01 * f0);
-    }
-    // sum over the four limb groups g = kb, transposing as we go: after the exchange with lane ^ 32 a lane keeps only
-    // the blocks bb = 4 (kb >> 1) + {0..3}, after the one with lane ^ 16 only bb = 4 (kb >> 1) + 2 (kb & 1) + {0, 1}
-    // -- the two bins it writes
-    // gfx950's lane-swap instructions do the exchange AND the selection in one go, without the LDS (sf_lane_swap): a + b is
-    // "my half's block plus the partner's" in both halves
-    double keep[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        double a_ = part[u], b_ = part[4 + u];
-        sf_lane_swap<32>(a_, b_);
-        keep[u] = a_ + b_;
-    }
-    double a0 = keep[0], b0_ = keep[2], a1 = keep[1], b1_ = keep[3];
-    sf_lane_swap<16>(a0, b0_);
-    sf_lane_swap<16>(a1, b1_);
-    const double vsel0 = a0 + b0_, vsel1 = a1 + b1_;
+    for (int bb = 0; bb < 8; ++bb) part[bb] = fpfh_mc_part(acc[bb], rpad, f0, f2);
+    double vsel0, vsel1;
+    fpfh_mc_reduce_full(part, vsel0, vsel1);
     {
         const int bb0 = 4 * (kb >> 1) + 2 * (kb & 1);
         const int b0 = 16 * bb0 + a, b1 = b0 + 16;
+        // (own text of fpfh_mc_finish_row, the zeros first: through the function k_fpfh_mc<1, 2, 4>'s MFMA blocks grew)
         double *o = out + q * (int64_t)W.nb3;
         fpfh_mc_zero_outside(o, W, lane);
         o += W.win_lo;
-        // count / k (the keypoint's own SPFH term, fpfh.py:88-90) through the reciprocal already at hand and one residual
-        // step -- the closing step of a division: correctly rounded for these small integers at a tenth of the instructions
-        const double c0 = (double)(own0 ^ 128u), c1 = (double)(own1 ^ 128u);
-        double s0 = c0 * inv_k, s1 = c1 * inv_k;
-        s0 = __builtin_fma(__builtin_fma(-s0, kd, c0), inv_k, s0);
-        s1 = __builtin_fma(__builtin_fma(-s1, kd, c1), inv_k, s1);
+        const double s0 = fpfh_mc_own_term(own0, kd, inv_k), s1 = fpfh_mc_own_term(own1, kd, inv_k);
         double h0 = 0.0, h1 = 0.0;
         if (HI) fpfh_mc_hi<NKS>(hi, jv, wv, lm, b0, b1, h0, h1);
         const double r0 = s0 + (HI ? vsel0 + h0 : vsel0) * inv_k, r1 = s1 + (HI ? vsel1 + h1 : vsel1) * inv_k;
@@ -373,8 +501,6 @@ __device__ __forceinline__ void fpfh_mc_body(const double *__restrict__ rec, con
         }
     }
 }
-
-#undef SF_MC_DMA
 
 // --------------------------------------------------------------------------------------------------
 // The same contraction when at most TWO of the table's eight 16-bin blocks hold any count (blocks b0, b1; K6 keeps the OR
@@ -423,18 +549,6 @@ __device__ __forceinline__ void fpfh_mc_body_sparse(const double *__restrict__ r
     const int rd0 = 16 * rd_piece + 8 * (a & 1), rd1 = rd0 + 256;
     const unsigned lds_rows = (unsigned)__builtin_amdgcn_readfirstlane(
         (int)(unsigned)(size_t)(__attribute__((address_space(3))) unsigned *)rowbuf);
-#define SF_MCS_DMA(ST)                                                                                              \
-    {                                                                                                               \
-        const int jr0 = __shfl(jv[((ST) >> 1) < NKS ? ((ST) >> 1) : 0], 32 * ((ST) & 1) + d_row);                   \
-        const int jr = jr0 < 0 ? 0 : jr0; /* idle slots of the last step fetch row 0 */                             \
-        const unsigned voff = (unsigned)jr * ROW_BYTES + dma_chunk16;                                               \
-        unsigned keep_;                                                                                             \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"                                         \
-                     "buffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"                                  \
-                     : "=&s"(keep_)                                                                                 \
-                     : "v"(voff), "s"(rsrc), "s"(lds_rows + 1024u * (unsigned)((ST) & 3))                           \
-                     : "memory");                                                                                   \
-    }
     int jv[NKS];
     double wv[NKS];
     unsigned long long lm[NKS];
@@ -442,96 +556,55 @@ __device__ __forceinline__ void fpfh_mc_body_sparse(const double *__restrict__ r
     // The image of a step is 1 KB, so the 4 KB row buffer holds FOUR steps: the rows of the first two chunks (128
     // neighbours -- the whole list for nine keypoints in ten) are all requested here, in flight while the weights are
     // computed, and the step loop below never waits on memory again; only a third / fourth chunk re-uses the buffer.
-    SF_MCS_DMA(0)
-    if (32 < k) SF_MCS_DMA(1)
-    if (NKS >= 2 && 64 < k) SF_MCS_DMA(2)
-    if (NKS >= 2 && 96 < k) SF_MCS_DMA(3)
+    SF_MC_DMA_PAIR(0, NKS, true)
+    if (32 < k) SF_MC_DMA_PAIR(1, NKS, true)
+    if (NKS >= 2 && 64 < k) SF_MC_DMA_PAIR(2, NKS, true)
+    if (NKS >= 2 && 96 < k) SF_MC_DMA_PAIR(3, NKS, true)
     double mom = 0.0;
     const int S = fpfh_mc_weights<NKS, HI, MOM>(p4, px, py, pz, k, jv, wv, lm, mom_radius, mom);
 
     v4i acc0 = v4i{0, 0, 0, 0}, acc1 = v4i{0, 0, 0, 0}, accp = v4i{0, 0, 0, 0}; // blocks b0, b1, and the padding column
-    const long Bpad = (long)0x8080808080808080ull; // eight neighbours' padding bin: -128 each
 
 #pragma unroll
     for (int st = 0; st < 2 * NKS; ++st) {
         if (st * 32 < k) { // wave-uniform
-            if (st >= 4) SF_MCS_DMA(st) // (steps 0 .. 3 were requested up front; by now their regions have been consumed)
+            if (st >= 4) SF_MC_DMA_PAIR(st, NKS, true) // (steps 0 .. 3 were requested up front; by now their regions have been consumed)
             if ((st & 1) == 0) fpfh_mc_limbs(abuf, lane, wv[st >> 1], S);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the DMA pieces have landed
             __builtin_amdgcn_wave_barrier();
             const long A = fpfh_mc_a_operand(abuf, a, kb, st); // row a = limb a (rows 8 .. 15: zero)
             const unsigned char *rb = reinterpret_cast<const unsigned char *>(rowbuf);
-            const v2i_t t0 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i_t *)(rb + rd0 + 1024 * (st & 3)));
-            const v2i_t t1 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i_t *)(rb + rd1 + 1024 * (st & 3)));
-            accp = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, Bpad, accp, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, (long)(((unsigned long long)(unsigned)t0[1] << 32) | (unsigned)t0[0]), acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, (long)(((unsigned long long)(unsigned)t1[1] << 32) | (unsigned)t1[0]), acc1, 0, 0, 0);
+            fpfh_mc_step_pair(A, rb, rd0 + 1024 * (st & 3), rd1 + 1024 * (st & 3), acc0, acc1, accp);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // reads done before the next step's DMA overwrites the pieces
             __builtin_amdgcn_wave_barrier();
         }
     }
     // ---- recombination: lane (a, g) holds limbs 4g .. 4g + 3 of bin 16 b_u + a in acc_u, and of the padding column in accp
     //      (every column of accp is the same sum) ----
-    const int pad01 = (accp[1] << 8) + accp[0], pad23 = (accp[3] << 8) + accp[2];
-    const double p0 = ldexp(1.0, 32 * kb - S); // 2^(8 (4 g) - S)
-    const double f0 = p0, f2 = p0 * 65536.0;
-    const double kd = (double)k;
-    double inv_k = __builtin_amdgcn_rcp(kd);
-    inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
-    inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
-    double part0, part1;
-    {
-        const int e01 = ((acc0[1] << 8) + acc0[0]) - pad01, e23 = ((acc0[3] << 8) + acc0[2]) - pad23;
-        part0 = __builtin_fma((double)e23, f2, (double)e01 * f0);
-        const int g01 = ((acc1[1] << 8) + acc1[0]) - pad01, g23 = ((acc1[3] << 8) + acc1[2]) - pad23;
-        part1 = __builtin_fma((double)g23, f2, (double)g01 * f0);
-    }
-    // Sum over the four limb groups in the SAME order as the full kernel -- (g + (g ^ 2)) first, then the two halves of that
-    // -- so that the rounding, hence every bit of the row, is the full kernel's: after the 32-swap the lower half of the
-    // wave holds block b0's pair sums and the upper half block b1's, after the 16-swap both rows of a half hold the total.
-    sf_lane_swap<32>(part0, part1);
-    double v = part0 + part1;     // lanes 0..31: block b0, groups (g, g + 2) ; lanes 32..63: block b1
-    double w = v;
-    sf_lane_swap<16>(v, w);
-    const double tot = v + w;     // all four groups; lanes 0..31: bin 16 b0 + a, lanes 32..63: bin 16 b1 + a
-    // every lane needs both totals for the row it helps write: the other half's through one more 32-swap
-    double mine = tot, other = tot;
-    sf_lane_swap<32>(mine, other); // lower half: mine = own (b0), other = b1's ; upper half: mine = b0's, other = own (b1)
-    const double tot0 = mine, tot1 = other; // (after the swap `mine` is block b0's total in both halves, `other` b1's)
+    double f0, f2;
+    fpfh_mc_scales(kb, S, f0, f2);
+    const double kd = (double)k, inv_k = sf_fpfh_inv(kd);
+    const double part0 = fpfh_mc_part(acc0, accp, f0, f2), part1 = fpfh_mc_part(acc1, accp, f0, f2);
+    double v0, v1;
+    fpfh_mc_reduce_pair(part0, part1, bb0, b0, b1, v0, v1);
     if (MOM && (lane & 7) == 0 && lane >= 8 && lane < 56) cov[6 * q + (lane >> 3) - 1] = mom;
     {
-        double *o = out + q * (int64_t)W.nb3;
-        fpfh_mc_zero_outside(o, W, lane);
-        o += W.win_lo;
-        const double c0 = (double)(own0 ^ 128u), c1 = (double)(own1 ^ 128u);
-        double s0 = c0 * inv_k, s1 = c1 * inv_k;
-        s0 = __builtin_fma(__builtin_fma(-s0, kd, c0), inv_k, s0);
-        s1 = __builtin_fma(__builtin_fma(-s1, kd, c1), inv_k, s1);
-        const double v0 = bb0 == b0 ? tot0 : (bb0 == b1 ? tot1 : 0.0);
-        const double v1 = bb0 + 1 == b0 ? tot0 : (bb0 + 1 == b1 ? tot1 : 0.0);
+        const double s0 = fpfh_mc_own_term(own0, kd, inv_k), s1 = fpfh_mc_own_term(own1, kd, inv_k);
         double h0 = 0.0, h1 = 0.0;
         if (HI) fpfh_mc_hi<NKS>(hi, jv, wv, lm, o0, o1, h0, h1);
         const double r0 = s0 + (HI ? v0 + h0 : v0) * inv_k, r1 = s1 + (HI ? v1 + h1 : v1) * inv_k;
-        if (W.win_len == W.nb3 && W.win_len <= 126) { // (wave-uniform)
-            fpfh_mc_store_row(o, W.win_len, o0, r0, o1, r1, reinterpret_cast<double *>(rowbuf), lane);
-        } else {
-            if (o0 < W.win_len) sf_store_stream(o + o0, r0);
-            if (o1 < W.win_len) sf_store_stream(o + o1, r1);
-        }
+        fpfh_mc_finish_row(out, q, W, o0, o1, r0, r1, rowbuf, lane);
     }
 }
 
-#undef SF_MCS_DMA
-
 // --------------------------------------------------------------------------------------------------
-// The matrix-core contraction for lists of MORE than 255 points (round 5; until then the vector ALU served them at 3.4 x the
-// cost per pair: k_fpfh_tail).  Nothing in the arithmetic above is tied to 255 neighbours but the registers that hold a list
+// The matrix-core contraction for lists of MORE than 255 points.  Nothing in the arithmetic above is tied to 255 neighbours but
+// the registers that hold a list
 // and the int32 recombination: |limb x (count - 128)| <= 2^14 per neighbour, so the int32 accumulators hold EXACT sums for any
 // list a byte table can have (k <= 65 535 -> < 2^30).  So: a first pass over the list finds the largest weight (the fixed-point
 // exponent), the second walks it in super-chunks of SC x 64 neighbours -- index loads, record gathers and weights of a
 // super-chunk at once, then its 2 SC steps of 32 neighbours through the same LDS-DMA / transposing reads / MFMAs -- and the
-// limb sums are recombined once, in float64 (the integer shift-adds of the short form would overflow; on a short list the
-// two give the same bits).  A list of at most SC x 64 points keeps entries and weights in registers between the passes.
+// limb sums are recombined once, in float64 (fpfh_mcl_part).  A list of at most SC x 64 points keeps entries and weights in registers between the passes.
 // High bytes of neighbours that have more than 255 neighbours of their own: fpfh_mc_hi per super-chunk, list order.
 // The sparse and the full form mirror each other operation by operation, as the short forms do: same bits.
 // --------------------------------------------------------------------------------------------------
@@ -559,21 +632,12 @@ __device__ __forceinline__ void fpfh_mcl_load(const int32_t *__restrict__ idx, c
     for (int c = 0; c < SC; ++c) {
         const double cx = u0[c].x - px, cy = u0[c].y - py, cz = u1[c].x - pz;
         const double d2 = (cx * cx + cy * cy) + cz * cz;
-        const double kd = u1[c].y, xx = d2 * (kd * kd);
-        const double y0 = __builtin_amdgcn_rsq(xx);
-        const double y1 = __builtin_fma(0.5 * y0, __builtin_fma(-(xx * y0), y0, 1.0), y0);
-        const double y2 = __builtin_fma(0.5 * y1, __builtin_fma(-(xx * y1), y1, 1.0), y1);
+        const double kd = u1[c].y;
         const bool on = jv[c] >= 0;
-        wv[c] = (on && d2 > 0.0) ? y2 : 0.0; // (weight 0 past the end and at distance 0, fpfh.py:110-114: all limbs 0)
+        wv[c] = sf_fpfh_weight(d2, kd, on); // (weight 0 past the end and at distance 0: all limbs 0)
         lm[c] = __ballot(wv[c] > 0.0 && kd > 255.0);
         jv[c] = on ? jv[c] : 0; // (past the end of the list row 0 is fetched, under weight 0)
     }
-}
-
-// limb sums -> float64, for one pair of accumulator registers against the padding column's
-__device__ __forceinline__ double fpfh_mcl_pair(int hi_limb, int lo_limb, int pad_hi, int pad_lo)
-{
-    return __builtin_fma((double)hi_limb - (double)pad_hi, 256.0, (double)lo_limb - (double)pad_lo); // exact: < 2^41
 }
 
 template <bool PACKED, int SC>
@@ -608,17 +672,6 @@ __device__ __forceinline__ void fpfh_mcl_body_sparse(const double *__restrict__ 
     const int rd0 = 16 * rd_piece + 8 * (a & 1), rd1 = rd0 + 256;
     const unsigned lds_rows = (unsigned)__builtin_amdgcn_readfirstlane(
         (int)(unsigned)(size_t)(__attribute__((address_space(3))) unsigned *)rowbuf);
-#define SF_MCL_DMA(ST)                                                                                              \
-    {                                                                                                               \
-        const int jr = __shfl(jv[((ST) >> 1) < SC ? ((ST) >> 1) : 0], 32 * ((ST) & 1) + d_row);                     \
-        const unsigned voff = (unsigned)jr * ROW_BYTES + dma_chunk16;                                               \
-        unsigned keep_;                                                                                             \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"                                         \
-                     "buffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"                                  \
-                     : "=&s"(keep_)                                                                                 \
-                     : "v"(voff), "s"(rsrc), "s"(lds_rows + 1024u * (unsigned)((ST) & 3))                           \
-                     : "memory");                                                                                   \
-    }
     int jv[SC];
     double wv[SC];
     unsigned long long lm[SC];
@@ -629,12 +682,9 @@ __device__ __forceinline__ void fpfh_mcl_body_sparse(const double *__restrict__ 
 #pragma unroll
         for (int c = 0; c < SC; ++c) wmax = fmax(wmax, wv[c]);
     }
-    wmax = sf_wave_max_nonneg(wmax);
-    const int e2 = wmax > 0.0 ? (int)((__double2hiint(wmax) >> 20) & 0x7ff) - 1023 : 0;
-    const int S = 61 - e2; // W = floor(w 2^S) < 2^62
+    const int S = fpfh_mc_exponent(wmax);
 
     v4i acc0 = v4i{0, 0, 0, 0}, acc1 = v4i{0, 0, 0, 0}, accp = v4i{0, 0, 0, 0}; // blocks b0, b1, and the padding column
-    const long Bpad = (long)0x8080808080808080ull;
     double h0 = 0.0, h1 = 0.0;
     for (int base = 0; base < k; base += 64 * SC) {
         if (k > 64 * SC) fpfh_mcl_load<SC>(idx, p4, s, k, base, lane, px, py, pz, jv, wv, lm); // (else: still held from pass 0)
@@ -644,7 +694,7 @@ __device__ __forceinline__ void fpfh_mcl_body_sparse(const double *__restrict__ 
         // have returned -- the loop waits for the OLDEST request only (vector-memory requests complete in order).
 #pragma unroll
         for (int st = 0; st < 4; ++st)
-            if (st < nst) SF_MCL_DMA(st)
+            if (st < nst) SF_MC_DMA_PAIR(st, SC, false)
 #pragma unroll
         for (int st = 0; st < 2 * SC; ++st) {
             if (st < nst) { // wave-uniform
@@ -656,50 +706,24 @@ __device__ __forceinline__ void fpfh_mcl_body_sparse(const double *__restrict__ 
                 __builtin_amdgcn_wave_barrier();
                 const long A = fpfh_mc_a_operand(abuf, a, kb, st);
                 const unsigned char *rb = reinterpret_cast<const unsigned char *>(rowbuf);
-                const v2i_t t0 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i_t *)(rb + rd0 + 1024 * (st & 3)));
-                const v2i_t t1 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i_t *)(rb + rd1 + 1024 * (st & 3)));
-                accp = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, Bpad, accp, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, (long)(((unsigned long long)(unsigned)t0[1] << 32) | (unsigned)t0[0]), acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, (long)(((unsigned long long)(unsigned)t1[1] << 32) | (unsigned)t1[0]), acc1, 0, 0, 0);
+                fpfh_mc_step_pair(A, rb, rd0 + 1024 * (st & 3), rd1 + 1024 * (st & 3), acc0, acc1, accp);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // reads done before the slot is refilled
                 __builtin_amdgcn_wave_barrier();
-                if (st + 4 < nst) SF_MCL_DMA(st + 4)
+                if (st + 4 < nst) SF_MC_DMA_PAIR(st + 4, SC, false)
             }
         }
         fpfh_mc_hi<SC>(hi, jv, wv, lm, o0, o1, h0, h1);
     }
     // ---- recombination: fpfh_mc_body_sparse's, the limb pairs formed in float64 ----
-    const double p0 = ldexp(1.0, 32 * kb - S);
-    const double f0 = p0, f2 = p0 * 65536.0;
-    const double kd = (double)k;
-    double inv_k = __builtin_amdgcn_rcp(kd);
-    inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
-    inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
-    double part0 = __builtin_fma(fpfh_mcl_pair(acc0[3], acc0[2], accp[3], accp[2]), f2, fpfh_mcl_pair(acc0[1], acc0[0], accp[1], accp[0]) * f0);
-    double part1 = __builtin_fma(fpfh_mcl_pair(acc1[3], acc1[2], accp[3], accp[2]), f2, fpfh_mcl_pair(acc1[1], acc1[0], accp[1], accp[0]) * f0);
-    sf_lane_swap<32>(part0, part1);
-    double v = part0 + part1;
-    double w = v;
-    sf_lane_swap<16>(v, w);
-    const double tot = v + w;
-    double mine = tot, other = tot;
-    sf_lane_swap<32>(mine, other);
-    const double tot0 = mine, tot1 = other;
+    double f0, f2;
+    fpfh_mc_scales(kb, S, f0, f2);
+    const double kd = (double)k, inv_k = sf_fpfh_inv(kd);
+    double v0, v1;
+    fpfh_mc_reduce_pair(fpfh_mcl_part(acc0, accp, f0, f2), fpfh_mcl_part(acc1, accp, f0, f2), bb0, b0, b1, v0, v1);
     {
-        double *o = out + q * (int64_t)W.nb3;
-        fpfh_mc_zero_outside(o, W, lane);
-        o += W.win_lo;
-        const double v0 = bb0 == b0 ? tot0 : (bb0 == b1 ? tot1 : 0.0);
-        const double v1 = bb0 + 1 == b0 ? tot0 : (bb0 + 1 == b1 ? tot1 : 0.0);
         const double r0 = (double)own0 / kd + (v0 + h0) * inv_k, r1 = (double)own1 / kd + (v1 + h1) * inv_k; // spfh[kp] + sum / len(neighbourhood)  (fpfh.py:109-115)
-        if (W.win_len == W.nb3 && W.win_len <= 126) { // (wave-uniform)
-            fpfh_mc_store_row(o, W.win_len, o0, r0, o1, r1, reinterpret_cast<double *>(rowbuf), lane);
-        } else {
-            if (o0 < W.win_len) sf_store_stream(o + o0, r0);
-            if (o1 < W.win_len) sf_store_stream(o + o1, r1);
-        }
+        fpfh_mc_finish_row(out, q, W, o0, o1, r0, r1, rowbuf, lane);
     }
-#undef SF_MCL_DMA
 }
 
 // ... and on a table with more than two live blocks: whole 128-byte rows, one step (4 KB) in LDS at a time, eight MFMAs per step
@@ -726,27 +750,15 @@ __device__ __forceinline__ void fpfh_mcl_body(const double *__restrict__ rec, co
     unsigned own0 = (unsigned)counts[i * 128 + o0] ^ 128u, own1 = (unsigned)counts[i * 128 + o1] ^ 128u;
     if (k > 255) { own0 += 256u * (unsigned)hi[i * 128 + o0]; own1 += 256u * (unsigned)hi[i * 128 + o1]; }
     if (lane == 0) *reinterpret_cast<unsigned long long *>(abuf + 512) = 0ull;
+    // (lane map of the full form: fpfh_mc_body)
     const int frow = ((a >> 2) & 3) | ((kb & 1) << 2);
-    const int rd_base = (8 * kb + (a >> 1)) * 128 + 8 * (a & 1);
+    const int rd_base = (8 * kb + (a >> 1)) * 128 + 8 * (a & 1); // bytes
     int xoff[8];
 #pragma unroll
     for (int bb = 0; bb < 8; ++bb) xoff[bb] = rd_base + 16 * (bb ^ frow);
     const int dma_chunk = (lane & 7) ^ ((lane >> 4) & 3);
     const unsigned lds_rows = (unsigned)__builtin_amdgcn_readfirstlane(
         (int)(unsigned)(size_t)(__attribute__((address_space(3))) unsigned *)rowbuf);
-#define SF_MCLF_DMA(ST)                                                                                             \
-    {                                                                                                               \
-        _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                             \
-            const int jr = __shfl(jv[(ST) >> 1], 32 * ((ST) & 1) + 8 * u + (lane >> 3));                            \
-            const unsigned voff = (unsigned)jr * 128u + 16u * (unsigned)(dma_chunk ^ ((u & 1) << 2));              \
-            unsigned keep_;                                                                                         \
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"                                     \
-                         "buffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"                              \
-                         : "=&s"(keep_)                                                                             \
-                         : "v"(voff), "s"(rsrc), "s"(lds_rows + 1024u * u)                                          \
-                         : "memory");                                                                               \
-        }                                                                                                           \
-    }
     int jv[SC];
     double wv[SC];
     unsigned long long lm[SC];
@@ -756,9 +768,7 @@ __device__ __forceinline__ void fpfh_mcl_body(const double *__restrict__ rec, co
 #pragma unroll
         for (int c = 0; c < SC; ++c) wmax = fmax(wmax, wv[c]);
     }
-    wmax = sf_wave_max_nonneg(wmax);
-    const int e2 = wmax > 0.0 ? (int)((__double2hiint(wmax) >> 20) & 0x7ff) - 1023 : 0;
-    const int S = 61 - e2;
+    const int S = fpfh_mc_exponent(wmax);
     v4i acc[8];
 #pragma unroll
     for (int bb = 0; bb < 8; ++bb) acc[bb] = v4i{0, 0, 0, 0};
@@ -771,19 +781,15 @@ __device__ __forceinline__ void fpfh_mcl_body(const double *__restrict__ rec, co
 #pragma unroll
         for (int st = 0; st < 2 * SC; ++st) {
             if (st < nst) { // wave-uniform
-                SF_MCLF_DMA(st)
+                SF_MC_DMA_ROWS(st, false)
                 if ((st & 1) == 0) fpfh_mc_limbs(abuf, lane, wv[st >> 1], S);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_wave_barrier();
                 const long A = fpfh_mc_a_operand(abuf, a, kb, st);
                 const unsigned char *rb = reinterpret_cast<const unsigned char *>(rowbuf);
 #pragma unroll
-                for (int bb = 0; bb < 8; ++bb) {
-                    const v2i_t t = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i_t *)(rb + xoff[bb]));
-                    const long B = (long)(((unsigned long long)(unsigned)t[1] << 32) | (unsigned)t[0]);
-                    acc[bb] = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, B, acc[bb], 0, 0, 0);
-                }
-                if (PADC) accp = __builtin_amdgcn_mfma_i32_16x16x32_i8(A, (long)0x8080808080808080ull, accp, 0, 0, 0);
+                for (int bb = 0; bb < 8; ++bb) acc[bb] = fpfh_mc_mfma(A, fpfh_mc_tr_read(rb + xoff[bb]), acc[bb]);
+                if (PADC) accp = fpfh_mc_mfma(A, SF_MC_BPAD, accp);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_wave_barrier();
             }
@@ -791,41 +797,23 @@ __device__ __forceinline__ void fpfh_mcl_body(const double *__restrict__ rec, co
         fpfh_mc_hi<SC>(hi, jv, wv, lm, o0, o1, h0, h1);
     }
     // ---- recombination: fpfh_mc_body's, the limb pairs formed in float64 ----
-    int rpad[4];
+    int rp[4]; // the padding column: the constant operand's, or column 15 of bb = 7 (bin 127) of the table
 #pragma unroll
-    for (int r = 0; r < 4; ++r) rpad[r] = PADC ? accp[r] : __builtin_amdgcn_update_dpp(0, acc[7][r], 0x150 + 15, 0xf, 0xf, false); // bin 127: the padding column
-    const double p0 = ldexp(1.0, 32 * kb - S);
-    const double f0 = p0, f2 = p0 * 65536.0;
-    const double kd = (double)k;
-    double inv_k = __builtin_amdgcn_rcp(kd);
-    inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
-    inv_k = __builtin_fma(inv_k, __builtin_fma(-kd, inv_k, 1.0), inv_k);
+    for (int r = 0; r < 4; ++r) rp[r] = PADC ? accp[r] : __builtin_amdgcn_update_dpp(0, acc[7][r], 0x150 + 15, 0xf, 0xf, false);
+    const v4i rpad = v4i{rp[0], rp[1], rp[2], rp[3]};
+    double f0, f2;
+    fpfh_mc_scales(kb, S, f0, f2);
+    const double kd = (double)k, inv_k = sf_fpfh_inv(kd);
     double part[8];
 #pragma unroll
-    for (int bb = 0; bb < 8; ++bb)
-        part[bb] = __builtin_fma(fpfh_mcl_pair(acc[bb][3], acc[bb][2], rpad[3], rpad[2]), f2, fpfh_mcl_pair(acc[bb][1], acc[bb][0], rpad[1], rpad[0]) * f0);
-    double keep[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        double a_ = part[u], b_ = part[4 + u];
-        sf_lane_swap<32>(a_, b_);
-        keep[u] = a_ + b_;
-    }
-    double a0 = keep[0], b0_ = keep[2], a1 = keep[1], b1_ = keep[3];
-    sf_lane_swap<16>(a0, b0_);
-    sf_lane_swap<16>(a1, b1_);
-    const double vsel0 = a0 + b0_, vsel1 = a1 + b1_;
+    for (int bb = 0; bb < 8; ++bb) part[bb] = fpfh_mcl_part(acc[bb], rpad, f0, f2);
+    double vsel0, vsel1;
+    fpfh_mc_reduce_full(part, vsel0, vsel1);
     {
-        double *o = out + q * (int64_t)W.nb3;
-        fpfh_mc_zero_outside(o, W, lane);
-        o += W.win_lo;
         const double r0 = (double)own0 / kd + (vsel0 + h0) * inv_k, r1 = (double)own1 / kd + (vsel1 + h1) * inv_k;
-        if (W.win_len == W.nb3 && W.win_len <= 126) { // (wave-uniform)
-            fpfh_mc_store_row(o, W.win_len, o0, r0, o1, r1, reinterpret_cast<double *>(rowbuf), lane);
-        } else {
-            if (o0 < W.win_len) sf_store_stream(o + o0, r0);
-            if (o1 < W.win_len) sf_store_stream(o + o1, r1);
-        }
+        fpfh_mc_finish_row(out, q, W, o0, o1, r0, r1, rowbuf, lane);
     }
-#undef SF_MCLF_DMA
 }
+
+#undef SF_MC_DMA_ROWS
+#undef SF_MC_DMA_PAIR
