@@ -646,6 +646,29 @@ int sf_icp_accumulate_trimmed(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev,
                               const int64_t *sel_dev, int64_t m, const double *Rt, double d_max, int mode /* 0, 1, 2 */, double epsilon,
                               int loss /* 0 .. 4 */, double scale, double trim /* in (0, 1] */, double *sums /* 48 */);
 
+/* ---- symmetric point-to-plane ICP, K19 (Rusinkiewicz, "A Symmetric Objective Function for ICP", SIGGRAPH 2019; no counterpart in
+ * the reference) --------
+ * The chain of the calls above in a fourth mode, with sf_icp_accumulate_robust's weight and sf_icp_accumulate_trimmed's share.  The
+ * reference cloud needs normals; nrm_dev holds the scan's (required), reached through sel_dev and turned by Rt as in
+ * sf_icp_accumulate_gicp.  For a pair inside d_max (the gate is applied first and is unchanged) with p the moved point, b its
+ * neighbour, nb b's normal and m = R n_scan:
+ *   s = +1 if (m0 nb0 + m1 nb1) + m2 nb2 >= 0, else -1          the sign of either normal cancels
+ *   n = 0.5 (nb + s m)                                          the mean normal; a zero row on one side leaves half the other
+ *   h = (b - p) . n,  r2 = h h                                  a length: point-to-plane's h for parallel unit normals
+ *   c = p + b,  g = [c x n, n]
+ * The weight comes from r2, loss and scale as in sf_icp_accumulate_robust; rank, cut and the used pairs from r2 and trim as in
+ * sf_icp_accumulate_trimmed.  sums[48] (host), that call's layout with mode 1's slots:
+ *   [0] the USED pair count, [1..3] sum p, [4..6] sum b, [7] sum w,
+ *   [8..28] upper triangle of sum w g g^T row by row, [29..34] sum w g h, [35] sum |h|, [36] sum |b - p|^2  (both unweighted),
+ *   [37] n0, [38] the rank, [40..42] sum w p, [43..45] sum w b, [46] sum w r2, [47] the cut; the rest is zero.
+ * The host step: x = solve(sum w g g^T, sum w g h), a = x[0..2], t = x[3..5], theta = atan |a|, R_h the rotation by theta about a;
+ * e = a / |a|; the pair of clouds is aligned by p <- R_h (R_h p + cos(theta) t + (1 - cos(theta)) (e . t) e).
+ * With trim == 1.0 no selection is launched: [37] = [38] = [0] and [47] = 0.  One host wait, at the end.  With no pair inside d_max
+ * everything is zero.  SF_ERR_ARG names the offending argument in sf_last_error(). */
+int sf_icp_accumulate_symmetric(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev /* scan normals, required */,
+                                const int64_t *sel_dev, int64_t m, const double *Rt, double d_max, int loss /* 0 .. 4 */, double scale,
+                                double trim /* in (0, 1] */, double *sums /* 48 */);
+
 /* ---- multi-GPU: RCCL over xGMI (no counterpart in the reference) --------------------------
  * One process per GPU.  Rank 0 calls sf_comm_unique_id, ships the 128 bytes to the other ranks by
  * any host channel, then every rank calls sf_comm_init.  sf_comm_allgather gathers

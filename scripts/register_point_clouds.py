@@ -61,10 +61,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--ransac-edge-similarity", type=float, default=0.9), p.add_argument("--ransac-refit", type=int, default=2)
     p.add_argument("--ransac-threshold", type=float, default=1.0)
     p.add_argument("--fgr-iterations", type=int, default=64), p.add_argument("--fgr-tuples", type=int, default=0)
-    p.add_argument("--icp", default="point_to_plane", choices=["point_to_point", "point_to_plane", "generalized", "none"],
-                   help="generalized: plane-to-plane ICP, every pair weighted by the local surface of both clouds")
+    p.add_argument("--icp", default="point_to_plane", choices=["point_to_point", "point_to_plane", "generalized", "symmetric", "none"],
+                   help="generalized: plane-to-plane ICP, every pair weighted by the local surface of both clouds; "
+                        "symmetric: point-to-plane along the mean of both clouds' normals")
     p.add_argument("--gicp-neighbors", type=int, default=20, metavar="K",
-                   help="--icp generalized: neighbours of a normal that the clouds do not bring along")
+                   help="--icp generalized, symmetric: neighbours of a normal that the clouds do not bring along")
     p.add_argument("--gicp-epsilon", type=float, default=1e-3, metavar="EPS",
                    help="--icp generalized: a point's covariance along its normal, in (0, 1]")
     p.add_argument("--icp-loss", default=None, choices=["none", "huber", "cauchy", "geman_mcclure", "tukey"],

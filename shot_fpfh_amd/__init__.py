@@ -10,6 +10,7 @@ from ._ffi import ShotFpfhError
 from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor, compute_normals
 from .engine import Cloud, DeviceArray, Engine, Neighbors, Spfh, default_engine
 from .helpers import get_data, read_ply, write_ply
+from .icp import icp_symmetric
 from .matching import (
     basic_matching,
     fast_global_registration,
@@ -45,6 +46,7 @@ __all__ = [
     "SecondOrderRecord",
     "sc2_registration",
     "Sc2RegistrationRecord",
+    "icp_symmetric",
     "RegistrationPipeline",
     "read_ply",
     "write_ply",

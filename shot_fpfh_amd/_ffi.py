@@ -138,6 +138,7 @@ SIGNATURES = {
     "sf_icp_accumulate_gicp": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64, _f64, _vp]),
     "sf_icp_accumulate_robust": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64, _int, _f64, _int, _f64, _vp]),
     "sf_icp_accumulate_trimmed": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64, _int, _f64, _int, _f64, _f64, _vp]),
+    "sf_icp_accumulate_symmetric": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64, _int, _f64, _f64, _vp]),
     "sf_select_kth": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "sf_comm_unique_id": (_int, [_vp]),
     "sf_comm_init": (_int, [_vp, _vp, _int, _int]),

@@ -15,7 +15,7 @@
 // fixed order, so a run is reproducible bit for bit.  Point-to-point is centred in a second pass (centroids first),
 // which keeps the cross-covariance free of cancellation, like the reference's explicit centring.
 //
-// ONE kernel family, k_icp_sums<PASS, MODE>, and ONE host chain, icp_chain, serve the three entry points:
+// ONE kernel family, k_icp_sums<PASS, MODE>, and ONE host chain, icp_chain, serve every entry point:
 //   MODE 0 point to point, MODE 1 point to plane (sf_icp_accumulate);
 //   MODE 2 generalized (plane-to-plane) ICP, K16 (Segal, Haehnel, Thrun, RSS 2009; no counterpart in the reference): every pair is
 //     weighted by M = (C_b + R C_a R^T)^-1, C = I - (1 - eps) n n^T from the unit normal of either point, and the 6x6 Gauss-Newton
@@ -25,6 +25,9 @@
 //   K18, trimmed ICP for all three modes (no counterpart in the reference): a key pass writes every pair's squared residual, the radix
 //     selection of select.hip finds the order statistic that bounds the best-fitting share of them, and both sums passes leave out the
 //     pairs beyond that cut (sf_icp_accumulate_trimmed).  The residual is formed by ONE function, icp_pair_residual, for all of them.
+//   K19, MODE 3, the symmetric point-to-plane objective (Rusinkiewicz, SIGGRAPH 2019; no counterpart in the reference): the residual
+//     of a pair is taken along the mean of its two normals and its lever arm is p + b; the 6x6 system is point-to-plane's, with a loss
+//     and a trim like the others (sf_icp_accumulate_symmetric).
 // The two plain entry points are the chain with loss none: every weight is 1.0, w * term is the term, and they return the first 40
 // of its 48 numbers with [7] (sum w) cleared.
 #include "common.h"
@@ -146,6 +149,21 @@ __device__ inline bool icp_pair_residual(int64_t i, const double *__restrict__ q
         P.maha = (dx * P.u[0] + dy * P.u[1]) + dz * P.u[2];
         P.r2 = P.maha < 0.0 ? 0.0 : P.maha;
     }
+    if (MODE == 3) { // K19: the residual along the mean of the two normals; P.nx .. P.nz become that mean
+        const int64_t row = qrow ? (int64_t)qrow[i] : i;
+        const int64_t j = sel ? sel[row] : row;
+        const double ax = nrm[3 * j], ay = nrm[3 * j + 1], az = nrm[3 * j + 2];
+        double m0 = ax, m1 = ay, m2 = az;
+        if (turned) {
+            m0 = (ax * R[0] + ay * R[1]) + az * R[2];
+            m1 = (ax * R[3] + ay * R[4]) + az * R[5];
+            m2 = (ax * R[6] + ay * R[7]) + az * R[8];
+        }
+        const double s = (m0 * nx + m1 * ny) + m2 * nz >= 0.0 ? 1.0 : -1.0; // the sign of either normal cancels
+        P.nx = 0.5 * (nx + s * m0); P.ny = 0.5 * (ny + s * m1); P.nz = 0.5 * (nz + s * m2);
+        P.h = (dx * P.nx + dy * P.ny) + dz * P.nz;
+        P.r2 = P.h * P.h;
+    }
     return true;
 }
 
@@ -160,7 +178,7 @@ __global__ __launch_bounds__(256) void k_icp_keys(const double *__restrict__ qx,
                                                   uint64_t *__restrict__ keys)
 {
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (MODE == 2 && Rt) {
+    if ((MODE == 2 || MODE == 3) && Rt) {
 #pragma unroll
         for (int v = 0; v < 9; ++v) R[v] = Rt[v];
     }
@@ -178,6 +196,8 @@ __global__ __launch_bounds__(256) void k_icp_keys(const double *__restrict__ qx,
 //   PASS 1, MODE 0 (point to point): centred cross-covariance H = sum w (p - pbar)(q - qbar)^T (9) and sum |p - q|^2, centred with
 //           `mean`, the WEIGHTED centroids k_icp_means leaves
 //   PASS 1, MODE 1 (point to plane): upper triangle of G^T G (21), G^T h (6), sum |h| with g = [p x n, n], h = (q - p) . n
+//   PASS 1, MODE 3 (symmetric, K19): MODE 1's sums with the lever arm c = p + b for p and the mean normal n = (nb + s m) / 2 for nb
+//           (m as in MODE 2, s = +1 if (m0 nb0 + m1 nb1) + m2 nb2 >= 0 else -1), h = (b - p) . n, and sum |b - p|^2 behind sum |h| (29)
 //   PASS 1, MODE 2 (generalized, K16): with p the moved scan point, b its nearest reference point, nb b's normal, na the scan point's
 //           normal (row qrow[slot] of the scan, through sel) and c = 1 - eps:
 //     m   = (na.x R0 + na.y R1) + na.z R2 per row of R (no t; m = na when Rt is null)
@@ -188,7 +208,7 @@ __global__ __launch_bounds__(256) void k_icp_keys(const double *__restrict__ qx,
 //     Q   = [p]x M  (Q_0j = py M_2j - pz M_1j, ...),  T = Q [p]x^T  (T_i0 = py Q_i2 - pz Q_i1, ...)
 //     H   = J^T M J = [[T, Q], [Q^T, M]] (upper triangle, 21),  g = J^T M r = [p x u; u] (6),  r.u,  |r|^2  with J = [-[p]x, I]
 //           A zero normal makes its dyad vanish (C = I); the sign of a normal cancels in the dyad.
-// The pair's squared residual r2 is d2 (MODE 0), h h (MODE 1) or the Mahalanobis term (r0 u0 + r1 u1) + r2 u2 clamped at 0 (MODE 2),
+// The pair's squared residual r2 is d2 (MODE 0), h h (MODES 1 and 3) or the Mahalanobis term (r0 u0 + r1 u1) + r2 u2 clamped at 0 (MODE 2),
 // formed by icp_pair_residual above, and both passes form w from it by the same operations, so they get the same bits.  PASS 1
 // multiplies every fit term by w (one more rounding); the residual sums the host reports as rms stay unweighted: d2 (MODE 0: [9],
 // MODE 2: [28]), |h| (MODE 1: [27]), the Mahalanobis term as formed (MODE 2: [27]).
@@ -215,7 +235,7 @@ __global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx,
         qm[0] = mean[3]; qm[1] = mean[4]; qm[2] = mean[5];
     }
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (MODE == 2 && Rt) {
+    if ((MODE == 2 || MODE == 3) && Rt) {
 #pragma unroll
         for (int v = 0; v < 9; ++v) R[v] = Rt[v];
     }
@@ -246,8 +266,10 @@ __global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx,
             acc[3] += w * (ay * bx); acc[4] += w * (ay * by); acc[5] += w * (ay * bz);
             acc[6] += w * (az * bx); acc[7] += w * (az * by); acc[8] += w * (az * bz);
             acc[9] += d2;
-        } else if constexpr (MODE == 1) {
-            const double g[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz}; // cross(p, n), n
+        } else if constexpr (MODE == 1 || MODE == 3) {
+            // the lever arm: p (MODE 1), c = p + b (MODE 3, where n is the mean normal icp_pair_residual left)
+            const double lx = MODE == 3 ? px + x : px, ly = MODE == 3 ? py + y : py, lz = MODE == 3 ? pz + z : pz;
+            const double g[6] = {ly * nz - lz * ny, lz * nx - lx * nz, lx * ny - ly * nx, nx, ny, nz}; // cross(lever, n), n
             int t = 0;
 #pragma unroll
             for (int a = 0; a < 6; ++a)
@@ -256,6 +278,7 @@ __global__ __launch_bounds__(256) void k_icp_sums(const double *__restrict__ qx,
 #pragma unroll
             for (int a = 0; a < 6; ++a) acc[21 + a] += w * (g[a] * h);
             acc[27] += fabs(h);
+            if constexpr (MODE == 3) acc[28] += d2;
         } else {
             double Q[3][3];
 #pragma unroll
@@ -361,7 +384,8 @@ static int icp_chain(const char *who, sf_ctx *ctx, sf_cloud *ref, const double *
               (const double *)dRt, m, d_max, epsilon, keys)
         if (mode == 0) { SF_ICP_KEYS(0); }
         else if (mode == 1) { SF_ICP_KEYS(1); }
-        else { SF_ICP_KEYS(2); }
+        else if (mode == 2) { SF_ICP_KEYS(2); }
+        else { SF_ICP_KEYS(3); }
 #undef SF_ICP_KEYS
         SF_CHECK(sf_select_launch(ctx, keys, m, 0, trim, dout + 48)); // [48] the cut, [52] n0, [53] the rank
         cut = dout + 48;
@@ -371,11 +395,13 @@ static int icp_chain(const char *who, sf_ctx *ctx, sf_cloud *ref, const double *
               sel_dev, (const double *)dRt, m, d_max, epsilon, loss, scale, mean, cut, partial)
     if (mode == 0) { SF_ICP_PASS(0, 0, no_mean); }
     else if (mode == 1) { SF_ICP_PASS(0, 1, no_mean); }
-    else { SF_ICP_PASS(0, 2, no_mean); }
+    else if (mode == 2) { SF_ICP_PASS(0, 2, no_mean); }
+    else { SF_ICP_PASS(0, 3, no_mean); }
     SF_LAUNCH(ctx, "i1_icp_means", k_icp_means, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, dout, dmean);
     if (mode == 0) { SF_ICP_PASS(1, 0, (const double *)dmean); }
     else if (mode == 1) { SF_ICP_PASS(1, 1, no_mean); }
-    else { SF_ICP_PASS(1, 2, no_mean); }
+    else if (mode == 2) { SF_ICP_PASS(1, 2, no_mean); }
+    else { SF_ICP_PASS(1, 3, no_mean); }
 #undef SF_ICP_PASS
     SF_LAUNCH(ctx, "i1_icp_final", k_icp_final, dim3(1), dim3(64), (const double *)partial, ICP_BLOCKS, mode == 0 ? 10 : (mode == 1 ? 28 : 29),
               dout + 8);
@@ -466,6 +492,29 @@ extern "C" int sf_icp_accumulate_trimmed(sf_ctx *ctx, sf_cloud *ref, const doubl
     for (int i = 0; i < 48; ++i) sums[i] = 0.0;
     if (!m) return SF_OK;
     SF_CHECK(icp_chain("sf_icp_accumulate_trimmed", ctx, ref, pts_dev, nrm_dev, sel_dev, m, Rt, d_max, mode, epsilon, loss, scale, sums, trim));
+    if (trim == 1.0) sums[37] = sums[38] = sums[0]; // no selection: every pair inside d_max is used, and the cut stays 0
+    return SF_OK;
+}
+
+// K19: the symmetric point-to-plane objective, the chain in its fourth mode with a loss and a trim (sums[48], layout in include/shotfpfh.h)
+extern "C" int sf_icp_accumulate_symmetric(sf_ctx *ctx, sf_cloud *ref, const double *pts_dev, const double *nrm_dev, const int64_t *sel_dev,
+                                           int64_t m, const double *Rt, double d_max, int loss, double scale, double trim, double *sums)
+{
+    const char *bad = nullptr;
+    if (!ctx) bad = "ctx";
+    else if (!ref) bad = "ref";
+    else if (!pts_dev) bad = "pts_dev";
+    else if (!nrm_dev) bad = "nrm_dev (the symmetric objective needs the scan's normals)";
+    else if (!sums) bad = "sums";
+    else if (m < 0) bad = "m (negative)";
+    else if (loss < 0 || loss > 4) bad = "loss (0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey)";
+    else if (!(scale > 0.0 && scale < INFINITY)) bad = "scale (must be positive and finite)";
+    else if (!(trim > 0.0 && trim <= 1.0)) bad = "trim (must lie in (0, 1])";
+    if (bad) { sf_set_error("sf_icp_accumulate_symmetric: bad argument %s", bad); return SF_ERR_ARG; }
+    SF_HIP(hipSetDevice(ctx->device));
+    for (int i = 0; i < 48; ++i) sums[i] = 0.0;
+    if (!m) return SF_OK;
+    SF_CHECK(icp_chain("sf_icp_accumulate_symmetric", ctx, ref, pts_dev, nrm_dev, sel_dev, m, Rt, d_max, 3, 1.0, loss, scale, sums, trim));
     if (trim == 1.0) sums[37] = sums[38] = sums[0]; // no selection: every pair inside d_max is used, and the cut stays 0
     return SF_OK;
 }

@@ -26,6 +26,12 @@ call (`sf_icp_accumulate_trimmed`) finds the exact order statistic of the residu
 best-fitting share (a radix selection, csrc/select.hip) and sums over the pairs up to it only.  The share comes down from 1 to
 `overlap` over the first iterations: a fixed share from a coarse start is worse than no trimming, the same lesson as the scale's.
 
+`icp_symmetric` (K19) has no counterpart in the reference either: the symmetric point-to-plane objective (Rusinkiewicz, SIGGRAPH
+2019).  A pair's residual is taken along the mean of its two normals and its lever arm is p + b, so it vanishes whenever the pair
+lies on a common second-order patch, not only on a common plane; the 6x6 system is point-to-plane's, with no per-pair inverse.  The
+device call (`sf_icp_accumulate_symmetric`, the chain in its fourth mode) carries a loss and a trim of its own, and the host applies
+the paper's rotate-translate-rotate step (`_symmetric_fit`).
+
 Deviation, on purpose: the reference's `icp_point_to_point` computes its RMS from `ref[neighbors]` (all queried points,
 shape (n, 1, 3)) instead of `ref[inliers_neighbors]` (icp.py:122-124); the broadcast yields an array, and formatting it for
 the progress bar raises TypeError on the first iteration, so that function cannot run there at all.  Here the RMS is taken
@@ -55,11 +61,15 @@ __all__ = [
     "icp_generalized",
     "icp_robust",
     "icp_trimmed",
+    "icp_symmetric",
     "compute_point_to_point_error",
     "nearest_within",
 ]
 
 _POINT, _PLANE, _GICP = 0, 1, 2
+# The chain's fourth mode has a call of its own (sf_icp_accumulate_symmetric) and is NOT a `mode` of the shared calls, which keep
+# rejecting 3: `_MODES` stays their three, and `pairs` tells the symmetric objective by this marker, never by a number.
+_SYMMETRIC = "symmetric"
 _TRIU = np.triu_indices(6)
 _MODES = {"point_to_point": _POINT, "point_to_plane": _PLANE, "generalized": _GICP}
 LOSSES = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3, "tukey": 4}  # the `loss` of sf_icp_accumulate_robust
@@ -103,6 +113,9 @@ class _PairSums:
             self.gth = raw[29:35]
             if mode == _PLANE:
                 self.abs_h = float(raw[35])           # sum |(q - p) . n|
+            elif mode == _SYMMETRIC:                  # gtg = sum w g g^T, gth = sum w g h, g = [(p + q) x n, n], n the mean normal
+                self.abs_h = float(raw[35])           # sum |(q - p) . n|
+                self.sq_dist = float(raw[36])         # sum |q - p|^2
             else:                                     # generalized: gtg = sum J^T M J, gth = sum J^T M r, J = [-[p]x, I], r = q - p
                 self.mahalanobis = float(raw[35])     # sum r^T M r
                 self.sq_dist = float(raw[36])         # sum |r|^2
@@ -155,6 +168,24 @@ def _gicp_fit(s: _PairSums) -> RigidTransform:
     return RigidTransform(_rodrigues(s.step[:3]), s.step[3:6])
 
 
+def _symmetric_fit(s: _PairSums) -> RigidTransform:
+    """The step of the symmetric objective from x = solve(sum w g g^T, sum w g h) = [a~, t~]: theta = atan |a~|, R_h the rotation
+    by theta about e = a~ / |a~|, and p <- R_h (R_h p + cos(theta) t~ + (1 - cos(theta))(e . t~) e) -- the paper's rotate, translate,
+    rotate, without its centring, and with t~'s component along the axis left unscaled: that is (I - [a~]x)^-1 t~ turned by R_h^-1,
+    the exact translation of the linear system, so a rigid copy with exact pairs is recovered in ONE step (the paper's cos(theta) t~
+    leaves the share 1 - cos(theta) of that component to the next iteration; the fixed points are the same)."""
+    s.require_pairs()
+    s.step = np.linalg.solve(s.gtg, s.gth)
+    norm = math.sqrt((s.step[0] * s.step[0] + s.step[1] * s.step[1]) + s.step[2] * s.step[2])
+    if not norm > 0.0:
+        return RigidTransform(np.eye(3), s.step[3:6])
+    theta = math.atan(norm)
+    half = _rodrigues((theta / norm) * s.step[:3])
+    e, c = s.step[:3] / norm, math.cos(theta)
+    along = (e[0] * s.step[3] + e[1] * s.step[4]) + e[2] * s.step[5]
+    return RigidTransform(half @ half, half @ (c * s.step[3:6] + ((1.0 - c) * along) * e))
+
+
 class _Registration:
     """Working points + reference cloud resident on one GPU for the length of an ICP run; for generalized ICP also the
     working points' normals (`scan_normals`, one unit or zero row per point)."""
@@ -180,7 +211,8 @@ class _Registration:
               epsilon: float = 1e-3, loss: Optional[int] = None, scale: float = 1.0, trim: float = 1.0) -> _PairSums:
         """Inlier-pair sums of the working points (all of them, or the given `rows`) after `moved_by`; with a `loss` (0 .. 4,
         `LOSSES`) the 48 weighted sums of sf_icp_accumulate_robust at `scale`; with a `trim` below 1 the 48 sums of
-        sf_icp_accumulate_trimmed over that share of the pairs (a trim of 1.0 is the call without one)."""
+        sf_icp_accumulate_trimmed over that share of the pairs (a trim of 1.0 is the call without one).  The symmetric mode has
+        one call, sf_icp_accumulate_symmetric, for all of it: always 48 numbers, no loss being loss 0."""
         m, sel = self.n, None
         if rows is not None:
             rows = _checked_rows(rows, self.n)
@@ -193,14 +225,17 @@ class _Registration:
                 _ffi.check(self.engine.lib.sf_h2d(self.engine.h, self.rows.ptr, rows.ctypes.data_as(C.c_void_p), m * 8), "sf_h2d")
             sel = self.rows.ptr
         rt = None if moved_by is None else np.ascontiguousarray(moved_by.as_row12())
-        if mode == _GICP and self.normals is None:
-            raise ValueError("generalized ICP needs the normals of the working points")
+        if mode in (_GICP, _SYMMETRIC) and self.normals is None:
+            raise ValueError(f"{'generalized' if mode == _GICP else 'symmetric'} ICP needs the normals of the working points")
         trimmed = float(trim) != 1.0
-        raw = np.zeros(40 if loss is None and not trimmed else 48)
+        raw = np.zeros(40 if loss is None and not trimmed and mode != _SYMMETRIC else 48)
         head = (self.engine.h, self.ref.h, self.points.ptr)
         rows_and_motion = (sel, m, None if rt is None else rt.ctypes.data_as(C.c_void_p), float(d_max))
         out = raw.ctypes.data_as(C.c_void_p)
-        if trimmed:
+        if mode == _SYMMETRIC:
+            name, args = "sf_icp_accumulate_symmetric", (*head, self.normals.ptr, *rows_and_motion, int(loss or 0), float(scale),
+                                                         float(trim), out)
+        elif trimmed:
             name, args = "sf_icp_accumulate_trimmed", (*head, self.normals.ptr if mode == _GICP else None, *rows_and_motion, int(mode),
                                                        float(epsilon), int(loss or 0), float(scale), float(trim), out)
         elif loss is not None:
@@ -411,7 +446,7 @@ def _refine_robust(reg: _Registration, start: RigidTransform, mode: int, d_max: 
     below 1 (K18) iteration i fits the share `trimmed_overlap(.., i)` of the pairs, the residual is over the pairs used, and a
     small step stops the run only once the share, too, has come down to `overlap`."""
     total, rms, small_step = start, 0.0, False
-    fit = {_POINT: _weighted_rigid_fit, _PLANE: _plane_fit, _GICP: _gicp_fit}[mode]
+    fit = {_POINT: _weighted_rigid_fit, _PLANE: _plane_fit, _GICP: _gicp_fit, _SYMMETRIC: _symmetric_fit}[mode]
     try:
         for i in range(max_iter):
             k = annealed_scale(scale, scale_start, division_factor, i)
@@ -424,7 +459,7 @@ def _refine_robust(reg: _Registration, start: RigidTransform, mode: int, d_max: 
                 rms = float(np.sqrt(found.sq_dist))
                 size = max(float(np.abs(step.rotation - np.eye(3)).max()), float(np.abs(step.translation).max()))
             else:
-                rms = found.abs_h / found.count if mode == _PLANE else float(np.sqrt(found.sq_dist / found.count))
+                rms = found.abs_h / found.count if mode in (_PLANE, _SYMMETRIC) else float(np.sqrt(found.sq_dist / found.count))
                 size = float(np.abs(found.step).max())
             small_step = k == scale and share == overlap and size < step_tolerance
             if rms < rms_threshold:
@@ -573,6 +608,68 @@ def icp_trimmed(
     try:
         return _refine_robust(reg, transformation_init, kind, d_max, LOSSES[loss], float(scale), float(scale_start),
                               float(division_factor), max_iter, rms_threshold, epsilon, step_tolerance, float(overlap),
+                              int(anneal_iterations))
+    finally:
+        reg.close()
+
+
+def icp_symmetric(
+    scan: npt.NDArray[np.float64],
+    ref: npt.NDArray[np.float64],
+    transformation_init: RigidTransform,
+    d_max: float,
+    *,
+    scan_normals: Optional[npt.NDArray[np.float64]] = None,
+    ref_normals: Optional[npt.NDArray[np.float64]] = None,
+    k_normals: int = 20,
+    loss: str = "none",
+    scale: Optional[float] = None,
+    scale_start: Optional[float] = None,
+    division_factor: float = 1.4,
+    overlap: float = 1.0,
+    anneal_iterations: int = 10,
+    voxel_size: float = 0.2,
+    max_iter: int = 50,
+    rms_threshold: float = 1e-2,
+    step_tolerance: float = 1e-9,
+) -> tuple[RigidTransform, float, bool]:
+    """Symmetric point-to-plane ICP, K19 (Rusinkiewicz, SIGGRAPH 2019): a pair's residual is h = (b - p) . n along the mean
+    n = (nb + s R na) / 2 of the reference point's normal and the moved scan point's (s = +-1 makes them agree in sign, so the
+    orientation of either normal does not matter), and its lever arm is p + b.  h vanishes whenever the pair lies on a common
+    second-order patch, not only on a common plane, at point-to-plane's cost: the same 6x6 system, no per-pair inverse, no
+    epsilon.  Normals are treated as `icp_generalized` treats them: computed from `k_normals` neighbours of the full clouds when
+    not given, normalised when given, zero rows kept (n is then half the other normal).
+    `loss` and `scale` (.. `scale_start`, `division_factor`) weight the pairs as `icp_robust` does, from h h, in point-to-plane's
+    unit; `overlap` below 1 (.. `anneal_iterations`) fits only that share of them as `icp_trimmed` does.
+    Returns (transform, rms = mean |h| of the pairs the last step was fitted on, converged); converged means rms < rms_threshold,
+    or a step x = [a~, t~] with max|x| < step_tolerance once scale and share have come down."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss={loss!r}: expected one of {sorted(LOSSES)}")
+    if overlap is None or not 0.0 < float(overlap) <= 1.0:
+        raise ValueError(f"overlap={overlap!r} must lie in (0, 1]")
+    if int(anneal_iterations) != anneal_iterations or anneal_iterations < 0:
+        raise ValueError(f"anneal_iterations={anneal_iterations!r} must be a non-negative integer (0 switches the annealing off)")
+    if loss == "none":
+        scale = scale_start = 1.0  # no weight looks at it
+    elif scale is None or not 0.0 < float(scale) < math.inf:
+        raise ValueError(f"scale={scale!r} must be positive and finite (loss={loss!r} needs one)")
+    scale_start = d_max if scale_start is None else scale_start
+    if not 0.0 < float(scale_start) < math.inf:
+        raise ValueError(f"scale_start={scale_start!r} must be positive and finite (it defaults to d_max)")
+    if not 1.0 < float(division_factor) < math.inf:
+        raise ValueError(f"division_factor={division_factor!r} must be greater than 1 (scale_start=scale switches the annealing off)")
+    if not step_tolerance >= 0.0:
+        raise ValueError(f"step_tolerance={step_tolerance} must not be negative")
+    scan, ref = np.asarray(scan, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    for name, a in (("scan", scan), ("ref", ref)):
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name}: expected an (N, 3) array, got shape {a.shape}")
+    scan_normals, ref_normals = _both_normals(scan, ref, scan_normals, ref_normals, k_normals)
+    keep = grid_subsampling(scan, voxel_size)
+    reg = _Registration(scan[keep], ref, ref_normals, scan_normals=scan_normals[keep])
+    try:
+        return _refine_robust(reg, transformation_init, _SYMMETRIC, d_max, LOSSES[loss], float(scale), float(scale_start),
+                              float(division_factor), max_iter, rms_threshold, 1.0, step_tolerance, float(overlap),
                               int(anneal_iterations))
     finally:
         reg.close()

@@ -19,7 +19,7 @@ from . import keypoint_selection as _ks
 from .core import RigidTransform
 from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor
 from .helpers import write_ply
-from .icp import icp_generalized, icp_point_to_plane, icp_point_to_point, icp_robust, icp_trimmed, nearest_within
+from .icp import icp_generalized, icp_point_to_plane, icp_point_to_point, icp_robust, icp_symmetric, icp_trimmed, nearest_within
 from .matching import (
     basic_matching,
     double_matching_with_rejects,
@@ -260,7 +260,7 @@ class RegistrationPipeline:
         return transformation, inliers_ratio
 
     # ---- stage 5: fine registration (pipeline.py:488-542) ---------------------------------------------------------
-    def run_icp(self, icp_type: Literal["point_to_point", "point_to_plane", "generalized"], transformation_init: RigidTransform, *,
+    def run_icp(self, icp_type: Literal["point_to_point", "point_to_plane", "generalized", "symmetric"], transformation_init: RigidTransform, *,
                 d_max: float, voxel_size: float = 0.2, max_iter: int = 30, rms_threshold: float = 1e-2,
                 disable_progress_bar: bool = False, gicp_neighbors: int = 20,
                 gicp_epsilon: float = 1e-3, robust_loss: Optional[str] = None, robust_scale: Optional[float] = None,
@@ -271,7 +271,20 @@ class RegistrationPipeline:
         `robust_loss` ("huber", "cauchy", "geman_mcclure", "tukey", "none"; K17) runs the chosen `icp_type` through `icp_robust` with
         the loss's scale `robust_scale`, annealed from `robust_scale_start` (`d_max` unless given); None is the call of before.
         `trim_overlap` (K18) runs it through `icp_trimmed`, fitting only that share of the pairs within `d_max`, annealed from 1 over
-        `trim_anneal_iterations` iterations; it combines with `robust_loss`.  None is the call of before."""
+        `trim_anneal_iterations` iterations; it combines with `robust_loss`.  None is the call of before.
+        "symmetric" (K19, no counterpart in the reference): `icp_symmetric`, the residual along the mean of both clouds' normals, with
+        the normals treated as "generalized" treats them (`gicp_neighbors` for the missing ones); it takes `robust_loss` and
+        `trim_overlap` itself."""
+        if icp_type == "symmetric":
+            if robust_loss not in (None, "none") and robust_scale is None:
+                raise ValueError(f"robust_loss={robust_loss!r} needs robust_scale, the loss's scale in the residual's unit")
+            if robust_loss is None and (robust_scale is not None or robust_scale_start is not None):
+                raise ValueError("robust_scale and robust_scale_start need a robust_loss")
+            return icp_symmetric(self.scan, self.ref, transformation_init, d_max, scan_normals=self.scan_normals,
+                                 ref_normals=self.ref_normals, k_normals=gicp_neighbors, loss=robust_loss or "none",
+                                 scale=robust_scale, scale_start=robust_scale_start,
+                                 overlap=1.0 if trim_overlap is None else trim_overlap, anneal_iterations=trim_anneal_iterations,
+                                 voxel_size=voxel_size, max_iter=max_iter, rms_threshold=rms_threshold)
         if trim_overlap is not None:
             if robust_loss not in (None, "none") and robust_scale is None:
                 raise ValueError(f"robust_loss={robust_loss!r} needs robust_scale, the loss's scale in the residual's unit")

@@ -7,6 +7,7 @@ sf_icp_accumulate_robust without a loss and with Cauchy.  The yardstick is the o
 Writes a markdown table.  Needs an MI355X.
 
     python tools/icp_trimmed_ab.py abl_libs/other_tree [--rounds 3] [--out profiles/icp_trimmed_ab.md]
+A later change to the kernel family names itself with --title and --change (K19: profiles/icp_symmetric_ab.md).
 """
 from __future__ import annotations
 
@@ -19,6 +20,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = ("plain", "none", "cauchy")
+TITLE = "Trimmed ICP (K18)"
+CHANGE = ("K18 gave `k_icp_sums` one more argument, a nullable pointer to the cut, which the three existing entry points pass as null, "
+          "and moved the residual into a function it shares with the key pass")
 
 
 def run(tree):
@@ -33,6 +37,8 @@ def main() -> int:
     ap.add_argument("other")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "icp_trimmed_ab.md"))
+    ap.add_argument("--title", default=TITLE, help="what the new tree adds, for the heading")
+    ap.add_argument("--change", default=CHANGE, help="what it changed in the code the existing calls run, for the text")
     a = ap.parse_args()
     trees = {"parent": os.path.abspath(a.other), "new": ROOT}
     runs = {name: [] for name in trees}
@@ -41,12 +47,11 @@ def main() -> int:
             runs[name].append(run(tree))
             print(f"round {r + 1} {name}: " + ", ".join(f"{m} {v['plain']['one_iteration_host_to_host_ms_median']:.3f}"
                                                         for m, v in runs[name][-1]["modes"].items()), flush=True)
-    out = ["# Trimmed ICP (K18): the existing ICP calls against the parent commit, same box", "",
+    out = [f"# {a.title}: the existing ICP calls against the parent commit, same box", "",
            f"Written by `tools/icp_trimmed_ab.py` from one call on one MI355X: the parent commit's tree (its own library, Python and tools)",
            f"and this tree, alternating, {a.rounds} rounds; in every round `tools/bench_icp_robust.py` with its defaults (a 10^5-point scan against",
            "a 10^6-point reference, 21 repeats after 3 warm-up rounds), every run a process of its own.  The figure is the one-iteration",
-           "host-to-host median in ms.  K18 gave `k_icp_sums` one more argument, a nullable pointer to the cut, which the three existing",
-           "entry points pass as null, and moved the residual into a function it shares with the key pass; the bar is the parent's own",
+           f"host-to-host median in ms.  {a.change}; the bar is the parent's own",
            "spread (max - min) over its rounds: the new median passes where it lies within that spread of the parent's median, or below it.", "",
            f"libraries: parent `{runs['parent'][0]['library']}`, new `{runs['new'][0]['library']}`", "",
            "| mode | call | parent, rounds | parent median | parent spread | new, rounds | new median | new - parent | within the spread |",
