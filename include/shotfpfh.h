@@ -212,6 +212,13 @@ int sf_iss_keypoints(sf_ctx *ctx, sf_cloud *cloud, double salient_radius, double
  * the neighbours centred on their barycentre (:121-144).  The feature formulas on top stay on the host. */
 int sf_pca(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, double *eigenvalues /* m x 3 */,
            double *eigenvectors /* m x 9 */, double *moments /* nullable, m x 8 */, int flags);
+/* numpy.linalg.eigh of m symmetric 3 x 3 matrices given by their lower triangles, elementwise: the device function K3, K4 and
+ * the ISS saliency solve with (LAPACK dsyevd's values, eigenvector order AND signs for max|a| in [1.0010415475915505e-146,
+ * 9.989595361011175e+145]; outside it LAPACK rescales the matrix first and this function does not).  w: ascending;
+ * v[9 i + 3 r + k] = component r of eigenvector k of matrix i, as sf_pca stores them.  A test hook: one matrix per lane.
+ * m == 0 returns at once.  flags: SF_IN_DEVICE = lower is a device pointer, SF_OUT_DEVICE = w and v are. */
+int sf_eigh3(sf_ctx *ctx, const double *lower /* m x 6: a11 a21 a31 a22 a32 a33 */, int64_t m, double *w /* m x 3 */,
+             double *v /* m x 9 */, int flags);
 
 /* ---- SHOT --------------------------------------------------------------------------------
  * sf_shot_lrf (K4): get_local_rf (shot.py:16-48) for every query of `nbrs`; radius = the search

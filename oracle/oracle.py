@@ -114,6 +114,17 @@ def eigh3(a):
     return w, v
 
 
+def eigh3_batch(a):
+    """orc_eigh3 on every matrix of an (m, 3, 3) stack: (w (m, 3), v (m, 3, 3)), shaped like np.linalg.eigh's."""
+    a = _f64(a).reshape(-1, 3, 3)
+    w = np.zeros((a.shape[0], 3))
+    v = np.zeros((a.shape[0], 3, 3))
+    f = lib().orc_eigh3
+    for i in range(a.shape[0]):
+        f(a[i], w[i], v[i])
+    return w, v
+
+
 # --------------------------------------------------------------------------------------------
 # (a2) compute_normals, radius branch (pca_based_descriptors.py:29-59)
 # --------------------------------------------------------------------------------------------

@@ -75,6 +75,7 @@ SIGNATURES = {
     "sf_iss_select": (_int, [_vp, _vp, _vp, _f64, _int, _vp, _vp, _int]),
     "sf_iss_keypoints": (_int, [_vp, _vp, _f64, _f64, _f64, _f64, _int, _vp, _vp, _vp, _int]),
     "sf_pca": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int]),
+    "sf_eigh3": (_int, [_vp, _vp, _i64, _vp, _vp, _int]),
     "sf_shot_lrf": (_int, [_vp, _vp, _vp, _vp, _int]),
     "sf_shot": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _vp, _int]),
     "sf_shot_single_scale": (_int, [_vp, _vp, _vp, _int, _i64, _vp, _vp, _int]),

@@ -10,15 +10,24 @@
 // carried out here in float64 registers, so signs agree except for numerically repeated
 // eigenvalues, where the basis is rounding noise in LAPACK too.
 //
+// Domain: this is dsyevd for max|a| in [1.0010415475915505e-146, 9.989595361011175e+145] (rmin = sqrt(safmin / eps),
+// rmax = sqrt(eps / safmin)).  Outside it dsyevd first rescales the whole matrix (dlascl) and this header does not -- a
+// covariance that small or large is a point spread under 1e-73 or over 1e73 -- so there the result is whatever dsteqr's own
+// inner scaling (ssfmin, ssfmax below) makes of it: still the test suite's CPU restatement bit for bit, not LAPACK's,
+// and not finite near the ends of the exponent range.
+//
+// Host and device: every function is __host__ __device__ so that the very same text can be compiled for the host and
+// checked without a GPU (tests/eigh3_host_shim.hip); the library only ever calls it from kernels.
+//
 // All state is scalar (no arrays indexed at run time) so it stays in VGPRs.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace sf_eig {
 
-__device__ inline double fsign(double a, double b) { return copysign(fabs(a), b); } // Fortran SIGN
+__host__ __device__ inline double fsign(double a, double b) { return copysign(fabs(a), b); } // Fortran SIGN
 
-__device__ inline double pythag(double x, double y) // dlapy2
+__host__ __device__ inline double pythag(double x, double y) // dlapy2
 {
     double xa = fabs(x), ya = fabs(y);
     double w = fmax(xa, ya), z = fmin(xa, ya);
@@ -28,10 +37,10 @@ __device__ inline double pythag(double x, double y) // dlapy2
 }
 
 // Givens rotation, LAPACK >= 3.10 convention (c >= 0, r carries the sign of f).
-__device__ inline void givens(double f, double g, double &c, double &s, double &r)
+__host__ __device__ inline void givens(double f, double g, double &c, double &s, double &r)
 {
     const double safmin = 2.2250738585072014e-308, safmax = 1.0 / safmin;
-    const double rtmin = 1.4916681462400413e-154, rtmax = 9.480751908109176e+153; // sqrt(safmin), sqrt(safmax/2)
+    const double rtmin = 1.4916681462400413e-154, rtmax = 4.740375954054589e+153; // sqrt(safmin), sqrt(safmax/2)
     double f1 = fabs(f), g1 = fabs(g);
     if (g == 0.0) {
         c = 1.0; s = 0.0; r = f;
@@ -54,7 +63,7 @@ __device__ inline void givens(double f, double g, double &c, double &s, double &
 }
 
 // Eigen-decomposition of [[a, b], [b, c]] (dlaev2): rt1 has the larger |.|, (cs1, sn1) its vector.
-__device__ inline void sym2x2(double a, double b, double c, double &rt1, double &rt2, double &cs1, double &sn1)
+__host__ __device__ inline void sym2x2(double a, double b, double c, double &rt1, double &rt2, double &cs1, double &sn1)
 {
     double sm = a + c, df = a - c, adf = fabs(df), tb = b + b, ab = fabs(tb);
     double acmx = fabs(a) > fabs(c) ? a : c, acmn = fabs(a) > fabs(c) ? c : a;
@@ -90,7 +99,7 @@ struct tri3 {
     double z11, z21, z31, z12, z22, z32, z13, z23, z33; // z<row><col>
 
     // rotate columns (j, j+1), j in {1,2}: dlasr side='R', pivot='V' body
-    __device__ inline void rot(int j, double ct, double st)
+    __host__ __device__ inline void rot(int j, double ct, double st)
     {
         if (ct == 1.0 && st == 0.0) return;
         if (j == 1) {
@@ -106,20 +115,20 @@ struct tri3 {
         }
     }
     // select-based accessors: a run-time index into a register array would be spilled to scratch
-    __device__ inline double D(int i) const { return i == 1 ? d1 : (i == 2 ? d2 : d3); }
-    __device__ inline double E(int i) const { return i == 1 ? e1 : e2; }
-    __device__ inline void setD(int i, double v)
+    __host__ __device__ inline double D(int i) const { return i == 1 ? d1 : (i == 2 ? d2 : d3); }
+    __host__ __device__ inline double E(int i) const { return i == 1 ? e1 : e2; }
+    __host__ __device__ inline void setD(int i, double v)
     {
         d1 = i == 1 ? v : d1;
         d2 = i == 2 ? v : d2;
         d3 = i == 3 ? v : d3;
     }
-    __device__ inline void setE(int i, double v)
+    __host__ __device__ inline void setE(int i, double v)
     {
         e1 = i == 1 ? v : e1;
         e2 = i == 2 ? v : e2;
     }
-    __device__ inline void swap_cols(int i, int k)
+    __host__ __device__ inline void swap_cols(int i, int k)
     {
         // only (1,2), (1,3), (2,3) occur
         double t;
@@ -131,10 +140,10 @@ struct tri3 {
 
 // dsteqr(compz='I') specialised to n = 3.  The sequence of floating-point operations per matrix is LAPACK's (labels in
 // comments) because the rotation sequence determines the eigenvector signs; its QL and QR loops share one body (below).
-__device__ inline void steqr3(tri3 &T)
+__host__ __device__ inline void steqr3(tri3 &T)
 {
     const double eps = 1.1102230246251565e-16, eps2 = eps * eps, safmin = 2.2250738585072014e-308;
-    const double ssfmax = 4.4692311799612e+153 /* sqrt(1/safmin)/3 */, ssfmin = 1.2100683175775647e-122 /* sqrt(safmin)/eps^2 */;
+    const double ssfmax = 2.2346346549904327e+153 /* sqrt(1/safmin)/3 */, ssfmin = 1.210184973390412e-122 /* sqrt(safmin)/eps^2 */;
     T.z11 = T.z22 = T.z33 = 1.0;
     T.z21 = T.z31 = T.z12 = T.z32 = T.z13 = T.z23 = 0.0;
     const int n = 3, nmaxit = 90;
@@ -297,7 +306,7 @@ struct eig3 {
     double v11, v21, v31, v12, v22, v32, v13, v23, v33;
 };
 
-__device__ inline eig3 eigh3_lower(double a11, double a21, double a31, double a22, double a32, double a33)
+__host__ __device__ inline eig3 eigh3_lower(double a11, double a21, double a31, double a22, double a32, double a33)
 {
     tri3 T;
     double tau = 0.0, v2 = 0.0;

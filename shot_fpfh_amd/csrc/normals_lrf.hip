@@ -575,6 +575,45 @@ extern "C" int sf_shot_lrf(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double *lrf, i
 }
 
 namespace {
+// eigh3.h as an elementwise function: the very device function K3, K4 and the ISS saliency solve with, called as they call
+// it, one matrix per lane (a test hook, like sf_azimuth_idx)
+__global__ __launch_bounds__(256) void k_eigh3(const double *__restrict__ lower, int64_t m, double *__restrict__ out_w,
+                                               double *__restrict__ out_v)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= m) return;
+    const double *c = lower + 6 * q;
+    const sf_eig::eig3 e = sf_eig::eigh3_lower(c[0], c[1], c[2], c[3], c[4], c[5]);
+    out_w[3 * q + 0] = e.w1; out_w[3 * q + 1] = e.w2; out_w[3 * q + 2] = e.w3;
+    double *v = out_v + 9 * q; // row-major: v[3 i + k] = component i of eigenvector k
+    v[0] = e.v11; v[1] = e.v12; v[2] = e.v13;
+    v[3] = e.v21; v[4] = e.v22; v[5] = e.v23;
+    v[6] = e.v31; v[7] = e.v32; v[8] = e.v33;
+}
+} // namespace
+
+extern "C" int sf_eigh3(sf_ctx *ctx, const double *lower, int64_t m, double *w, double *v, int flags)
+{
+    if (!ctx) { sf_set_error("sf_eigh3: null ctx"); return SF_ERR_ARG; }
+    if (!lower) { sf_set_error("sf_eigh3: null lower"); return SF_ERR_ARG; }
+    if (m < 0) { sf_set_error("sf_eigh3: m < 0"); return SF_ERR_ARG; }
+    if (!w) { sf_set_error("sf_eigh3: null w"); return SF_ERR_ARG; }
+    if (!v) { sf_set_error("sf_eigh3: null v"); return SF_ERR_ARG; }
+    if (m == 0) return SF_OK;
+    SF_HIP(hipSetDevice(ctx->device));
+    sf_pool_guard tmp(ctx);
+    const double *dlower;
+    double *dw, *dv;
+    SF_CHECK(stage_in(tmp, lower, (size_t)m * 6, flags, &dlower));
+    SF_CHECK(stage_out(tmp, w, (size_t)m * 3, flags, &dw));
+    SF_CHECK(stage_out(tmp, v, (size_t)m * 9, flags, &dv));
+    SF_LAUNCH(ctx, "k3_eigh3", k_eigh3, dim3((unsigned)sf_div_up(m, 256)), dim3(256), dlower, m, dw, dv);
+    SF_CHECK(finish_out(ctx, w, (size_t)m * 3, flags, dw));
+    SF_CHECK(finish_out(ctx, v, (size_t)m * 9, flags, dv));
+    return stage_sync(ctx, flags);
+}
+
+namespace {
 // K4 when the moments come from K6 (sf_spfh_compute_moments): one LAPACK-compatible 3 x 3 eigen-solve per lane, the
 // largest / smallest eigenvectors stored as k_shot_lrf does in its raw mode (the fused K5 completes the frame).
 // It is meant to run on the side stream UNDER K7, which holds eight 64-register waves on every SIMD: a wave of this kernel

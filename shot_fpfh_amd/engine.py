@@ -335,6 +335,17 @@ class Engine:
         _ffi.check(self.lib.sf_azimuth_idx(self.h, _ptr(x), _ptr(y), x.size, _ptr(out), SF_HOST), "sf_azimuth_idx")
         return out
 
+    def eigh3(self, a):
+        """np.linalg.eigh of an (m, 3, 3) stack (the lower triangles are read) evaluated by the device function K3, K4 and
+        the ISS saliency solve with: (w (m, 3) ascending, v (m, 3, 3) with column k the eigenvector of w[:, k])."""
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 3 or a.shape[1:] != (3, 3):
+            raise ValueError(f"expected an (m, 3, 3) array, got shape {a.shape}")
+        lower = np.ascontiguousarray(np.stack([a[:, 0, 0], a[:, 1, 0], a[:, 2, 0], a[:, 1, 1], a[:, 2, 1], a[:, 2, 2]], axis=1))
+        w, v = np.zeros((a.shape[0], 3)), np.zeros((a.shape[0], 3, 3))
+        _ffi.check(self.lib.sf_eigh3(self.h, _ptr(lower), a.shape[0], _ptr(w), _ptr(v), SF_HOST), "sf_eigh3")
+        return w, v
+
     # ---- matching (K8) / RANSAC scoring (K9) ------------------------------------------------------
     def match_argmin(self, a, b, want_dist=True, want_col=False):
         """Row arg-min of cdist(a, b) (first minimum), winners' distances, optional column arg-min."""
