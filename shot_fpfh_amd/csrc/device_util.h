@@ -224,6 +224,25 @@ __device__ inline void sf_store_stream2(double *p, double a, double b)
 #define SF_LIST_LOAD(p) __builtin_nontemporal_load(p)
 #define SF_LIST_STORE(p, v) __builtin_nontemporal_store((int)(v), p)
 
+// Wave priority for the head of a wave of K7.  The SIMD's arbiter serves the oldest ready wave first, so a wave that has just
+// started issues the dozen address instructions and loads of its head -- header, indices, DMA of the rows, record gathers: a
+// chain of dependent memory round trips during which it has nothing else to do -- in whatever slots the seven older, computing
+// waves leave, and every link of the chain starts late.  The wave therefore runs at priority 1 from its first instruction until
+// its up-front DMA statements and its record loads have been issued, and at 0 from there on: the loads of a new wave go out at
+// once, under the arithmetic of the others.  Scheduling only: no result changes.  Same-box A/B in profiles/list_head_ab.md:
+// K7 -9 %.  The same two statements in K5 and K6 cost those kernels 2-3 %, so they have none.
+// -DSF_HEAD_PRIO=0 (make HEAD_EXTRA=-DSF_HEAD_PRIO=0) builds without it.  Never under a lane test: wave-uniform instructions.
+#ifndef SF_HEAD_PRIO
+#define SF_HEAD_PRIO 1
+#endif
+#if SF_HEAD_PRIO
+#define SF_HEAD_PRIO_RAISE() __builtin_amdgcn_s_setprio(1)
+#define SF_HEAD_PRIO_DROP() __builtin_amdgcn_s_setprio(0)
+#else
+#define SF_HEAD_PRIO_RAISE()
+#define SF_HEAD_PRIO_DROP()
+#endif
+
 // XCD-aware block remap.  Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 says which blocks
 // share an XCD / an L2).  Consecutive queries are spatial neighbours (cell-sorted order), so giving each
 // XCD ONE contiguous eighth of the queries makes the cells a query needs hot in that XCD's own 4 MB L2

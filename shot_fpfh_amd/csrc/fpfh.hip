@@ -234,6 +234,7 @@ __global__ __launch_bounds__(64 * SF_MC_WPB) __attribute__((amdgpu_waves_per_eu(
 {
     __shared__ __attribute__((aligned(16))) unsigned rowbuf_all[SF_MC_WPB][32 * 32]; // 32 rows of 128 B
     __shared__ __attribute__((aligned(16))) unsigned char abuf_all[SF_MC_WPB][9 * 64];
+    SF_HEAD_PRIO_RAISE(); // (until the weight pass has issued its record loads: device_util.h, fpfh_mc_weights)
     const int wv_id = threadIdx.x >> 6;
     // (the query pick stays written out in the three kernels: behind a function the first MFMA block of 17 instantiations grew)
     int64_t q = sf_uniform64(sf_xcd_block() * SF_MC_WPB + wv_id);
@@ -270,6 +271,7 @@ __global__ __launch_bounds__(64 * SF_MC_WPB) __attribute__((amdgpu_waves_per_eu(
     static_assert(!MOM || NKS <= 3, "the moments ride on the forms of at most three chunks");
     __shared__ __attribute__((aligned(16))) unsigned rowbuf_all[SF_MC_WPB][32 * 32]; // four steps of 32 rows x 32 B
     __shared__ __attribute__((aligned(16))) unsigned char abuf_all[SF_MC_WPB][9 * 64];
+    SF_HEAD_PRIO_RAISE(); // (until the weight pass has issued its record loads: device_util.h, fpfh_mc_weights)
     const int wv_id = threadIdx.x >> 6;
     // (the query pick stays written out in the three kernels: behind a function the first MFMA block of 17 instantiations grew)
     int64_t q = sf_uniform64(sf_xcd_block() * SF_MC_WPB + wv_id);

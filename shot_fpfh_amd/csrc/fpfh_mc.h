@@ -209,6 +209,7 @@ __device__ __forceinline__ int fpfh_mc_weights(const double *__restrict__ p4, do
             gx[c] = u0.x; gy[c] = u0.y; gz[c] = u1.x; gk[c] = u1.y;
         }
     }
+    SF_HEAD_PRIO_DROP(); // (raised at the kernel's start; the up-front DMA statements and the record loads have been issued)
     double wmax = 0.0;
     double ws = 0, a11 = 0, a21 = 0, a31 = 0, a22 = 0, a32 = 0, a33 = 0;
 #pragma unroll
