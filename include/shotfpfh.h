@@ -204,6 +204,30 @@ int sf_iss_select(sf_ctx *ctx, sf_cloud *cloud, const double *saliency /* n */, 
 int sf_iss_keypoints(sf_ctx *ctx, sf_cloud *cloud, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
                      int min_neighbors, double *saliency /* nullable, n */, int64_t *selected /* n */, int64_t *n_selected,
                      int flags);
+/* ---- Outlier removal (K20): the filters PCL and Open3D run in front of the normals; the reference has neither ----
+ * Statistical: mean[i] = (sum of the distances from point i to its k + 1 nearest cloud points) / k -- the nearest is the point
+ * itself or an exact duplicate, distance 0 -- i.e. the mean distance to the k nearest OTHER points; mu = sum(mean) / n,
+ * sigma = sqrt(sum((mean - mu)^2) / (n - 1)), threshold = mu + std_ratio sigma; point i is kept <=> mean[i] <= threshold.
+ * n >= 2, 1 <= k <= n - 1, std_ratio finite.  sf_knn_mean_distance: mean in the CALLER's point order (the self query of
+ * sf_knn_search at k + 1, which builds its own grid, and one pass over its lists: the bits depend on the cloud and k alone).
+ * flags: SF_OUT_DEVICE = mean is a device pointer. */
+int sf_knn_mean_distance(sf_ctx *ctx, sf_cloud *cloud, int k, double *mean /* n */, int flags);
+/* sf_knn_mean_distance, the two statistics (fixed-order sums: a call repeats bit for bit) and the selection, nothing leaving
+ * the device in between; bit-identical to the separate steps.  mean (nullable, n): receives the mean distances; stats (host,
+ * nullable, 3): mu, sigma, threshold -- the very threshold the mask was taken against; selected (room for n): the kept int64
+ * indices in ascending caller order; *n_selected (host): how many.  Behind the search the call waits for the device once, at
+ * its end (a host `selected` receives all n slots then, the first *n_selected of them meaningful).
+ * flags: SF_OUT_DEVICE = mean and selected are device pointers. */
+int sf_outliers_statistical(sf_ctx *ctx, sf_cloud *cloud, int k, double std_ratio, double *mean /* nullable, n */,
+                            double *stats /* host, 3: mu, sigma, threshold */, int64_t *selected /* n */, int64_t *n_selected,
+                            int flags);
+/* Radius: count[i] = the size of the ball of `radius` around point i, i included (the inclusion rule of sf_radius_search; K2's
+ * count sweep, no lists), caller order; point i is kept <=> count[i] - 1 >= min_neighbors.  radius > 0 and finite,
+ * min_neighbors >= 0.  The sweep runs on the grid sf_cloud_build_grid makes for `radius` (rebuilt if the cloud carries another).
+ * flags: SF_OUT_DEVICE = count (sf_outliers_radius: nullable) and selected are device pointers. */
+int sf_ball_counts(sf_ctx *ctx, sf_cloud *cloud, double radius, int32_t *count /* n */, int flags);
+int sf_outliers_radius(sf_ctx *ctx, sf_cloud *cloud, double radius, int min_neighbors, int32_t *count /* nullable, n */,
+                       int64_t *selected /* n */, int64_t *n_selected, int flags);
 /* Local PCA of every query's neighbourhood, same kernel (K3) with the full decomposition as output: replaces
  * the per-point loops of compute_sphericity / compute_pca_based_basic_features (pca_based_descriptors.py:60-73,
  * 150-187, via pca() :15-26) and compute_local_pca_with_moments (:75-146).  eigenvalues: ascending, m x 3.

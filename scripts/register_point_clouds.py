@@ -5,7 +5,7 @@ scripts/register_point_clouds.py, with plain argparse flags instead of its YAML 
     python scripts/register_point_clouds.py scan.ply ref.ply --radius 0.05 --descriptor shot_single_scale \
         --keypoints subsampling --keypoint-size 0.03 --ransac-threshold 0.01 --icp point_to_plane --icp-dmax 0.05
 
-Stages: read PLY (+ PCA normals, k nearest neighbours) -> keypoints -> SHOT / FPFH descriptors -> matching ->
+Stages: read PLY (optionally --outliers: stray points removed; + PCA normals, k nearest neighbours) -> keypoints -> SHOT / FPFH descriptors -> matching ->
 RANSAC -> ICP -> overlap metrics; optionally writes the aligned pair as PLY.
 """
 from __future__ import annotations
@@ -16,10 +16,13 @@ import os
 import sys
 import time
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from shot_fpfh_amd import compute_normals  # noqa: E402
-from shot_fpfh_amd.helpers import get_data  # noqa: E402
+from shot_fpfh_amd.helpers import get_data, read_ply  # noqa: E402
+from shot_fpfh_amd.outlier_removal import remove_radius_outliers, remove_statistical_outliers  # noqa: E402
 from shot_fpfh_amd.pipeline import RegistrationPipeline  # noqa: E402
 
 
@@ -28,6 +31,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("scan"), p.add_argument("ref")
     p.add_argument("--normals-k", type=int, default=30, help="neighbours for the PCA normals (reference default 30)")
     p.add_argument("--keep-stored-normals", action="store_true", help="use the file's normals instead of recomputing them")
+    p.add_argument("--outliers", default="none", choices=["none", "statistical", "radius"],
+                   help="remove stray points from both clouds right after loading, before the normals are computed: statistical "
+                        "(mean distance to --outlier-neighbors neighbours above mean + --outlier-std-ratio sigma) or radius (fewer "
+                        "than --outlier-min-neighbors other points within --outlier-radius)")
+    p.add_argument("--outlier-neighbors", type=int, default=20, metavar="K")
+    p.add_argument("--outlier-std-ratio", type=float, default=2.0, metavar="S")
+    p.add_argument("--outlier-radius", type=float, default=None, metavar="R")
+    p.add_argument("--outlier-min-neighbors", type=int, default=2, metavar="N")
     p.add_argument("--keypoints", default="subsampling", choices=["random", "iterative", "subsampling", "subsampling_with_density", "iss"])
     p.add_argument("--keypoint-size", type=float, default=None,
                    help="sphere / voxel size of the keypoint selection (iss: the salient radius, default 6 x the cloud's resolution)")
@@ -84,6 +95,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--metric-threshold", type=float, default=0.1)
     p.add_argument("--write", default=None, help="basename for the aligned clouds (<name>_ransac.ply, <name>_icp.ply)")
     args = p.parse_args(argv)
+    if args.outliers == "radius" and args.outlier_radius is None:
+        p.error("--outliers radius needs --outlier-radius")
     if args.icp_loss is not None and args.icp_loss_scale is None:
         p.error("--icp-loss needs --icp-loss-scale")
     if args.icp_loss is None and (args.icp_loss_scale is not None or args.icp_loss_scale_start is not None):
@@ -95,14 +108,40 @@ def parse_args(argv=None) -> argparse.Namespace:
     return args
 
 
+def load_filtered(path: str, args: argparse.Namespace):
+    """(points, normals, kept) of a PLY cloud with --outliers on: what get_data does, with the filter between the file and the
+    normals -- the stored normals of the kept points are used as they are (--keep-stored-normals) or orient the ones
+    computed on the filtered cloud."""
+    data = read_ply(path)
+    points = np.vstack((data["x"], data["y"], data["z"])).T
+    stored = next((names for names in (("nx", "ny", "nz"), ("n_x", "n_y", "n_z")) if names[0] in data.dtype.fields), None)
+    if args.outliers == "statistical":
+        kept = remove_statistical_outliers(points, args.outlier_neighbors, args.outlier_std_ratio)
+    else:
+        kept = remove_radius_outliers(points, args.outlier_radius, args.outlier_min_neighbors)
+    logging.info(f"{kept.shape[0]} points kept out of {points.shape[0]} in {path} (--outliers {args.outliers})")
+    points = np.ascontiguousarray(points[kept])
+    pre = None if stored is None else np.vstack([data[name] for name in stored]).T[kept]
+    if pre is not None and args.keep_stored_normals:
+        return points, pre, kept
+    extra = {} if pre is None else {"pre_computed_normals": pre}
+    return points, compute_normals(points, points, k=args.normals_k, radius=None, **extra), kept
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     t0 = time.perf_counter()
-    load = dict(recompute_normals=not args.keep_stored_normals, k=args.normals_k, normals_computation_callback=compute_normals)
-    scan, scan_normals = get_data(args.scan, **load)
-    ref, ref_normals = get_data(args.ref, **load)
-    pipe = RegistrationPipeline(scan=scan, scan_normals=scan_normals, ref=ref, ref_normals=ref_normals)
+    if args.outliers == "none":
+        load = dict(recompute_normals=not args.keep_stored_normals, k=args.normals_k, normals_computation_callback=compute_normals)
+        scan, scan_normals = get_data(args.scan, **load)
+        ref, ref_normals = get_data(args.ref, **load)
+        pipe = RegistrationPipeline(scan=scan, scan_normals=scan_normals, ref=ref, ref_normals=ref_normals)
+    else:
+        scan, scan_normals, scan_kept = load_filtered(args.scan, args)
+        ref, ref_normals, ref_kept = load_filtered(args.ref, args)
+        pipe = RegistrationPipeline(scan=scan, scan_normals=scan_normals, ref=ref, ref_normals=ref_normals, scan_kept=scan_kept,
+                                    ref_kept=ref_kept)
     pipe.select_keypoints(args.keypoints, neighborhood_size=args.keypoint_size, min_n_neighbors=args.min_n_neighbors,
                           proportion_picked=args.proportion, iss_non_max_radius=args.iss_non_max_radius,
                           iss_gamma_21=args.iss_gamma21, iss_gamma_32=args.iss_gamma32)

@@ -23,6 +23,7 @@ from .matching import (
     second_order_consistency_filter,
     SecondOrderRecord,
 )
+from .outlier_removal import remove_radius_outliers, remove_statistical_outliers
 from .pipeline import RegistrationPipeline
 
 __all__ = [
@@ -47,6 +48,8 @@ __all__ = [
     "sc2_registration",
     "Sc2RegistrationRecord",
     "icp_symmetric",
+    "remove_statistical_outliers",
+    "remove_radius_outliers",
     "RegistrationPipeline",
     "read_ply",
     "write_ply",

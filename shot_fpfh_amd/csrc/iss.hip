@@ -137,21 +137,13 @@ int check_rule(const char *who, double gamma_21, double gamma_32, int min_neighb
     return SF_OK;
 }
 
-// the grid sf_cloud_build_grid makes for this radius, whatever grid the cloud carries (see "Orders" above)
-int saliency_grid(sf_ctx *ctx, sf_cloud *c, double radius)
-{
-    const bool whole = c->cell_start && c->pop_begin == 0 && c->pop_end == c->n;
-    if (whole && c->cell == radius * (1.0 + 9.5367431640625e-07)) return SF_OK; // (grid.hip: edge = cell (1 + 2^-20))
-    return sf_cloud_build_grid(ctx, c, radius);
-}
-
 // saliency (and counts, nullable) of every point in the caller's order, device pointers
 int saliency_dev(sf_ctx *ctx, sf_cloud *c, double radius, double gamma_21, double gamma_32, int min_neighbors, double *saliency,
                  int32_t *count)
 {
     const int64_t n = c->n;
     if (!n) return SF_OK;
-    SF_CHECK(saliency_grid(ctx, c, radius));
+    SF_CHECK(sf_k2_own_grid(ctx, c, radius)); // (see "Orders" above)
     sf_pool_guard tmp(ctx);
     double *cov = nullptr;
     int32_t *cnt = nullptr;

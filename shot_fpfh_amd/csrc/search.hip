@@ -1034,6 +1034,14 @@ extern "C" int sf_normals_radius(sf_ctx *ctx, sf_cloud *c, const double *queries
 // position, under the timer name `prof`.
 int sf_k2_ensure_grid(sf_ctx *ctx, sf_cloud *c, double radius) { return ensure_grid(ctx, c, radius); }
 
+// the grid sf_cloud_build_grid makes for this radius, whatever grid the cloud carries (iss.hip, "Orders")
+int sf_k2_own_grid(sf_ctx *ctx, sf_cloud *c, double radius)
+{
+    const bool whole = c->cell_start && c->pop_begin == 0 && c->pop_end == c->n;
+    if (whole && c->cell == radius * (1.0 + 9.5367431640625e-07)) return SF_OK; // (grid.hip: edge = cell (1 + 2^-20))
+    return sf_cloud_build_grid(ctx, c, radius);
+}
+
 int sf_k2_radius_cov_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, double *cov, int32_t *count)
 {
     const int64_t m = c->n;
@@ -1041,6 +1049,19 @@ int sf_k2_radius_cov_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *p
     const sf_grid_desc g = sf_make_grid_desc(c);
     SF_LAUNCH(ctx, prof, k_radius_cov, dim3(sf_xcd_grid(sf_div_up(m, 4 * SF_K2C_WPB))), dim3(64 * SF_K2C_WPB), g, c->cell_start, c->xs,
               c->ys, c->zs, c->xs, c->ys, c->zs, m, radius * radius, cov, (double *)nullptr, count);
+    return SF_OK;
+}
+
+// (for outliers.hip) K2's count pass over the cloud's own points, all of them, on the grid the cloud carries: count[q] = size of
+// the ball of position q, q included; count[n] = 0 (the pass writes the element past the last query).
+int sf_k2_count_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, int32_t *count)
+{
+    const int64_t m = c->n;
+    if (!m) return SF_OK;
+    const sf_grid_desc g = sf_make_grid_desc(c);
+    SF_LAUNCH(ctx, prof, (k_radius<0, false>), dim3(sf_xcd_grid(sf_div_up(m, 4 * SF_K2_WPB))), dim3(64 * SF_K2_WPB), g, c->cell_start,
+              c->xs, c->ys, c->zs, c->xs, c->ys, c->zs, m, radius * radius, 0, count, (int64_t *)nullptr, (int32_t *)nullptr,
+              (const int32_t *)nullptr);
     return SF_OK;
 }
 // ---- caller-supplied neighbourhoods ------------------------------------------------------------------------------------------

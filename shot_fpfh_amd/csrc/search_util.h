@@ -162,7 +162,11 @@ __device__ __forceinline__ int2 sf_k2_hit_pos(int total, unsigned long long m0, 
 // search.hip, for knn.hip: queries into processing order, and the lists of a strided sample of them counted at a radius
 int sf_k2_prepare_queries(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const double *queries, int flags);
 int sf_k2_count_sample(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double r2, int32_t *sel_dev, int32_t *cnt_dev);
-// search.hip, for iss.hip: keep or rebuild the grid for a radius, and k_radius_cov over the whole cloud with its counts
+// search.hip, for iss.hip and outliers.hip: keep or rebuild the grid for a radius (sf_k2_own_grid: the grid sf_cloud_build_grid
+// makes for this very radius, whatever valid grid the cloud carries), k_radius_cov over the whole cloud with its counts, and
+// the count sweep (k_radius, MODE 0) over the whole cloud: count[n + 1] by cell-sorted position
 int sf_k2_ensure_grid(sf_ctx *ctx, sf_cloud *c, double radius);
+int sf_k2_own_grid(sf_ctx *ctx, sf_cloud *c, double radius);
 int sf_k2_radius_cov_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, double *cov, int32_t *count);
+int sf_k2_count_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, int32_t *count);
 

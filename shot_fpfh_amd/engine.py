@@ -1030,6 +1030,50 @@ class Cloud:
         idx = sel[: k.value].copy()
         return (idx, sal) if return_saliency else idx
 
+    # ---- outlier removal (K20) ----------------------------------------------------------------------------
+    def knn_mean_distance(self, k: int) -> np.ndarray:
+        """sf_knn_mean_distance: every point's mean distance to its k nearest OTHER cloud points (an exact duplicate counts
+        as another point at distance 0); caller order."""
+        if not 1 <= int(k) <= self.n - 1:
+            raise ValueError(f"k={k} must be between 1 and the number of other cloud points ({self.n - 1})")
+        mean = np.zeros(self.n, dtype=np.float64)
+        _ffi.check(self.engine.lib.sf_knn_mean_distance(self.engine.h, self.h, int(k), _ptr(mean), SF_HOST), "sf_knn_mean_distance")
+        return mean
+
+    def statistical_outliers(self, k: int, std_ratio: float, return_stats: bool = False):
+        """sf_outliers_statistical: the int64 indices, ascending, of the points whose mean distance to their k nearest other
+        points is at most mu + std_ratio sigma over the cloud [, the mean distances and (mu, sigma, threshold)]."""
+        if not 1 <= int(k) <= self.n - 1:
+            raise ValueError(f"k={k} must be between 1 and the number of other cloud points ({self.n - 1})")
+        if not np.isfinite(float(std_ratio)):
+            raise ValueError(f"std_ratio must be finite (got {std_ratio})")
+        mean = np.zeros(self.n, dtype=np.float64) if return_stats else None
+        stats = np.zeros(3, dtype=np.float64)
+        sel = np.zeros(self.n, dtype=np.int64)
+        kept = C.c_int64(0)
+        _ffi.check(self.engine.lib.sf_outliers_statistical(self.engine.h, self.h, int(k), float(std_ratio), _ptr(mean), _ptr(stats),
+                                                          _ptr(sel), C.byref(kept), SF_HOST), "sf_outliers_statistical")
+        idx = sel[: kept.value].copy()
+        return (idx, mean, stats) if return_stats else idx
+
+    def ball_counts(self, radius: float) -> np.ndarray:
+        """sf_ball_counts: the number of cloud points within `radius` of every point, itself included (K2's count sweep, no
+        lists); int32, caller order."""
+        cnt = np.zeros(self.n, dtype=np.int32)
+        _ffi.check(self.engine.lib.sf_ball_counts(self.engine.h, self.h, float(radius), _ptr(cnt), SF_HOST), "sf_ball_counts")
+        return cnt
+
+    def radius_outliers(self, radius: float, min_neighbors: int, return_counts: bool = False):
+        """sf_outliers_radius: the int64 indices, ascending, of the points with at least min_neighbors OTHER points within
+        `radius` [, the ball sizes, the point itself included]."""
+        cnt = np.zeros(self.n, dtype=np.int32) if return_counts else None
+        sel = np.zeros(max(self.n, 1), dtype=np.int64)
+        kept = C.c_int64(0)
+        _ffi.check(self.engine.lib.sf_outliers_radius(self.engine.h, self.h, float(radius), int(min_neighbors), _ptr(cnt), _ptr(sel),
+                                                     C.byref(kept), SF_HOST), "sf_outliers_radius")
+        idx = sel[: kept.value].copy()
+        return (idx, cnt) if return_counts else idx
+
     def radius_search_self(self, radius: float, begin: int = 0, end: Optional[int] = None) -> "Neighbors":
         end = self.n if end is None else end
         h = _ffi.check_handle(

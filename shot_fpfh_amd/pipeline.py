@@ -33,6 +33,7 @@ from .matching import (
     second_order_consistency_filter,
     threshold_filter,
 )
+from .outlier_removal import remove_radius_outliers, remove_statistical_outliers
 
 __all__ = ["RegistrationPipeline"]
 
@@ -52,6 +53,9 @@ class RegistrationPipeline:
     scan_descriptors: Optional[npt.NDArray[np.float64]] = None
     ref_descriptors: Optional[npt.NDArray[np.float64]] = None
     matches: Optional[tuple[np.ndarray, np.ndarray]] = None
+    # remove_outliers: the indices of the points its last call kept, into the clouds as they stood before that call
+    scan_kept: Optional[np.ndarray] = None
+    ref_kept: Optional[np.ndarray] = None
 
     # ---- helpers: run one function on both sides, honouring the cache ---------------------------------
     def _fill(self, attr: str, force: bool, make: Callable[[str], np.ndarray]) -> None:
@@ -61,6 +65,45 @@ class RegistrationPipeline:
 
     def _cloud(self, side: str):
         return getattr(self, side), getattr(self, f"{side}_normals"), getattr(self, f"{side}_keypoints")
+
+    # ---- stage 0: outlier removal (not in the reference) ---------------------------------------------------
+    def remove_outliers(
+        self,
+        method: Literal["statistical", "radius"],
+        *,
+        nb_neighbors: int = 20,
+        std_ratio: float = 2.0,
+        radius: float | None = None,
+        min_neighbors: int = 2,
+        force_recompute: bool = False,
+    ) -> None:
+        """Filters both clouds and their normals by `remove_statistical_outliers(nb_neighbors, std_ratio)` or
+        `remove_radius_outliers(radius, min_neighbors)`; `scan_kept` / `ref_kept` hold the kept indices.  Keypoints, descriptors
+        and matches index into the clouds: once any of them is filled the call raises ValueError, unless `force_recompute`,
+        which clears them."""
+        pick = {
+            "statistical": lambda p: remove_statistical_outliers(p, nb_neighbors, std_ratio),
+            "radius": lambda p: remove_radius_outliers(p, radius, min_neighbors),
+        }.get(method)
+        if pick is None:
+            raise ValueError("Incorrect outlier removal method.")
+        if method == "radius" and radius is None:
+            raise ValueError('remove_outliers("radius") needs a radius')
+        derived = ("scan_keypoints", "ref_keypoints", "scan_descriptors", "ref_descriptors", "matches")
+        filled = [a for a in derived if getattr(self, a) is not None]
+        if filled and not force_recompute:
+            raise ValueError(f"{', '.join(filled)} index into the clouds: remove the outliers first, or pass force_recompute=True "
+                             "to clear them")
+        logging.info(f"-- Removing outliers: {method} --")
+        kept = {side: pick(getattr(self, side)) for side in ("scan", "ref")}  # (both filters run before anything is replaced)
+        for a in derived:
+            setattr(self, a, None)
+        for side, idx in kept.items():
+            total = getattr(self, side).shape[0]
+            setattr(self, side, getattr(self, side)[idx])
+            setattr(self, f"{side}_normals", getattr(self, f"{side}_normals")[idx])
+            setattr(self, f"{side}_kept", idx)
+            logging.info(f"{idx.shape[0]} points kept on {side} out of {total}.")
 
     # ---- stage 1: keypoints (pipeline.py:53-130) ---------------------------------------------------------
     def select_keypoints(
