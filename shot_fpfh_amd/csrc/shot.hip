@@ -12,9 +12,6 @@
 #include "shot_core.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-int sf_launch_shot_lrf(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int raw, int skip_zero, double *dlrf); // normals_lrf.hip
-int sf_launch_lrf_from_cov(sf_ctx *ctx, const double *cov_dev, int64_t m, double *dlrf);             // normals_lrf.hip
-
 namespace {
 
 
@@ -41,77 +38,6 @@ __global__ void k_azimuth_idx(const double *__restrict__ x, const double *__rest
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = azimuth_octant(x[i], y[i]);
-}
-
-__device__ inline void shot_geometry(double cx, double cy, double cz, double d2, double nx, double ny, double nz,
-                                     const double *E, double half_r, shot_kept &o)
-{
-    double rho, inv_rho;
-    SF_K5_MARK(50, 0);
-    sf_sqrt_rsqrt(d2, rho, inv_rho);
-    SF_K5_PIN(rho); SF_K5_PIN(inv_rho);
-    SF_K5_MARK(51, 0);
-    // (neighbors - point) @ eigenvectors and normals @ eigenvectors[:, 2] (shot.py:214-215) as the multiply-add chain an
-    // FMA BLAS kernel runs over the inner index -- what the reference's NumPy does on any current x86 / OpenBLAS
-    const double lx = sf_dot3(cx, cy, cz, E[0], E[3], E[6]);
-    const double ly = sf_dot3(cx, cy, cz, E[1], E[4], E[7]);
-    const double lz = sf_dot3(cx, cy, cz, E[2], E[5], E[8]);
-    double cosine = sf_dot3(nx, ny, nz, E[2], E[5], E[8]);
-    cosine = fmin(fmax(cosine, -1.0), 1.0);
-    double lxp = lx, lyp = ly, lzp = lz;
-    SF_K5_PIN(lxp); SF_K5_PIN(lyp); SF_K5_PIN(lzp); SF_K5_PIN(cosine);
-    SF_K5_MARK(52, 0);
-    const double cpos = (cosine + 1.0) * 11.0 / 2.0 - 0.5;
-    const double cf = rint(cpos);
-    int ci = (int)cf;
-    double dcp = cpos - cf;
-    SF_K5_PIN(ci); SF_K5_PIN(dcp);
-    SF_K5_MARK(53, 0);
-    int ti = azimuth_octant_wave(lx, ly);
-    SF_K5_PIN(ti);
-    SF_K5_MARK(54, 0);
-    const int pi_ = lz > 0.0 ? 1 : 0;
-    const int ri = rho > half_r ? 1 : 0; // (radius / 2 is exact: the host passes that very double)
-    const double dc = cpos - cf;
-    const int sc = (dc > 0.0) - (dc < 0.0);
-    int cin = ci + sc; // -1 .. 11, wrapped as the reference's % 11 does
-    cin = cin < 0 ? 10 : (cin > 10 ? 0 : cin);
-    // Offset from the octant's centre ray, in the octant's own frame: with a >= b the larger / smaller of |lx|, |ly|, the
-    // point sits atan(b / a) in [0, pi/4] off the nearest axis and the centre ray pi/8 off it, so rotating (a, b) by
-    // -pi/8 gives cross' / dot' = tan(angle off the centre).  Whether theta grows or shrinks with that angle alternates
-    // from octant to octant (even octants: grows).
-    const double C8 = 0.9238795325112867, S8 = 0.3826834323650898; // cos, sin of pi/8
-    const double am = fmax(fabs(lx), fabs(ly)), bm = fmin(fabs(lx), fabs(ly));
-    const double crs = __builtin_fma(C8, bm, -(S8 * am));
-    const double dot = __builtin_fma(C8, am, S8 * bm);
-    const double cross = (ti & 1) ? -crs : crs;
-    int sth;
-    if (fabs(cross) > 1e-9 * (fabs(lx) + fabs(ly))) {
-        sth = cross > 0.0 ? 1 : -1;
-    } else { // on (or within rounding of) the centre ray, or lx = ly = 0: the reference's expression decides
-        const double tsz = 2 * SHOT_PI / 8;
-        double dth = (atan2(ly, lx) - (-SHOT_PI + ti * tsz)) / tsz - 0.5;
-        dth = fmin(fmax(dth, -0.5), 0.5);
-        sth = (dth > 0.0) - (dth < 0.0);
-    }
-    const int tin = (ti + sth) & 7;
-    const unsigned base = (unsigned)(((ci * 8 + ti) * 2 + pi_) * 2 + ri);
-    const unsigned bcos = (unsigned)(((cin * 8 + ti) * 2 + pi_) * 2 + ri);
-    const unsigned bth = (unsigned)(((ci * 8 + tin) * 2 + pi_) * 2 + ri);
-    {
-        double crp = cross, dtp = dot;
-        unsigned b0p = base, b1p = bcos, b2p = bth;
-        SF_K5_PIN(crp); SF_K5_PIN(dtp); SF_K5_PIN(b0p); SF_K5_PIN(b1p); SF_K5_PIN(b2p);
-    }
-    SF_K5_MARK(55, 0);
-    // lz / rho through the reciprocal, then one residual correction: acos has an unbounded derivative at +-1, so for a
-    // neighbour on the frame's z axis a one-ulp error of the quotient would be a 1.5e-8 error of phi (the reference's
-    // correctly rounded division gives exactly +-1 there)
-    double lzr = lz * inv_rho;
-    lzr = __builtin_fma(__builtin_fma(-lzr, rho, lz), inv_rho, lzr);
-    o.rho = rho; o.dc = dc; o.tcross = cross; o.tdot = dot; o.lzr = lzr;
-    o.bins0 = base | (bcos << 9) | (bth << 18);
-    o.bins1 = 0x80000000u | (base & 3u); // (bits 0-1: shell and half-space, for the form that re-maps its slot numbers)
 }
 
 #ifndef SF_SHOT_WPB
@@ -171,25 +97,12 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
     // one gather for all chunks
     double cx[NCH], cy[NCH], cz[NCH], nx[NCH], ny[NCH], nz[NCH];
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int t = c * 64 + lane;
-        const int j = t < k ? SF_LIST_LOAD(idx + s + t) : -1;
-        const int jj = j < 0 ? 0 : j;
-        double x, y, z;
-        sf_load_pn(rec, jj, x, y, z, nx[c], ny[c], nz[c]);
-        cx[c] = x - px; // padding lanes (j < 0) carry point 0's offset; they are masked by `on` / d2 = 0 below
-        cy[c] = y - py;
-        cz[c] = z - pz;
-    }
+    for (int c = 0; c < NCH; ++c) // (padding lanes carry point 0's offset; they are masked by `onm` below)
+        shot_gather64<true>(rec, idx + s, c * 64 + lane, k, px, py, pz, cx[c], cy[c], cz[c], nx[c], ny[c], nz[c]);
     SF_K5_MARK(3, NCH);
-    // the lanes of each chunk that hold a list entry, as wave-uniform masks: votes and gate are mask arithmetic on the scalar
-    // unit (a ballot of a bare comparison is the comparison's own result register)
     unsigned long long onm[NCH];
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int rem = k - 64 * c;
-        onm[c] = rem >= 64 ? ~0ull : (rem > 0 ? (1ull << rem) - 1ull : 0ull);
-    }
+    for (int c = 0; c < NCH; ++c) onm[c] = shot_chunk_mask(k - 64 * c);
     double E[9];
     if (FUSED) {
         double *lr = lrf + 9 * row;
@@ -199,20 +112,16 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
         // compiler, seeing stores to `lrf` in the same kernel, proves that for one of the two inlined bodies only and loads the
         // other's frame into vector registers (every flip below then costs vector instructions).  The pin keeps all nine loads
         // in front of the votes (left alone the scheduler sinks the y loads to their first use: a scalar-memory round trip of
-        // their own in the middle of the kernel).
-        const __attribute__((address_space(4))) double *clr = (const __attribute__((address_space(4))) double *)lr;
+        // their own in the middle of the kernel).  (The same lines stand in k_shot_team: as a function of shot_core.h they
+        // cost k_shot_cached<1, true> four scalar registers and k_shot_team<3, 16, true> two -- profiles/k5_family_isa.md.)
+        sf_const_doubles clr = (sf_const_doubles)lr;
 #pragma unroll
         for (int i = 0; i < 9; ++i) raw[i] = clr[i];
 #pragma unroll
         for (int i = 0; i < 9; ++i) asm volatile("" : "+s"(raw[i]));
         int xneg = 0, zneg = 0;
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) { // the query itself (c = 0) votes ">= 0", as in the reference
-            const double xo = sf_dot3(cx[c], cy[c], cz[c], raw[0], raw[3], raw[6]);
-            const double zo = sf_dot3(cx[c], cy[c], cz[c], raw[2], raw[5], raw[8]);
-            xneg += __popcll(__ballot(xo < 0.0) & onm[c]);
-            zneg += __popcll(__ballot(zo < 0.0) & onm[c]);
-        }
+        for (int c = 0; c < NCH; ++c) shot_count_votes(cx[c], cy[c], cz[c], raw, onm[c], xneg, zneg);
         if (shot_finish_frame(raw, k, xneg, zneg, E) && lane == 0) {
 #pragma unroll
             for (int i = 0; i < 9; ++i) lr[i] = E[i]; // (streamed past the L2 like the rows: no difference)
@@ -223,16 +132,11 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
     }
 
     SF_K5_MARK(4, NCH);
-    // gate (shot.py:212): neighbours at non-zero distance, as one mask per chunk (padding lanes carry point 0's offset: masked)
     double d2[NCH];
     unsigned long long posm[NCH];
     int npos = 0;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        d2[c] = (cx[c] * cx[c] + cy[c] * cy[c]) + cz[c] * cz[c];
-        posm[c] = __ballot(d2[c] > 0.0) & onm[c];
-        npos += __popcll(posm[c]);
-    }
+    for (int c = 0; c < NCH; ++c) shot_gate(cx[c], cy[c], cz[c], onm[c], d2[c], posm[c], npos);
     if (!(npos > (int)min_nb)) { // (launch_shot passes min_nb clamped into [-1, 2^31 - 1]: a scalar 32-bit comparison)
         for (int b = lane; b < SF_SHOT_LEN; b += 64) o[b] = 0.0;
         return;
@@ -263,11 +167,10 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
         // scheduler interleaves them and the kernel needs 87 registers instead of 70 -- 5 waves per SIMD, 1.72 ms; capped at
         // 72 / 80 registers it spills / runs 1.62 ms)
         if (__builtin_amdgcn_inverse_ballot_w64(posm[c])) {
-            shot_geometry(cx[c], cy[c], cz[c], d2[c], nx[c], ny[c], nz[c], E, K.half_r, g[c]);
+            shot_geometry<11>(cx[c], cy[c], cz[c], d2[c], nx[c], ny[c], nz[c], E, K.half_r, 11, 11.0, g[c]);
             g[c].bins0 = shot_swz3(g[c].bins0);
             SF_K5_MARK(6, NCH);
-            const unsigned long long key = (unsigned long long)__double_as_longlong(g[c].rho);
-            atomicMax(&sA[g[c].bins0 & 511u], key);
+            atomicMax(&sA[shot_slot_a<11>(g[c])], shot_key(g[c]));
         }
     }
     SF_SHOT_SYNC();
@@ -276,17 +179,15 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         if (__builtin_amdgcn_inverse_ballot_w64(posm[c])) {
-            const unsigned long long key = (unsigned long long)__double_as_longlong(g[c].rho);
-            const unsigned iA = g[c].bins0 & 511u;
+            const unsigned long long key = shot_key(g[c]);
+            const unsigned iA = shot_slot_a<11>(g[c]);
             const bool up = g[c].bins1 & 2u, odd = g[c].bins1 & 1u; // (z > 0; outer shell -- iA is a SLOT number: shot_swz3)
             const unsigned long long own = sA[iA], other_shell = sA[iA ^ 1u], other_half = sA[iA ^ 2u];
             unsigned f = 0u;
             if (own == key) {
                 f = WON_A;
-                // every rho of the outer shell exceeds every rho of the inner one
-                if (odd || other_shell == 0ull) f |= WON_CD;
-                // equal distances in the two half-spaces: undefined in the reference (unstable argsort, shot.py:218); z > 0 here
-                if (key > other_half || (key == other_half && up)) f |= WON_EF;
+                if (shot_writes_cd(odd, other_shell)) f |= WON_CD;
+                if (shot_writes_ef(key, other_half, up)) f |= WON_EF;
             }
             g[c].bins1 |= f;
         }
@@ -299,8 +200,8 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
         v_ef[c] = 0.0;
         SF_K5_MARK(8, NCH);
         if (__builtin_amdgcn_inverse_ballot_w64(posm[c])) {
-            const unsigned long long key = (unsigned long long)__double_as_longlong(g[c].rho);
-            const unsigned iA = g[c].bins0 & 511u;
+            const unsigned long long key = shot_key(g[c]);
+            const unsigned iA = shot_slot_a<11>(g[c]);
             double vA, adth;
             shot_weights(g[c], K, vA, v_cd[c], v_ef[c], adth);
             SF_K5_MARK(9, NCH);
@@ -317,7 +218,7 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         if (g[c].bins1 & WON_A) {
-            const unsigned iA = g[c].bins0 & 511u;
+            const unsigned iA = shot_slot_a<11>(g[c]);
             if ((g[c].bins1 & WON_CD) && v_cd[c] != 0.0) unsafeAtomicAdd(&acc[iA ^ 1u], -v_cd[c]);
             if ((g[c].bins1 & WON_EF) && v_ef[c] != 0.0) unsafeAtomicAdd(&acc[iA ^ 2u], -v_ef[c]);
         }
@@ -331,17 +232,15 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
         SF_SHOT_SYNC();
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            if (__builtin_amdgcn_inverse_ballot_w64(posm[c])) {
-                const unsigned long long key = (unsigned long long)__double_as_longlong(g[c].rho);
-                atomicMax(&sX[(g[c].bins0 >> (stmt ? 18 : 9)) & 511u], key);
-            }
+            if (__builtin_amdgcn_inverse_ballot_w64(posm[c]))
+                atomicMax(&sX[stmt ? shot_slot_g<11>(g[c]) : shot_slot_b<11>(g[c])], shot_key(g[c]));
         }
         SF_SHOT_SYNC();
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             if (__builtin_amdgcn_inverse_ballot_w64(posm[c])) {
-                const unsigned long long key = (unsigned long long)__double_as_longlong(g[c].rho);
-                const unsigned iW = (g[c].bins0 >> (stmt ? 18 : 9)) & 511u;
+                const unsigned long long key = shot_key(g[c]);
+                const unsigned iW = stmt ? shot_slot_g<11>(g[c]) : shot_slot_b<11>(g[c]);
                 const double val = stmt ? g[c].tdot : fabs(g[c].dc); // S1's range mask is always true for cf in 0..10
                 if (atomicCAS(&sX[iW], key, SHOT_CLAIMED) == key && val != 0.0) unsafeAtomicAdd(&acc[iW], -val);
             }
@@ -366,9 +265,7 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
         ss += vals[u].x * vals[u].x;
         ss += vals[u].y * vals[u].y;
     }
-    double nrm, inv_nrm; // (the short root / inverse-root pair: ~1 ulp each, a third of sqrt() followed by a division)
-    sf_sqrt_rsqrt_uniform(sf_wave_sum(ss), nrm, inv_nrm);
-    const double nscale = nrm > 0.0 ? (normalize ? -inv_nrm : -1.0) : -0.0; // shot.py:301-305
+    const double nscale = shot_row_scale(ss, normalize, true);
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
         const int b = 2 * lane + 128 * u;
@@ -414,12 +311,7 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     shot_long_lds &L = lds_all[wave];
     int64_t q = sf_xcd_block() * SF_SHOT_LONG_WPB + wave;
-    if (SEL) {
-        if (q >= nsel) return;
-        q = (int64_t)sf_uniform(sel[q]) - view_first;
-        if (q < 0) return;
-    }
-    if (q >= m) return;
+    if (!shot_pick_keypoint(q, SEL, sel, nsel, view_first, m)) return;
     const int64_t s = offset[q];
     const int k = sf_uniform(cnt[q]);
     if (k <= lo) return; // (a list the team form of another launch holds: launch_shot)
@@ -473,27 +365,10 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
         return;
     }
     SF_SHOT_SYNC(); // (the cleared tables)
-    // one step of a sweep: 128 neighbours gathered together, their geometry
+    // one step of a sweep (shot_geometry128 with 11 bins; the list is read through the caches: it is swept three times)
     auto geometry128 = [&](int t0, shot_kept (&g)[2]) {
-        int jj[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int t = t0 + 64 * u + lane;
-            jj[u] = t < k ? idx[s + t] : -1;
-        }
-        double cx[2], cy[2], cz[2], nx[2], ny[2], nz[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            double x, y, z;
-            sf_load_pn(rec, jj[u] < 0 ? 0 : jj[u], x, y, z, nx[u], ny[u], nz[u]);
-            cx[u] = x - px; cy[u] = y - py; cz[u] = z - pz;
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            g[u].bins1 = 0u;
-            const double d2 = (cx[u] * cx[u] + cy[u] * cy[u]) + cz[u] * cz[u];
-            if (jj[u] >= 0 && d2 > 0.0) shot_geometry(cx[u], cy[u], cz[u], d2, nx[u], ny[u], nz[u], E, K.half_r, g[u]);
-        }
+        unsigned long long pos[2], over[2];
+        shot_geometry128<11, false>(rec, idx + s, t0, k, lane, px, py, pz, E, K.half_r, 11, 11.0, g, pos, over);
     };
     // ---- sweep 1: the three elections ----
     for (int t0 = 0; t0 < k; t0 += 128) {
@@ -502,10 +377,9 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
 #pragma unroll
         for (int u = 0; u < 2; ++u)
             if (g[u].bins1 >> 31) {
-                const unsigned long long key = (unsigned long long)__double_as_longlong(g[u].rho);
-                atomicMax(&L.keyA[g[u].bins0 & 511u], key);
-                atomicMax(&L.keyB[(g[u].bins0 >> 9) & 511u], key);
-                atomicMax(&L.keyG[(g[u].bins0 >> 18) & 511u], key);
+                atomicMax(&L.keyA[shot_slot_a<11>(g[u])], shot_key(g[u]));
+                atomicMax(&L.keyB[shot_slot_b<11>(g[u])], shot_key(g[u]));
+                atomicMax(&L.keyG[shot_slot_g<11>(g[u])], shot_key(g[u]));
             }
     }
     SF_SHOT_SYNC();
@@ -520,20 +394,17 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             if (g[u].bins1 >> 31) {
-                const unsigned long long key = (unsigned long long)__double_as_longlong(g[u].rho);
-                const unsigned iA = g[u].bins0 & 511u, iB = (g[u].bins0 >> 9) & 511u, iG = (g[u].bins0 >> 18) & 511u;
-                const bool up = iA & 2u, odd = iA & 1u; // (bit 1: z > 0, bit 0: outer shell)
+                const unsigned long long key = shot_key(g[u]);
+                const unsigned iA = shot_slot_a<11>(g[u]), iB = shot_slot_b<11>(g[u]), iG = shot_slot_g<11>(g[u]);
+                // (bit 1 of a slot: z > 0, bit 0: outer shell)
                 const unsigned long long own = L.keyA[iA], other_shell = L.keyA[iA ^ 1u], other_half = L.keyA[iA ^ 2u];
                 const bool winB = L.keyB[iB] == key, winG = L.keyG[iG] == key;
                 double vA, v_cd, v_ef, adth;
                 shot_weights(g[u], K, vA, v_cd, v_ef, adth);
                 if (own == key && claim(0, iA)) {
                     unsafeAtomicAdd(&L.acc[iA], vA);
-                    // S3/S4: the farthest neighbour of the cell over BOTH shells (every rho of the outer shell exceeds every
-                    // rho of the inner one); S6/S7: the farther of the two half-spaces' winners (equal distances: undefined in
-                    // the reference -- unstable argsort, shot.py:218 --, z > 0 here, as in the cached form)
-                    if ((odd || other_shell == 0ull) && v_cd != 0.0) unsafeAtomicAdd(&L.acc[iA ^ 1u], v_cd);
-                    if ((key > other_half || (key == other_half && up)) && v_ef != 0.0) unsafeAtomicAdd(&L.acc[iA ^ 2u], v_ef);
+                    if (shot_writes_cd(iA & 1u, other_shell) && v_cd != 0.0) unsafeAtomicAdd(&L.acc[iA ^ 1u], v_cd);
+                    if (shot_writes_ef(key, other_half, iA & 2u) && v_ef != 0.0) unsafeAtomicAdd(&L.acc[iA ^ 2u], v_ef);
                 }
                 const double adc = fabs(g[u].dc);
                 if (winB && claim(1, iB) && adc != 0.0) unsafeAtomicAdd(&L.acc[iB], adc);
@@ -542,6 +413,8 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
         }
     }
     SF_SHOT_SYNC();
+    // (six values held across the norm: read twice from LDS, through a loop shared with k_shot_bins, the kernel took 117
+    // registers instead of 115 -- profiles/k5_family_isa.md)
     double vals[6];
     double ss = 0.0;
 #pragma unroll
@@ -551,9 +424,7 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
         vals[u] = v;
         ss += v * v;
     }
-    double nrm, inv_nrm;
-    sf_sqrt_rsqrt(sf_wave_sum(ss), nrm, inv_nrm);
-    const double scale = nrm > 0.0 ? (normalize ? inv_nrm : 1.0) : 0.0; // shot.py:301-305
+    const double scale = shot_row_scale(ss, normalize, false);
 #pragma unroll
     for (int u = 0; u < 6; ++u) {
         const int b = lane + 64 * u;
@@ -575,12 +446,8 @@ __global__ __launch_bounds__(64 * SF_SHOT_WPB) void k_shot_cached(const double *
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     unsigned long long *const slot = slots[wave];
     int64_t q = sf_xcd_block() * SF_SHOT_WPB + wave;
-    if (sel) { // (the launch of the lists that need more chunks than the bulk: sf_dispatch::mid_sel, owner numbering)
-        if (q >= nsel) return;
-        q = (int64_t)sf_uniform(sel[q]) - view_first;
-        if (q < 0) return;
-    }
-    if (q >= m) return;
+    // (sel: the launch of the lists that need more chunks than the bulk, sf_dispatch::mid_sel)
+    if (!shot_pick_keypoint(q, sel != nullptr, sel, nsel, view_first, m)) return;
     // (a keypoint whose own list is longer than this launch's form holds belongs to the second launch: launch_shot)
     if (sf_uniform(cnt[q]) > limit) return;
     // The kernel is instantiated for the LONGEST list of the launch (a 1M-point uniform cloud at 110 neighbours on average
@@ -628,12 +495,7 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int64_t q = sf_xcd_block();
-    if (sel) {
-        if (q >= nsel) return;
-        q = (int64_t)sf_uniform(sel[q]) - view_first;
-        if (q < 0) return;
-    }
-    if (q >= m) return;
+    if (!shot_pick_keypoint(q, sel != nullptr, sel, nsel, view_first, m)) return;
     const int k = sf_uniform(cnt[q]);
     if (k <= lo || k > 64 * NCH * NW) return; // (another launch's list: launch_shot)
     const int nact = (((k + 63) >> 6) + NCH - 1) / NCH; // waves that hold a part of this list
@@ -656,44 +518,28 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
         cx[c] = cy[c] = cz[c] = nx[c] = ny[c] = nz[c] = 0.0;
         onm[c] = 0ull;
         if (first < k) { // (wave-uniform)
-            const int t = first + lane;
-            const int j = t < k ? SF_LIST_LOAD(idx + s + t) : -1;
-            double x, y, z;
-            sf_load_pn(rec, j < 0 ? 0 : j, x, y, z, nx[c], ny[c], nz[c]);
-            cx[c] = x - px;
-            cy[c] = y - py;
-            cz[c] = z - pz;
-            const int rem = k - first;
-            onm[c] = rem >= 64 ? ~0ull : (1ull << rem) - 1ull;
+            shot_gather64<true>(rec, idx + s, first + lane, k, px, py, pz, cx[c], cy[c], cz[c], nx[c], ny[c], nz[c]);
+            onm[c] = shot_chunk_mask(k - first);
         }
     }
     double raw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int xneg = 0, zneg = 0;
     if (FUSED) { // (read by every wave of the team before the barriers below, written back by one lane after them)
-        const __attribute__((address_space(4))) double *clr = (const __attribute__((address_space(4))) double *)(lrf + 9 * row);
+        // (scalar loads through the constant address space, pinned: see shot_cached_body)
+        sf_const_doubles clr = (sf_const_doubles)(lrf + 9 * row);
 #pragma unroll
         for (int i = 0; i < 9; ++i) raw[i] = clr[i];
 #pragma unroll
         for (int i = 0; i < 9; ++i) asm volatile("" : "+s"(raw[i]));
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            if (onm[c]) {
-                const double xo = sf_dot3(cx[c], cy[c], cz[c], raw[0], raw[3], raw[6]);
-                const double zo = sf_dot3(cx[c], cy[c], cz[c], raw[2], raw[5], raw[8]);
-                xneg += __popcll(__ballot(xo < 0.0) & onm[c]);
-                zneg += __popcll(__ballot(zo < 0.0) & onm[c]);
-            }
-        }
+        for (int c = 0; c < NCH; ++c)
+            if (onm[c]) shot_count_votes(cx[c], cy[c], cz[c], raw, onm[c], xneg, zneg);
     }
     double d2[NCH];
     unsigned long long posm[NCH];
     int npos = 0;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        d2[c] = (cx[c] * cx[c] + cy[c] * cy[c]) + cz[c] * cz[c];
-        posm[c] = __ballot(d2[c] > 0.0) & onm[c];
-        npos += __popcll(posm[c]);
-    }
+    for (int c = 0; c < NCH; ++c) shot_gate(cx[c], cy[c], cz[c], onm[c], d2[c], posm[c], npos);
     if (lane == 0) {
         L.red[wave][0] = npos;
         L.red[wave][1] = xneg;
@@ -728,11 +574,10 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
     for (int c = 0; c < NCH; ++c) {
         g[c].bins1 = 0u;
         if (__builtin_amdgcn_inverse_ballot_w64(posm[c])) {
-            shot_geometry(cx[c], cy[c], cz[c], d2[c], nx[c], ny[c], nz[c], E, K.half_r, g[c]);
-            const unsigned long long key = (unsigned long long)__double_as_longlong(g[c].rho);
-            atomicMax(&L.keyA[g[c].bins0 & 511u], key);
-            atomicMax(&L.keyB[(g[c].bins0 >> 9) & 511u], key);
-            atomicMax(&L.keyG[(g[c].bins0 >> 18) & 511u], key);
+            shot_geometry<11>(cx[c], cy[c], cz[c], d2[c], nx[c], ny[c], nz[c], E, K.half_r, 11, 11.0, g[c]);
+            atomicMax(&L.keyA[shot_slot_a<11>(g[c])], shot_key(g[c]));
+            atomicMax(&L.keyB[shot_slot_b<11>(g[c])], shot_key(g[c]));
+            atomicMax(&L.keyG[shot_slot_g<11>(g[c])], shot_key(g[c]));
         }
     }
     __syncthreads();
@@ -740,18 +585,18 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         if (__builtin_amdgcn_inverse_ballot_w64(posm[c])) {
-            const unsigned long long key = (unsigned long long)__double_as_longlong(g[c].rho);
-            const unsigned iA = g[c].bins0 & 511u;
-            const bool up = iA & 2u, odd = iA & 1u; // (bit 1: z > 0, bit 0: outer shell)
+            const unsigned long long key = shot_key(g[c]);
+            const unsigned iA = shot_slot_a<11>(g[c]);
+            const bool up = iA & 2u, odd = iA & 1u; // (bit 1 of a slot: z > 0, bit 0: outer shell)
             const unsigned long long own = L.keyA[iA], other_shell = L.keyA[iA ^ 1u], other_half = L.keyA[iA ^ 2u];
             unsigned f = 0u;
             if (own == key) {
                 f = WON_A;
-                if (odd || other_shell == 0ull) f |= WON_CD; // (as in the cached form: shot_cached_body)
-                if (key > other_half || (key == other_half && up)) f |= WON_EF;
+                if (shot_writes_cd(odd, other_shell)) f |= WON_CD;
+                if (shot_writes_ef(key, other_half, up)) f |= WON_EF;
             }
-            if (L.keyB[(g[c].bins0 >> 9) & 511u] == key) f |= WON_B;
-            if (L.keyG[(g[c].bins0 >> 18) & 511u] == key) f |= WON_G;
+            if (L.keyB[shot_slot_b<11>(g[c])] == key) f |= WON_B;
+            if (L.keyG[shot_slot_g<11>(g[c])] == key) f |= WON_G;
             g[c].bins1 |= f;
         }
     }
@@ -760,8 +605,8 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         if (__builtin_amdgcn_inverse_ballot_w64(posm[c])) {
-            const unsigned long long key = (unsigned long long)__double_as_longlong(g[c].rho);
-            const unsigned iA = g[c].bins0 & 511u;
+            const unsigned long long key = shot_key(g[c]);
+            const unsigned iA = shot_slot_a<11>(g[c]);
             double vA, v_cd, v_ef, adth;
             shot_weights(g[c], K, vA, v_cd, v_ef, adth);
             const unsigned f = g[c].bins1;
@@ -771,8 +616,8 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
                 if ((f & WON_CD) && v_cd != 0.0) unsafeAtomicAdd(&L.vx[iA ^ 1u], v_cd);
                 if ((f & WON_EF) && v_ef != 0.0) unsafeAtomicAdd(&L.vx[iA ^ 2u], v_ef);
             }
-            if (f & WON_B) atomicCAS(&L.keyB[(g[c].bins0 >> 9) & 511u], key, tag_value(fabs(g[c].dc)));
-            if (f & WON_G) atomicCAS(&L.keyG[(g[c].bins0 >> 18) & 511u], key, tag_value(adth));
+            if (f & WON_B) atomicCAS(&L.keyB[shot_slot_b<11>(g[c])], key, tag_value(fabs(g[c].dc)));
+            if (f & WON_G) atomicCAS(&L.keyG[shot_slot_g<11>(g[c])], key, tag_value(adth));
         }
     }
     __syncthreads();
@@ -797,9 +642,7 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
         ss += vals[u].x * vals[u].x;
         ss += vals[u].y * vals[u].y;
     }
-    double nrm, inv_nrm;
-    sf_sqrt_rsqrt_uniform(sf_wave_sum(ss), nrm, inv_nrm);
-    const double scale = nrm > 0.0 ? (normalize ? inv_nrm : 1.0) : 0.0; // shot.py:301-305
+    const double scale = shot_row_scale(ss, normalize, false);
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
         const int b = 2 * lane + 128 * u;
@@ -809,63 +652,59 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
 
 } // namespace
 
-// launch K5 on resident buffers; fused != 0: dlrf holds raw axes (k_shot_lrf raw mode) and receives the frames.
+// launch K5 on resident buffers; FUSED: dlrf holds raw axes (k_shot_lrf raw mode) and receives the frames.
 // Dispatch by list length, per keypoint (sf_nbrs_dispatch): the register-cached form of the main launch leaves out the
-// keypoints whose own list exceeds it, and the streaming form serves exactly those in a second launch.
-static int launch_shot(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double *dlrf, int normalize, int64_t min_nb, double *dout,
-                       bool fused)
+// keypoints whose own list exceeds it, and the team and streaming forms serve exactly those in launches of their own.
+template <bool FUSED>
+static int launch_shot_as(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double *dlrf, int normalize, int64_t min_nb_, double *dout)
 {
     const int64_t m = nb->m;
     if (!m) return SF_OK;
-    // (a list holds fewer than 2^31 points: clamped here, "more than min_nb neighbours" is a 32-bit comparison in the kernels)
-    min_nb = std::min<int64_t>(std::max<int64_t>(min_nb, -1), 2147483647LL);
-    const dim3 grid(sf_xcd_grid(sf_div_up(m, SF_SHOT_WPB))), block(64 * SF_SHOT_WPB), block_streaming(64 * SF_SHOT_LONG_WPB);
-#define SF_SHOT_ARGS c->rec, nb->qx, nb->qy, nb->qz, nb->offset, nb->count, nb->idx, nb->qrow, m
-    const double r_ = nb->radius;
-    if (!ctx->shot_coef) { // (once per context)
-        SF_HIP(hipMalloc(&ctx->shot_coef, sizeof(SF_SHOT_COEF)));
-        SF_HIP(hipMemcpy(ctx->shot_coef, SF_SHOT_COEF, sizeof(SF_SHOT_COEF), hipMemcpyHostToDevice));
-    }
-    const shot_consts K{r_, r_ / 2, r_ / 4, r_ * 3 / 4, 1.0 / (r_ / 2), ctx->shot_coef}; // the reference's own expressions (shot.py:95-117, 235)
+    shot_consts K;
+    int nmin;
+    SF_CHECK(sf_shot_consts(ctx, nb->radius, min_nb_, &K, &nmin));
+    const int64_t min_nb = nmin;
     const sf_dispatch d = sf_nbrs_dispatch(nb);
-#define SF_SHOT_CASE(N)                                                                                              \
-    if (fused) { SF_LAUNCH(ctx, "k5_shot", (k_shot_cached<N, true>), grid, block, SF_SHOT_ARGS, K, dlrf, normalize, min_nb, dout, d.limit, (const int32_t *)nullptr, (int64_t)0, (int64_t)0); } \
-    else { SF_LAUNCH(ctx, "k5_shot", (k_shot_cached<N, false>), grid, block, SF_SHOT_ARGS, K, dlrf, normalize, min_nb, dout, d.limit, (const int32_t *)nullptr, (int64_t)0, (int64_t)0); }
-#define SF_SHOT_STREAM(NAME, SEL, GRID, SELP, NSEL, LO)                                                               \
-    if (fused) { SF_LAUNCH(ctx, NAME, (k_shot_long<true, SEL>), dim3(sf_xcd_grid(sf_div_up(GRID, SF_SHOT_LONG_WPB))), block_streaming, SF_SHOT_ARGS, K, dlrf, normalize, min_nb, dout, SELP, NSEL, d.view_first, LO); } \
-    else { SF_LAUNCH(ctx, NAME, (k_shot_long<false, SEL>), dim3(sf_xcd_grid(sf_div_up(GRID, SF_SHOT_LONG_WPB))), block_streaming, SF_SHOT_ARGS, K, dlrf, normalize, min_nb, dout, SELP, NSEL, d.view_first, LO); }
-    // the team form (k_shot_team): one workgroup of NW waves per selected keypoint, lists of 256 .. 64 NCH NW points
-#define SF_SHOT_TEAM(NCH, NW)                                                                                         \
-    if (fused) { SF_LAUNCH(ctx, "k5_shot_tail", (k_shot_team<NCH, NW, true>), dim3(sf_xcd_grid(d.n_tail)), dim3(64 * NW), SF_SHOT_ARGS, K, dlrf, normalize, min_nb, dout, d.tail_sel, d.n_tail, d.view_first, 255); } \
-    else { SF_LAUNCH(ctx, "k5_shot_tail", (k_shot_team<NCH, NW, false>), dim3(sf_xcd_grid(d.n_tail)), dim3(64 * NW), SF_SHOT_ARGS, K, dlrf, normalize, min_nb, dout, d.tail_sel, d.n_tail, d.view_first, 255); }
-    if (d.chunks == 1) { SF_SHOT_CASE(1) }
-    else if (d.chunks == 2) { SF_SHOT_CASE(2) }
-    else if (d.chunks == 3) { SF_SHOT_CASE(3) }
-    else if (d.chunks == 4) { SF_SHOT_CASE(4) }
-    else { SF_SHOT_STREAM("k5_shot", false, m, (const int32_t *)nullptr, (int64_t)0, 0) }
-    if (d.n_mid) { // the few lists that need more chunks than the bulk: the same form, four chunks
-        const dim3 grid_mid(sf_xcd_grid(sf_div_up(d.n_mid, SF_SHOT_WPB)));
-        if (fused) { SF_LAUNCH(ctx, "k5_shot_mid", (k_shot_cached<4, true>), grid_mid, block, SF_SHOT_ARGS, K, dlrf, normalize, min_nb, dout, 255, d.mid_sel, d.n_mid, d.view_first); }
-        else { SF_LAUNCH(ctx, "k5_shot_mid", (k_shot_cached<4, false>), grid_mid, block, SF_SHOT_ARGS, K, dlrf, normalize, min_nb, dout, 255, d.mid_sel, d.n_mid, d.view_first); }
-    }
+    const int32_t *const none = nullptr;
+    const dim3 block(64 * SF_SHOT_WPB), block_streaming(64 * SF_SHOT_LONG_WPB);
+#define SF_SHOT_ARGS c->rec, nb->qx, nb->qy, nb->qz, nb->offset, nb->count, nb->idx, nb->qrow, m, K, dlrf, normalize, min_nb, dout
+    // the cached form over all m (sel = none) or over a selection; the streaming form likewise; the team of NW waves
+#define SF_SHOT_CACHED(NAME, N, COUNT, LIMIT, SELP)                                                                  \
+    SF_LAUNCH(ctx, NAME, (k_shot_cached<N, FUSED>), dim3(sf_xcd_grid(sf_div_up(COUNT, SF_SHOT_WPB))), block, SF_SHOT_ARGS, LIMIT, SELP, (int64_t)(COUNT), d.view_first)
+#define SF_SHOT_STREAM(NAME, SEL, COUNT, SELP, LO)                                                                    \
+    SF_LAUNCH(ctx, NAME, (k_shot_long<FUSED, SEL>), dim3(sf_xcd_grid(sf_div_up(COUNT, SF_SHOT_LONG_WPB))), block_streaming, SF_SHOT_ARGS, SELP, (int64_t)(COUNT), d.view_first, LO)
+#define SF_SHOT_TEAM(NW)                                                                                              \
+    SF_LAUNCH(ctx, "k5_shot_tail", (k_shot_team<SF_TEAM_NCH, NW, FUSED>), dim3(sf_xcd_grid(d.n_tail)), dim3(64 * NW), SF_SHOT_ARGS, d.tail_sel, d.n_tail, d.view_first, 255)
+    if (d.chunks == 1) { SF_SHOT_CACHED("k5_shot", 1, m, d.limit, none); }
+    else if (d.chunks == 2) { SF_SHOT_CACHED("k5_shot", 2, m, d.limit, none); }
+    else if (d.chunks == 3) { SF_SHOT_CACHED("k5_shot", 3, m, d.limit, none); }
+    else if (d.chunks == 4) { SF_SHOT_CACHED("k5_shot", 4, m, d.limit, none); }
+    else { SF_SHOT_STREAM("k5_shot", false, m, none, 0); }
+    // the few lists that need more chunks than the bulk: the same form, four chunks
+    if (d.n_mid) { SF_SHOT_CACHED("k5_shot_mid", 4, d.n_mid, 255, d.mid_sel); }
     if (d.n_tail) {
         // Lists above 255 points: a team of waves per keypoint while the list fits the team's registers (the longest list of
         // the search decides which team sizes are launched at all; every launch walks the selection and takes its own lengths),
         // the streaming form beyond.  Team size: the smallest that holds the longest list of the search (a shorter list uses as many
         // of the team's waves as it needs).
         const int64_t longest = nb->max_count > 255 ? nb->max_count : INT64_MAX; // (unknown: every form is launched)
-        constexpr int TN = SF_TEAM_NCH; // chunks a wave of the team holds
         int64_t covered;
-        if (longest <= 64 * TN * 4) { SF_SHOT_TEAM(TN, 4) covered = 64 * TN * 4; }
-        else if (longest <= 64 * TN * 8) { SF_SHOT_TEAM(TN, 8) covered = 64 * TN * 8; }
-        else { SF_SHOT_TEAM(TN, 16) covered = 64 * TN * 16; }
-        if (longest > covered) { SF_SHOT_STREAM("k5_shot_tail_stream", true, d.n_tail, d.tail_sel, d.n_tail, (int)covered) }
+        if (longest <= 64 * SF_TEAM_NCH * 4) { SF_SHOT_TEAM(4); covered = 64 * SF_TEAM_NCH * 4; }
+        else if (longest <= 64 * SF_TEAM_NCH * 8) { SF_SHOT_TEAM(8); covered = 64 * SF_TEAM_NCH * 8; }
+        else { SF_SHOT_TEAM(16); covered = 64 * SF_TEAM_NCH * 16; }
+        if (longest > covered) { SF_SHOT_STREAM("k5_shot_tail_stream", true, d.n_tail, d.tail_sel, (int)covered); }
     }
 #undef SF_SHOT_TEAM
 #undef SF_SHOT_STREAM
-#undef SF_SHOT_CASE
+#undef SF_SHOT_CACHED
 #undef SF_SHOT_ARGS
     return SF_OK;
+}
+
+static int launch_shot(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double *dlrf, int normalize, int64_t min_nb, double *dout, bool fused)
+{
+    return fused ? launch_shot_as<true>(ctx, c, nb, dlrf, normalize, min_nb, dout)
+                 : launch_shot_as<false>(ctx, c, nb, dlrf, normalize, min_nb, dout);
 }
 
 extern "C" int sf_shot(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const double *lrf, int normalize, int64_t min_nb,
@@ -912,25 +751,22 @@ extern "C" int sf_shot_serial(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int64_t min
     SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, c));
     const int64_t m = nb->m;
     sf_pool_guard guard(ctx);
-    double *dlrf = nullptr, *dout = out;
+    double *dlrf = nullptr, *dout;
     SF_CHECK(guard.alloc(&dlrf, (size_t)m * 9));
-    if (!(flags & SF_OUT_DEVICE)) SF_CHECK(guard.alloc(&dout, (size_t)m * SF_SHOT_LEN));
+    SF_CHECK(stage_out(guard, out, (size_t)m * SF_SHOT_LEN, flags, &dout));
     SF_CHECK(sf_launch_shot_lrf(ctx, c, nb, 0, 1, dlrf));
     SF_CHECK(launch_shot(ctx, c, nb, dlrf, 1, min_nb, dout, false));
-    if (dout != out) {
-        if (m) SF_HIP(hipMemcpyAsync(out, dout, (size_t)m * SF_SHOT_LEN * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        SF_HIP(hipStreamSynchronize(ctx->stream));
-    }
+    SF_CHECK(finish_out(ctx, out, (size_t)m * SF_SHOT_LEN, flags, dout));
+    if (!(flags & SF_OUT_DEVICE)) SF_HIP(hipStreamSynchronize(ctx->stream));
     return SF_OK;
 }
 
-// Single-scale SHOT in one go (shot_parallelization.py:135-183: frames and descriptor from the SAME search):
-// K4 without its vote sweep, then the fused K5, which votes on the neighbours it gathers anyway.
-extern "C" int sf_shot_single_scale(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int normalize, int64_t min_nb, double *lrf,
-                                    double *out, int flags)
+// Frames by `frames(dlrf)` (raw axes), then the fused K5, which votes on the neighbours it gathers anyway (the streaming K5
+// votes too: no list is too long for the fused path).  lrf: where the frames go, or null.
+template <class F>
+static int shot_fused(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, F frames, int normalize, int64_t min_nb, double *lrf, double *out,
+                      int flags)
 {
-    SF_CHECK(check_nbrs(ctx, c, nb, "sf_shot_single_scale"));
-    if (!out) { sf_set_error("sf_shot_single_scale: null out"); return SF_ERR_ARG; }
     SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, c));
     const int64_t m = nb->m;
     const bool out_dev = flags & SF_OUT_DEVICE;
@@ -941,13 +777,22 @@ extern "C" int sf_shot_single_scale(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int n
         dlrf = own_lrf;
     }
     SF_CHECK(stage_out(tmp, out, (size_t)m * SF_SHOT_LEN, flags, &dout));
-    const bool fused = true; // (the streaming K5 votes too: no list is too long for the fused path)
-    SF_CHECK(sf_launch_shot_lrf(ctx, c, nb, fused ? 1 : 0, 0, dlrf));
-    SF_CHECK(launch_shot(ctx, c, nb, dlrf, normalize, min_nb, dout, fused));
+    SF_CHECK(frames(dlrf));
+    SF_CHECK(launch_shot(ctx, c, nb, dlrf, normalize, min_nb, dout, true));
     if (own_lrf && lrf && m) SF_HIP(hipMemcpyAsync(lrf, own_lrf, (size_t)m * 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SF_CHECK(finish_out(ctx, out, (size_t)m * SF_SHOT_LEN, flags, dout));
     if (!out_dev) SF_HIP(hipStreamSynchronize(ctx->stream));
     return SF_OK;
+}
+
+// Single-scale SHOT in one go (shot_parallelization.py:135-183: frames and descriptor from the SAME search):
+// K4 without its vote sweep, then the fused K5.
+extern "C" int sf_shot_single_scale(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int normalize, int64_t min_nb, double *lrf,
+                                    double *out, int flags)
+{
+    SF_CHECK(check_nbrs(ctx, c, nb, "sf_shot_single_scale"));
+    if (!out) { sf_set_error("sf_shot_single_scale: null out"); return SF_ERR_ARG; }
+    return shot_fused(ctx, c, nb, [&](double *dlrf) { return sf_launch_shot_lrf(ctx, c, nb, 1, 0, dlrf); }, normalize, min_nb, lrf, out, flags);
 }
 
 // sf_shot_single_scale with the frame moments already computed by sf_spfh_compute_moments on the SAME lists (self
@@ -961,22 +806,7 @@ extern "C" int sf_shot_from_moments(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const
         sf_set_error("sf_shot_from_moments: needs a self search");
         return SF_ERR_UNSUPPORTED;
     }
-    SF_CHECK(sf_cloud_ensure_sorted_normals(ctx, c));
-    const int64_t m = nb->m;
-    const bool out_dev = flags & SF_OUT_DEVICE;
-    sf_pool_guard tmp(ctx);
-    double *dlrf = lrf, *own_lrf = nullptr, *dout;
-    if (!out_dev || !lrf) {
-        SF_CHECK(tmp.alloc(&own_lrf, (size_t)m * 9));
-        dlrf = own_lrf;
-    }
-    SF_CHECK(stage_out(tmp, out, (size_t)m * SF_SHOT_LEN, flags, &dout));
-    SF_CHECK(sf_launch_lrf_from_cov(ctx, cov_dev, m, dlrf));
-    SF_CHECK(launch_shot(ctx, c, nb, dlrf, normalize, min_nb, dout, true));
-    if (own_lrf && lrf && m) SF_HIP(hipMemcpyAsync(lrf, own_lrf, (size_t)m * 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SF_CHECK(finish_out(ctx, out, (size_t)m * SF_SHOT_LEN, flags, dout));
-    if (!out_dev) SF_HIP(hipStreamSynchronize(ctx->stream));
-    return SF_OK;
+    return shot_fused(ctx, c, nb, [&](double *dlrf) { return sf_launch_lrf_from_cov(ctx, cov_dev, nb->m, dlrf); }, normalize, min_nb, lrf, out, flags);
 }
 
 extern "C" int sf_shot_from_raw_lrf(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double *lrf_dev, int normalize, int64_t min_nb,

@@ -22,69 +22,9 @@
 #include "shot_core.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-int sf_launch_shot_lrf(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int raw, int skip_zero, double *dlrf); // normals_lrf.hip
-
 namespace {
 
 constexpr unsigned long long SHOT_BINS_SIGN = 0x8000000000000000ull;
-
-// The geometry of one neighbour for n cosine bins: shot_geometry (shot.hip) with the bin count a runtime value.  Bins of up to
-// 2 048-slot rows do not fit its 9-bit fields: bins0 = base | bcos << 16, bins1 = valid << 31 | bth << 2 | (base & 3) (bits 0-1,
-// shell and half-space, as shot_weights reads them).  Returns false for a neighbour whose cosine bin is n (a clipped cosine of
-// exactly +1 with n even: rint(n - 0.5) = n, the reference's IndexError), which then takes part in nothing.
-__device__ inline bool shot_bins_geometry(double cx, double cy, double cz, double d2, double nx, double ny, double nz,
-                                          const double *E, double half_r, int n, double nd, shot_kept &o)
-{
-    double rho, inv_rho;
-    sf_sqrt_rsqrt(d2, rho, inv_rho);
-    const double lx = sf_dot3(cx, cy, cz, E[0], E[3], E[6]);
-    const double ly = sf_dot3(cx, cy, cz, E[1], E[4], E[7]);
-    const double lz = sf_dot3(cx, cy, cz, E[2], E[5], E[8]);
-    double cosine = sf_dot3(nx, ny, nz, E[2], E[5], E[8]);
-    cosine = fmin(fmax(cosine, -1.0), 1.0);
-    // bin_dist = (cosine + 1.0) * n / 2.0 - 0.5 in that order, unfused (shot.py:386); rint rounds half to even (:387)
-    const double cpos = (cosine + 1.0) * nd / 2.0 - 0.5;
-    const double cf = rint(cpos);
-    const int ci = (int)cf; // 0 .. n (-0.5 rounds to -0)
-    if (ci >= n) return false;
-    const int ti = azimuth_octant_wave(lx, ly);
-    const int pi_ = lz > 0.0 ? 1 : 0;
-    const int ri = rho > half_r ? 1 : 0;
-    const double dc = cpos - cf;
-    const int sc = (dc > 0.0) - (dc < 0.0);
-    int cin = ci + sc; // -1 .. n, wrapped as the reference's % n does (shot.py:401): n = 1 wraps onto itself
-    cin = cin < 0 ? n - 1 : (cin >= n ? 0 : cin);
-    // the azimuth neighbour: the side of the octant's centre ray (shot_geometry has the derivation)
-    const double C8 = 0.9238795325112867, S8 = 0.3826834323650898; // cos, sin of pi/8
-    const double am = fmax(fabs(lx), fabs(ly)), bm = fmin(fabs(lx), fabs(ly));
-    const double crs = __builtin_fma(C8, bm, -(S8 * am));
-    const double dot = __builtin_fma(C8, am, S8 * bm);
-    const double cross = (ti & 1) ? -crs : crs;
-    int sth;
-    if (fabs(cross) > 1e-9 * (fabs(lx) + fabs(ly))) {
-        sth = cross > 0.0 ? 1 : -1;
-    } else { // on (or within rounding of) the centre ray, or lx = ly = 0: the reference's expression decides
-        const double tsz = 2 * SHOT_PI / 8;
-        double dth = (atan2(ly, lx) - (-SHOT_PI + ti * tsz)) / tsz - 0.5;
-        dth = fmin(fmax(dth, -0.5), 0.5);
-        sth = (dth > 0.0) - (dth < 0.0);
-    }
-    const int tin = (ti + sth) & 7;
-    const unsigned base = (unsigned)(((ci * 8 + ti) * 2 + pi_) * 2 + ri);
-    const unsigned bcos = (unsigned)(((cin * 8 + ti) * 2 + pi_) * 2 + ri);
-    const unsigned bth = (unsigned)(((ci * 8 + tin) * 2 + pi_) * 2 + ri);
-    // lz / rho with one residual correction (see shot_geometry: acos is steep at +-1)
-    double lzr = lz * inv_rho;
-    lzr = __builtin_fma(__builtin_fma(-lzr, rho, lz), inv_rho, lzr);
-    o.rho = rho; o.dc = dc; o.tcross = cross; o.tdot = dot; o.lzr = lzr;
-    o.bins0 = base | (bcos << 16);
-    o.bins1 = 0x80000000u | (bth << 2) | (base & 3u);
-    return true;
-}
-
-__device__ inline unsigned shot_bins_a(const shot_kept &g) { return g.bins0 & 0xffffu; }
-__device__ inline unsigned shot_bins_b(const shot_kept &g) { return g.bins0 >> 16; }
-__device__ inline unsigned shot_bins_g(const shot_kept &g) { return (g.bins1 >> 2) & 0xfffu; }
 
 // One wave per keypoint, blockDim.x / 64 waves per workgroup, each with its own 4 x 32 n slots of the dynamic LDS.
 // lrf: finished frames (K4 with skip_zero); err: set to 1 (a plain store) when a keypoint that passes the gate has a neighbour
@@ -119,32 +59,9 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
     for (int i = 0; i < 9; ++i) E[i] = lrf[9 * row + i];
     SF_SHOT_SYNC(); // (the cleared tables)
 
-    // one step of a sweep: 128 neighbours gathered together, their geometry; bins1 bit 31 marks a neighbour at non-zero
-    // distance whose bins are in range, `over` the ones at non-zero distance in cosine bin n
+    // one step of a sweep (shot_geometry128 with the bin count a run-time value)
     auto geometry128 = [&](int t0, shot_kept (&g)[2], unsigned long long (&pos)[2], unsigned long long (&over)[2]) {
-        int jj[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int t = t0 + 64 * u + lane;
-            jj[u] = t < k ? SF_LIST_LOAD(idx + s + t) : -1;
-        }
-        double cx[2], cy[2], cz[2], nx[2], ny[2], nz[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            double x, y, z;
-            sf_load_pn(rec, jj[u] < 0 ? 0 : jj[u], x, y, z, nx[u], ny[u], nz[u]);
-            cx[u] = x - px; cy[u] = y - py; cz[u] = z - pz;
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            g[u].bins1 = 0u;
-            const double d2 = (cx[u] * cx[u] + cy[u] * cy[u]) + cz[u] * cz[u];
-            const bool on = jj[u] >= 0 && d2 > 0.0;
-            bool bad = false;
-            if (on) bad = !shot_bins_geometry(cx[u], cy[u], cz[u], d2, nx[u], ny[u], nz[u], E, K.half_r, n, nd, g[u]);
-            pos[u] = __ballot(on);
-            over[u] = __ballot(bad);
-        }
+        shot_geometry128<0, true>(rec, idx + s, t0, k, lane, px, py, pz, E, K.half_r, n, nd, g, pos, over);
     };
 
     // ---- sweep 1: the three elections, the gate count (shot.py:360) ----
@@ -159,10 +76,9 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
             npos += __popcll(pos[u]);
             any_over |= over[u] != 0ull;
             if (g[u].bins1 >> 31) {
-                const unsigned long long key = (unsigned long long)__double_as_longlong(g[u].rho);
-                atomicMax(&keyA[shot_bins_a(g[u])], key);
-                atomicMax(&keyB[shot_bins_b(g[u])], key);
-                atomicMax(&keyG[shot_bins_g(g[u])], key);
+                atomicMax(&keyA[shot_slot_a<0>(g[u])], shot_key(g[u]));
+                atomicMax(&keyB[shot_slot_b<0>(g[u])], shot_key(g[u]));
+                atomicMax(&keyG[shot_slot_g<0>(g[u])], shot_key(g[u]));
             }
         }
     }
@@ -181,20 +97,18 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             if (g[u].bins1 >> 31) {
-                const unsigned long long key = (unsigned long long)__double_as_longlong(g[u].rho);
-                const unsigned iA = shot_bins_a(g[u]);
-                const bool up = iA & 2u, odd = iA & 1u; // (bit 1: z > 0, bit 0: outer shell)
+                const unsigned long long key = shot_key(g[u]);
+                const unsigned iA = shot_slot_a<0>(g[u]);
+                // (bit 1 of a slot: z > 0, bit 0: outer shell; the other half-space's key may be claimed already: its sign bit off)
                 const unsigned long long own = keyA[iA], other_shell = keyA[iA ^ 1u], other_half = keyA[iA ^ 2u] & ~SHOT_BINS_SIGN;
                 double vA, v_cd, v_ef, adth;
                 shot_weights(g[u], K, vA, v_cd, v_ef, adth);
                 if (own == key && atomicCAS(&keyA[iA], key, key | SHOT_BINS_SIGN) == key) {
-                    // S3/S4: the farthest neighbour of the cell over BOTH shells; S6/S7: the farther of the two half-spaces'
-                    // winners (equal distances: z > 0, as in every K5 form)
-                    if ((odd || other_shell == 0ull) && v_cd != 0.0) unsafeAtomicAdd(&vx[iA ^ 1u], v_cd);
-                    if ((key > other_half || (key == other_half && up)) && v_ef != 0.0) unsafeAtomicAdd(&vx[iA ^ 2u], v_ef);
+                    if (shot_writes_cd(iA & 1u, other_shell) && v_cd != 0.0) unsafeAtomicAdd(&vx[iA ^ 1u], v_cd);
+                    if (shot_writes_ef(key, other_half, iA & 2u) && v_ef != 0.0) unsafeAtomicAdd(&vx[iA ^ 2u], v_ef);
                 }
-                atomicCAS(&keyB[shot_bins_b(g[u])], key, tag_value(fabs(g[u].dc)));
-                atomicCAS(&keyG[shot_bins_g(g[u])], key, tag_value(adth));
+                atomicCAS(&keyB[shot_slot_b<0>(g[u])], key, tag_value(fabs(g[u].dc)));
+                atomicCAS(&keyG[shot_slot_g<0>(g[u])], key, tag_value(adth));
             }
         }
     }
@@ -208,8 +122,8 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             if (g[u].bins1 >> 31) {
-                const unsigned long long claimed = (unsigned long long)__double_as_longlong(g[u].rho) | SHOT_BINS_SIGN;
-                const unsigned iA = shot_bins_a(g[u]);
+                const unsigned long long claimed = shot_key(g[u]) | SHOT_BINS_SIGN;
+                const unsigned iA = shot_slot_a<0>(g[u]);
                 if (keyA[iA] == claimed) {
                     double vA, v_cd, v_ef, adth;
                     shot_weights(g[u], K, vA, v_cd, v_ef, adth);
@@ -226,9 +140,7 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
         const double v = ((shot_untag(keyA[b]) + vx[b]) + shot_untag(keyB[b])) + shot_untag(keyG[b]);
         ss += v * v;
     }
-    double nrm, inv_nrm;
-    sf_sqrt_rsqrt_uniform(sf_wave_sum(ss), nrm, inv_nrm);
-    const double scale = nrm > 0.0 ? inv_nrm : 0.0;
+    const double scale = shot_row_scale(ss, 1, false);
     for (int b = lane; b < S; b += 64) {
         const double v = ((shot_untag(keyA[b]) + vx[b]) + shot_untag(keyB[b])) + shot_untag(keyG[b]);
         sf_store_stream(o + b, v * scale);
@@ -255,21 +167,17 @@ extern "C" int sf_shot_serial_bins(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int64_
     const int64_t m = nb->m;
     const size_t row = (size_t)32 * n;
     sf_pool_guard guard(ctx);
-    double *dlrf = nullptr, *dout = out;
+    double *dlrf = nullptr, *dout;
     int *derr = nullptr;
     SF_CHECK(guard.alloc(&dlrf, (size_t)m * 9));
     SF_CHECK(guard.alloc(&derr, 1));
-    if (!(flags & SF_OUT_DEVICE)) SF_CHECK(guard.alloc(&dout, (size_t)m * row));
+    SF_CHECK(stage_out(guard, out, (size_t)m * row, flags, &dout));
     SF_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx->stream));
     SF_CHECK(sf_launch_shot_lrf(ctx, c, nb, 0, 1, dlrf));
-    if (!ctx->shot_coef) { // (once per context; K5 shares it)
-        SF_HIP(hipMalloc(&ctx->shot_coef, sizeof(SF_SHOT_COEF)));
-        SF_HIP(hipMemcpy(ctx->shot_coef, SF_SHOT_COEF, sizeof(SF_SHOT_COEF), hipMemcpyHostToDevice));
-    }
+    shot_consts K;
+    int nmin;
+    SF_CHECK(sf_shot_consts(ctx, nb->radius, min_nb, &K, &nmin)); // (the coefficients: once per context; K5 shares them)
     if (m) {
-        const double r_ = nb->radius;
-        const shot_consts K{r_, r_ / 2, r_ / 4, r_ * 3 / 4, 1.0 / (r_ / 2), ctx->shot_coef}; // as launch_shot (shot.py:95-117, 235)
-        const int nmin = (int)std::min<int64_t>(std::max<int64_t>(min_nb, -1), 2147483647LL);
         const int w = shot_bins_waves(n);
         const size_t lds = (size_t)w * 4 * row * sizeof(unsigned long long);
         sf_launch_timer t_(ctx, "k5_shot_bins");
@@ -277,7 +185,7 @@ extern "C" int sf_shot_serial_bins(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int64_
                            nb->qz, nb->offset, nb->count, nb->idx, nb->qrow, m, K, (const double *)dlrf, n, nmin, dout, derr);
         SF_HIP(hipGetLastError());
     }
-    if (dout != out && m) SF_HIP(hipMemcpyAsync(out, dout, (size_t)m * row * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SF_CHECK(finish_out(ctx, out, (size_t)m * row, flags, dout));
     int herr = 0;
     SF_HIP(hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));

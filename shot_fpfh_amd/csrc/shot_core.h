@@ -1,10 +1,15 @@
-// shot_core.h -- the device helpers of the SHOT kernels that do not depend on the number of cosine bins: the azimuth
-// octant, the root / inverse-root pair, the atan / acos polynomials and their coefficient table, the interpolation weights
-// of one neighbour, the slot tagging of the election tables.  Shared by K5 (shot.hip: 11 cosine bins, the tuned forms) and
-// the serial SHOT with any number of cosine bins (shot_bins.hip).
+// shot_core.h -- what the SHOT kernels share, one definition each: the azimuth octant, the root / inverse-root pair, the atan /
+// acos polynomials and their coefficient table, the geometry and the interpolation weights of one neighbour, the slots of the
+// election tables and their tagging, the rule for who writes what, the gather of a chunk, the prologue of the register-held
+// forms, the keypoint pick, the row epilogue, and the constants a launch is given.  Shared by K5 (shot.hip: 11 cosine bins, the
+// tuned forms) and the serial SHOT with any number of cosine bins (shot_bins.hip).
 #pragma once
 #include "common.h"
 #include "device_util.h"
+
+// K4's launches (normals_lrf.hip): raw != 0 leaves the raw axes for a fused K5; skip_zero: frames of the serial variant
+int sf_launch_shot_lrf(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int raw, int skip_zero, double *dlrf);
+int sf_launch_lrf_from_cov(sf_ctx *ctx, const double *cov_dev, int64_t m, double *dlrf);
 
 namespace {
 
@@ -41,20 +46,11 @@ __device__ inline double sf_dot3(double a0, double a1, double a2, double b0, dou
     return __builtin_fma(a2, b2, __builtin_fma(a1, b1, a0 * b0));
 }
 
-// --------------------------------------------------------------------------------------------------
-// K5, register-cached form for neighbourhoods of at most 64*NCH points (the common case; the streaming
-// kernel above stays as the fallback for larger ones).  The neighbour coordinates are gathered ONCE,
-// all NCH chunks in flight together; sweep 1 does the geometry (local coordinates, bins, rho) and keeps
-// the five numbers sweep 2 needs per neighbour in VGPRs, so sweep 2 is only the transcendental /
-// interpolation part.  The azimuth-neighbour decision in sweep 1 uses the sign of the cross product with
-// the octant's centre direction (no atan2); when that is not clearly non-zero it falls back to the
-// reference's own expression, so the decision equals shot.py:283-288 in every case.
-// --------------------------------------------------------------------------------------------------
 // sqrt(x) and 1/sqrt(x) together.  The root is ocml's own f64 sequence (v_rsq_f64 and three coupled Newton steps)
 // minus its exponent pre/post-scaling, which only matters outside [1e-290, 1e290]: bit-identical to sqrt() there
 // (tools/ubench/sqrt_check.hip: 0 differences in 1.6e7 inputs), 10 instructions instead of 22; the half-inverse
 // the iteration carries along, refined once more, is 1/sqrt(x) to ~1 ulp for two more instructions.
-__device__ inline void sf_sqrt_rsqrt(double x, double &root, double &inv)
+__device__ inline void sf_sqrt_rsqrt_newton(double x, double &root, double &inv)
 {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = 0.5 * y;
@@ -69,10 +65,15 @@ __device__ inline void sf_sqrt_rsqrt(double x, double &root, double &inv)
     h = __builtin_fma(h, r, h);
     root = g;
     inv = h + h;
-    // (wave-uniform, never taken for real clouds; the test is on the exponent -- 2^-964 <= x < 2^963, i.e. 4.6e-291 .. 7.8e289,
-    // positive, finite, not NaN -- one integer subtraction and comparison with 32-bit literals instead of two comparisons
-    // against 64-bit constants that each cost two scalar moves)
-    if (__ballot(!((unsigned)__double2hiint(x) - 0x03b00000u < 0x7c200000u - 0x03b00000u))) {
+}
+// 2^-964 <= x < 2^963, i.e. 4.6e-291 .. 7.8e289, positive, finite, not NaN, tested on the exponent: one integer subtraction and
+// comparison with 32-bit literals instead of two comparisons against 64-bit constants that each cost two scalar moves
+__device__ inline bool sf_sqrt_fast_range(unsigned hi) { return hi - 0x03b00000u < 0x7c200000u - 0x03b00000u; }
+
+__device__ inline void sf_sqrt_rsqrt(double x, double &root, double &inv)
+{
+    sf_sqrt_rsqrt_newton(x, root, inv);
+    if (__ballot(!sf_sqrt_fast_range((unsigned)__double2hiint(x)))) { // (wave-uniform, never taken for real clouds)
         root = sqrt(x);
         inv = 1.0 / root;
     }
@@ -83,21 +84,8 @@ __device__ inline void sf_sqrt_rsqrt(double x, double &root, double &inv)
 // comparisons against 64-bit literals (six vector instructions with their moves).
 __device__ inline void sf_sqrt_rsqrt_uniform(double x, double &root, double &inv)
 {
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane(__double2hiint(x));
-    if (hi - 0x03b00000u < 0x7c200000u - 0x03b00000u) { // 2^-964 <= x < 2^963, positive, finite
-        const double y = __builtin_amdgcn_rsq(x);
-        double g = x * y, h = 0.5 * y;
-        double r = __builtin_fma(-h, g, 0.5);
-        g = __builtin_fma(g, r, g);
-        h = __builtin_fma(h, r, h);
-        double d = __builtin_fma(-g, g, x);
-        g = __builtin_fma(d, h, g);
-        d = __builtin_fma(-g, g, x);
-        g = __builtin_fma(d, h, g);
-        r = __builtin_fma(-h, g, 0.5);
-        h = __builtin_fma(h, r, h);
-        root = g;
-        inv = h + h;
+    if (sf_sqrt_fast_range((unsigned)__builtin_amdgcn_readfirstlane(__double2hiint(x)))) {
+        sf_sqrt_rsqrt_newton(x, root, inv);
     } else {
         root = sqrt(x);
         inv = 1.0 / root;
@@ -312,5 +300,228 @@ __device__ inline void shot_weights(const shot_kept &g, const shot_consts &k, do
     } while (0)
 
 __device__ inline double shot_untag(unsigned long long x) { return fmax(-__longlong_as_double((long long)x), 0.0); }
+
+// ---- the pieces every body of K5 shares: k_shot_cached, k_shot_team, k_shot_long (shot.hip), k_shot_bins (shot_bins.hip) ------
+// N, where it appears: the number of cosine bins at compile time (11: the tuned forms), 0: a run-time value (k_shot_bins).
+
+// The three slots of a neighbour -- its own bin (A: S2+S5+S8+S10), the neighbouring cosine bin (B: S1), the neighbouring octant
+// (G: S9) -- in shot_kept.  11 bins: three 9-bit fields of bins0, bins1 = valid << 31 | (base & 3).  Any count (rows of up to
+// 2 048 slots): bins0 = base | bcos << 16, bins1 = valid << 31 | bth << 2 | (base & 3).  Bits 0-1 of bins1, shell and half-space,
+// are what shot_weights reads.
+template <int N> __device__ inline void shot_pack(unsigned base, unsigned bcos, unsigned bth, shot_kept &o)
+{
+    o.bins0 = N ? base | (bcos << 9) | (bth << 18) : base | (bcos << 16);
+    o.bins1 = 0x80000000u | (N ? 0u : bth << 2) | (base & 3u);
+}
+template <int N> __device__ inline unsigned shot_slot_a(const shot_kept &g) { return N ? g.bins0 & 511u : g.bins0 & 0xffffu; }
+template <int N> __device__ inline unsigned shot_slot_b(const shot_kept &g) { return N ? (g.bins0 >> 9) & 511u : g.bins0 >> 16; }
+template <int N> __device__ inline unsigned shot_slot_g(const shot_kept &g) { return N ? (g.bins0 >> 18) & 511u : (g.bins1 >> 2) & 0xfffu; }
+__device__ inline unsigned long long shot_key(const shot_kept &g) { return (unsigned long long)__double_as_longlong(g.rho); }
+
+// The geometry of one neighbour at non-zero distance: the five numbers shot_weights needs and its three slots.  With a run-time
+// bin count (n, nd = (double)n) it returns false for a neighbour whose cosine bin is n (a clipped cosine of exactly +1 with n
+// even: rint(n - 0.5) = n, the reference's IndexError), which then takes part in nothing; with 11 bins that cannot happen.
+// The azimuth-neighbour decision uses the sign of the cross product with the octant's centre direction (no atan2); when that is
+// not clearly non-zero it falls back to the reference's own expression, so the decision equals shot.py:283-288 in every case.
+template <int N>
+__device__ inline bool shot_geometry(double cx, double cy, double cz, double d2, double nx, double ny, double nz, const double *E,
+                                     double half_r, int n_, double nd_, shot_kept &o)
+{
+    const int n = N ? N : n_;
+    const double nd = N ? (double)N : nd_;
+    double rho, inv_rho;
+    SF_K5_MARK(50, 0);
+    sf_sqrt_rsqrt(d2, rho, inv_rho);
+    SF_K5_PIN(rho); SF_K5_PIN(inv_rho);
+    SF_K5_MARK(51, 0);
+    // (neighbors - point) @ eigenvectors and normals @ eigenvectors[:, 2] (shot.py:214-215) as the multiply-add chain an
+    // FMA BLAS kernel runs over the inner index -- what the reference's NumPy does on any current x86 / OpenBLAS
+    const double lx = sf_dot3(cx, cy, cz, E[0], E[3], E[6]);
+    const double ly = sf_dot3(cx, cy, cz, E[1], E[4], E[7]);
+    const double lz = sf_dot3(cx, cy, cz, E[2], E[5], E[8]);
+    double cosine = sf_dot3(nx, ny, nz, E[2], E[5], E[8]);
+    cosine = fmin(fmax(cosine, -1.0), 1.0);
+    double lxp = lx, lyp = ly, lzp = lz;
+    SF_K5_PIN(lxp); SF_K5_PIN(lyp); SF_K5_PIN(lzp); SF_K5_PIN(cosine);
+    SF_K5_MARK(52, 0);
+    // bin_dist = (cosine + 1.0) * n / 2.0 - 0.5 in that order, unfused (shot.py:386); rint rounds half to even (:387)
+    const double cpos = (cosine + 1.0) * nd / 2.0 - 0.5;
+    const double cf = rint(cpos);
+    int ci = (int)cf; // 0 .. n (-0.5 rounds to -0)
+    if (!N && ci >= n) return false;
+    double dcp = cpos - cf;
+    SF_K5_PIN(ci); SF_K5_PIN(dcp);
+    SF_K5_MARK(53, 0);
+    int ti = azimuth_octant_wave(lx, ly);
+    SF_K5_PIN(ti);
+    SF_K5_MARK(54, 0);
+    const int pi_ = lz > 0.0 ? 1 : 0;
+    const int ri = rho > half_r ? 1 : 0; // (radius / 2 is exact: the host passes that very double)
+    const double dc = cpos - cf;
+    const int sc = (dc > 0.0) - (dc < 0.0);
+    int cin = ci + sc; // -1 .. n, wrapped as the reference's % n does (shot.py:401): n = 1 wraps onto itself
+    cin = cin < 0 ? n - 1 : (cin >= n ? 0 : cin);
+    // Offset from the octant's centre ray, in the octant's own frame: with a >= b the larger / smaller of |lx|, |ly|, the
+    // point sits atan(b / a) in [0, pi/4] off the nearest axis and the centre ray pi/8 off it, so rotating (a, b) by
+    // -pi/8 gives cross' / dot' = tan(angle off the centre).  Whether theta grows or shrinks with that angle alternates
+    // from octant to octant (even octants: grows).
+    const double C8 = 0.9238795325112867, S8 = 0.3826834323650898; // cos, sin of pi/8
+    const double am = fmax(fabs(lx), fabs(ly)), bm = fmin(fabs(lx), fabs(ly));
+    const double crs = __builtin_fma(C8, bm, -(S8 * am));
+    const double dot = __builtin_fma(C8, am, S8 * bm);
+    const double cross = (ti & 1) ? -crs : crs;
+    int sth;
+    if (fabs(cross) > 1e-9 * (fabs(lx) + fabs(ly))) {
+        sth = cross > 0.0 ? 1 : -1;
+    } else { // on (or within rounding of) the centre ray, or lx = ly = 0: the reference's expression decides
+        const double tsz = 2 * SHOT_PI / 8;
+        double dth = (atan2(ly, lx) - (-SHOT_PI + ti * tsz)) / tsz - 0.5;
+        dth = fmin(fmax(dth, -0.5), 0.5);
+        sth = (dth > 0.0) - (dth < 0.0);
+    }
+    const int tin = (ti + sth) & 7;
+    const unsigned base = (unsigned)(((ci * 8 + ti) * 2 + pi_) * 2 + ri);
+    const unsigned bcos = (unsigned)(((cin * 8 + ti) * 2 + pi_) * 2 + ri);
+    const unsigned bth = (unsigned)(((ci * 8 + tin) * 2 + pi_) * 2 + ri);
+    {
+        double crp = cross, dtp = dot;
+        unsigned b0p = base, b1p = bcos, b2p = bth;
+        SF_K5_PIN(crp); SF_K5_PIN(dtp); SF_K5_PIN(b0p); SF_K5_PIN(b1p); SF_K5_PIN(b2p);
+    }
+    SF_K5_MARK(55, 0);
+    // lz / rho through the reciprocal, then one residual correction: acos has an unbounded derivative at +-1, so for a
+    // neighbour on the frame's z axis a one-ulp error of the quotient would be a 1.5e-8 error of phi (the reference's
+    // correctly rounded division gives exactly +-1 there)
+    double lzr = lz * inv_rho;
+    lzr = __builtin_fma(__builtin_fma(-lzr, rho, lz), inv_rho, lzr);
+    o.rho = rho; o.dc = dc; o.tcross = cross; o.tdot = dot; o.lzr = lzr;
+    shot_pack<N>(base, bcos, bth, o);
+    return true;
+}
+
+// Who writes what, from the A keys read back after the election: the neighbour's own, the one of the other radial shell
+// (slot ^ 1) and of the other half-space (slot ^ 2).  The winner of A (own == key) also writes S3/S4 when it is the farthest of
+// its cell over BOTH shells -- every rho of the outer shell (odd) exceeds every rho of the inner one -- and S6/S7 when it is the
+// farther of the two half-spaces' winners; equal distances there are undefined in the reference (unstable argsort,
+// shot.py:218): z > 0 (up) here.  The forms that hold their neighbours in registers keep the answers as flags of bins1, the
+// streamed forms ask where they add.
+__device__ inline bool shot_writes_cd(bool odd, unsigned long long other_shell) { return odd || other_shell == 0ull; }
+__device__ inline bool shot_writes_ef(unsigned long long key, unsigned long long other_half, bool up)
+{
+    return key > other_half || (key == other_half && up);
+}
+
+// One chunk of a list: entry t of the k entries at `list` (NT: read past the caches, SF_LIST_LOAD), its record, its offset from
+// the keypoint and its normal.  A lane past the end carries point 0's offset and returns false.
+template <bool NT> __device__ inline int shot_list_entry(const int32_t *__restrict__ list, int t, int k)
+{
+    return t < k ? (NT ? SF_LIST_LOAD(list + t) : list[t]) : -1;
+}
+__device__ inline bool shot_gather_entry(const double *__restrict__ rec, int j, double px, double py, double pz, double &cx,
+                                         double &cy, double &cz, double &nx, double &ny, double &nz)
+{
+    double x, y, z;
+    sf_load_pn(rec, j < 0 ? 0 : j, x, y, z, nx, ny, nz);
+    cx = x - px;
+    cy = y - py;
+    cz = z - pz;
+    return j >= 0;
+}
+template <bool NT>
+__device__ inline bool shot_gather64(const double *__restrict__ rec, const int32_t *__restrict__ list, int t, int k, double px,
+                                     double py, double pz, double &cx, double &cy, double &cz, double &nx, double &ny, double &nz)
+{
+    return shot_gather_entry(rec, shot_list_entry<NT>(list, t, k), px, py, pz, cx, cy, cz, nx, ny, nz);
+}
+
+// One step of a streamed sweep: 128 neighbours gathered together, their geometry.  bins1 bit 31 marks a neighbour at non-zero
+// distance whose bins are in range; pos: the lanes at non-zero distance, over: those of them in cosine bin n (N = 0 only).
+template <int N, bool NT>
+__device__ inline void shot_geometry128(const double *__restrict__ rec, const int32_t *__restrict__ list, int t0, int k, int lane,
+                                        double px, double py, double pz, const double *E, double half_r, int n, double nd,
+                                        shot_kept (&g)[2], unsigned long long (&pos)[2], unsigned long long (&over)[2])
+{
+    double cx[2], cy[2], cz[2], nx[2], ny[2], nz[2];
+    int jj[2];
+    bool on[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) jj[u] = shot_list_entry<NT>(list, t0 + 64 * u + lane, k); // (both indices requested before a record)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) on[u] = shot_gather_entry(rec, jj[u], px, py, pz, cx[u], cy[u], cz[u], nx[u], ny[u], nz[u]);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        g[u].bins1 = 0u;
+        const double d2 = (cx[u] * cx[u] + cy[u] * cy[u]) + cz[u] * cz[u];
+        const bool at = on[u] && d2 > 0.0;
+        bool bad = false;
+        if (at) bad = !shot_geometry<N>(cx[u], cy[u], cz[u], d2, nx[u], ny[u], nz[u], E, half_r, n, nd, g[u]);
+        pos[u] = __ballot(at);
+        over[u] = __ballot(bad);
+    }
+}
+
+// ---- the prologue of the forms that hold their chunks in registers (cached, team) ----
+// the lanes of a chunk that hold one of the `rem` entries left, as a wave-uniform mask: votes and gate are mask arithmetic on
+// the scalar unit (a ballot of a bare comparison is the comparison's own result register)
+__device__ inline unsigned long long shot_chunk_mask(int rem) { return rem >= 64 ? ~0ull : (rem > 0 ? (1ull << rem) - 1ull : 0ull); }
+
+// the sign votes of a chunk (shot.py:40-45): the neighbours that project negative on the raw x and z axes (the query itself
+// votes ">= 0", as in the reference)
+__device__ inline void shot_count_votes(double cx, double cy, double cz, const double (&raw)[9], unsigned long long onm, int &xneg,
+                                        int &zneg)
+{
+    const double xo = sf_dot3(cx, cy, cz, raw[0], raw[3], raw[6]);
+    const double zo = sf_dot3(cx, cy, cz, raw[2], raw[5], raw[8]);
+    xneg += __popcll(__ballot(xo < 0.0) & onm);
+    zneg += __popcll(__ballot(zo < 0.0) & onm);
+}
+
+// the gate of a chunk (shot.py:212): its neighbours at non-zero distance, as a mask (padding lanes carry point 0's offset: masked)
+__device__ inline void shot_gate(double cx, double cy, double cz, unsigned long long onm, double &d2, unsigned long long &posm,
+                                 int &npos)
+{
+    d2 = (cx * cx + cy * cy) + cz * cz;
+    posm = __ballot(d2 > 0.0) & onm;
+    npos += __popcll(posm);
+}
+
+// The keypoint of a wave (a team) of a launch over a selection `sel` (sf_dispatch::mid_sel / tail_sel, owner numbering) or over
+// all m: false when it has none.
+__device__ inline bool shot_pick_keypoint(int64_t &q, bool selected, const int32_t *__restrict__ sel, int64_t nsel,
+                                          int64_t view_first, int64_t m)
+{
+    if (selected) {
+        if (q >= nsel) return false;
+        q = (int64_t)sf_uniform(sel[q]) - view_first;
+        if (q < 0) return false;
+    }
+    return q < m;
+}
+
+// The scale of a row from its lanes' partial sums of squares (shot.py:301-305): 1 / norm when normalising, 1 otherwise, 0 for a
+// row of zeros.  negated: for a row held as MINUS its values (the cached form's accumulator), minus that -- with "x * scale + 0"
+// an empty slot then comes out +0 whatever the sign of the scale.  (The short root / inverse-root pair: ~1 ulp each, a third of
+// sqrt() followed by a division.)
+__device__ inline double shot_row_scale(double ss, int normalize, bool negated)
+{
+    double nrm, inv_nrm;
+    sf_sqrt_rsqrt_uniform(sf_wave_sum(ss), nrm, inv_nrm);
+    return nrm > 0.0 ? (normalize ? (negated ? -inv_nrm : inv_nrm) : (negated ? -1.0 : 1.0)) : (negated ? -0.0 : 0.0);
+}
+
+// ---- host: what every K5 launch is given ----
+// The radius-derived constants as the reference's own expressions (shot.py:95-117, 235), the polynomial coefficients (uploaded
+// once per context), and min_nb clamped into [-1, 2^31 - 1]: a list holds fewer than 2^31 points, so "more than min_nb
+// neighbours" is a 32-bit comparison in the kernels.
+static inline int sf_shot_consts(sf_ctx *ctx, double r_, int64_t min_nb, shot_consts *K, int *min_nb32)
+{
+    if (!ctx->shot_coef) {
+        SF_HIP(hipMalloc(&ctx->shot_coef, sizeof(SF_SHOT_COEF)));
+        SF_HIP(hipMemcpy(ctx->shot_coef, SF_SHOT_COEF, sizeof(SF_SHOT_COEF), hipMemcpyHostToDevice));
+    }
+    *K = shot_consts{r_, r_ / 2, r_ / 4, r_ * 3 / 4, 1.0 / (r_ / 2), ctx->shot_coef};
+    *min_nb32 = (int)std::min<int64_t>(std::max<int64_t>(min_nb, -1), 2147483647LL);
+    return SF_OK;
+}
 
 } // namespace
