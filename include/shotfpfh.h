@@ -47,6 +47,7 @@ extern "C" {
 
 #define SF_SHOT_LEN 352 /* 11 cosine x 8 azimuth x 2 elevation x 2 radial bins (shot.py:195) */
 #define SF_SHOT_MAX_COSINE_BINS 64 /* sf_shot_serial_bins: rows of up to 32 x 64 = 2048 bins */
+#define SF_USC_MAX_BINS 4096 /* sf_usc: azimuth_bins x elevation_bins x radius_bins at most (16 B of LDS per bin and wave) */
 #define SF_FAST_FPFH_BINS 8 /* n_bins up to here: LDS-histogram K6 and the matrix-core / streaming K7 */
 #define SF_MAX_FPFH_BINS 1290 /* n_bins^3 must fit an int; the reference takes any n_bins (fpfh.py:16).  What bounds n_bins in
                                 practice is the table of n x n_bins^3 32-bit counts in HBM (the reference holds twice that in host RAM) */
@@ -275,6 +276,31 @@ int sf_shot_serial(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, int64_t min_neig
  * The call waits for its kernels (it reads the range flag back). */
 int sf_shot_serial_bins(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, int64_t n_cosine_bins, int64_t min_neighborhood_size,
                         double *out /* m x 32 n */, int flags);
+
+/* ---- Unique Shape Context (K21; Tombari, Salti, Di Stefano 2010, pcl::UniqueShapeContext; the reference has none) ----------
+ * Per keypoint a histogram of its neighbours' offsets in the frame of sf_shot_lrf over L azimuth x K elevation x J log-radial
+ * bins, bin (l, k, j) at (l K + k) J + j of a row of D = L K J doubles: row[b] = (the exactly rounded sum of the density
+ * weights of the neighbours in bin b) vol[b].  L even and >= 2, K >= 1, J >= 1, D <= SF_USC_MAX_BINS, 0 < min_radius < radius.
+ * sf_usc_tables (host only, no context): what decides a bin, and the bin weights -- e2[J + 1], squared radial edges from
+ *   min_radius^2 to radius^2 in equal steps of log r; ca, sa [L / 2] = cos, sin(2 pi i / L); q[K + 1] = ct |ct| of
+ *   ct = cos(pi i / K); vol[D] = 1 / cbrt(bin volume).  A neighbour at offset d, r2 = |d|^2 > 0 (zero: skipped), (lx, ly, lz)
+ *   in the frame: j = #{1 <= i < J: r2 >= e2[i]}; h = ly < 0 or (ly == 0 and lx < 0), (u, v) = h ? (-lx, -ly) : (lx, ly),
+ *   l = #{1 <= i < L / 2: ca[i] v - sa[i] u >= 0} + h L / 2; k = #{1 <= i < K: lz |lz| <= q[i] r2}; unfused float64.
+ * sf_usc_weights: weight[i] = 1.0 / (number of cloud points within density_radius of point i, itself included), n doubles in
+ *   the caller's order.  It REBUILDS the grid for density_radius: call it before the search whose lists sf_usc is given (lists
+ *   of an earlier grid are refused with SF_ERR_STATE).  flags: SF_OUT_DEVICE = weight is a device pointer.
+ * sf_usc: the rows of the queries of `nbrs`, whose radius is R.  lrf (m x 9, nullable): the frames, as sf_shot_lrf lays them
+ *   out; NULL: K4 on these very lists.  weight: n doubles in the caller's order, each 1 / c of an integer 1 <= c < 2^22 (any
+ *   double in [2^-22, 1] is summed exactly).  normalize != 0: rows divided by their L2 norm.  A keypoint with at most
+ *   min_neighborhood_size neighbours at non-zero distance gets a row of zeros.  Returns SF_ERR_ARG when a weight lies outside
+ *   [2^-22, 1] or a list has 2^24 entries or more; `out` is then undefined.  flags: SF_IN_DEVICE = lrf and weight are device
+ *   pointers, SF_OUT_DEVICE = out is.  The call waits for its kernel (it reads the error word back). */
+int sf_usc_tables(double radius, double min_radius, int64_t azimuth_bins, int64_t elevation_bins, int64_t radius_bins,
+                  double *e2 /* J + 1 */, double *ca /* L / 2 */, double *sa /* L / 2 */, double *q /* K + 1 */, double *vol /* L K J */);
+int sf_usc_weights(sf_ctx *ctx, sf_cloud *cloud, double density_radius, double *weight /* n */, int flags);
+int sf_usc(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, const double *lrf /* m x 9, nullable: K4 on these lists */,
+           const double *weight /* n */, double min_radius, int64_t azimuth_bins, int64_t elevation_bins, int64_t radius_bins,
+           int normalize, int64_t min_neighborhood_size, double *out /* m x L K J */, int flags);
 
 /* ---- a repeated step as ONE launch (HIP graph) -------------------------------------------------------------------------
  * sf_graph_begin .. sf_graph_end capture every device operation the calls in between issue on the context's streams (nothing

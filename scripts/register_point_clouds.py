@@ -46,7 +46,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--iss-gamma21", type=float, default=0.975), p.add_argument("--iss-gamma32", type=float, default=0.975)
     p.add_argument("--min-n-neighbors", type=int, default=None)
     p.add_argument("--proportion", type=float, default=0.5, help="share of points kept by --keypoints random")
-    p.add_argument("--descriptor", default="shot_single_scale", choices=["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale"])
+    p.add_argument("--descriptor", default="shot_single_scale", choices=["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc"],
+                   help="usc: Unique Shape Context at --radius, 14 x 14 x 10 bins, no normals used")
+    p.add_argument("--usc-min-radius", type=float, default=None, metavar="R0", help="--descriptor usc: the first radial edge (default --radius / 10)")
+    p.add_argument("--usc-density-radius", type=float, default=None, metavar="RD",
+                   help="--descriptor usc: the ball whose population weighs a neighbour down (default --radius / 5)")
     p.add_argument("--radius", type=float, required=True)
     p.add_argument("--fpfh-bins", type=int, default=5)
     p.add_argument("--phi", type=float, default=3.0), p.add_argument("--rho", type=float, default=10.0)
@@ -97,6 +101,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.outliers == "radius" and args.outlier_radius is None:
         p.error("--outliers radius needs --outlier-radius")
+    if args.descriptor != "usc" and (args.usc_min_radius is not None or args.usc_density_radius is not None):
+        p.error("--usc-min-radius and --usc-density-radius need --descriptor usc")
     if args.icp_loss is not None and args.icp_loss_scale is None:
         p.error("--icp-loss needs --icp-loss-scale")
     if args.icp_loss is None and (args.icp_loss_scale is not None or args.icp_loss_scale_start is not None):
@@ -145,9 +151,12 @@ def main(argv=None) -> int:
     pipe.select_keypoints(args.keypoints, neighborhood_size=args.keypoint_size, min_n_neighbors=args.min_n_neighbors,
                           proportion_picked=args.proportion, iss_non_max_radius=args.iss_non_max_radius,
                           iss_gamma_21=args.iss_gamma21, iss_gamma_32=args.iss_gamma32)
-    pipe.compute_descriptors(radius=args.radius, descriptor_choice=args.descriptor, fpfh_n_bins=args.fpfh_bins, phi=args.phi,
-                             rho=args.rho, n_scales=args.n_scales, subsample_support=not args.no_support_subsampling,
-                             min_neighborhood_size=args.min_neighborhood_size, disable_progress_bars=True, verbose=False)
+    if args.descriptor == "usc":
+        pipe.compute_usc_descriptor(args.radius, min_radius=args.usc_min_radius, density_radius=args.usc_density_radius)
+    else:
+        pipe.compute_descriptors(radius=args.radius, descriptor_choice=args.descriptor, fpfh_n_bins=args.fpfh_bins, phi=args.phi,
+                                 rho=args.rho, n_scales=args.n_scales, subsample_support=not args.no_support_subsampling,
+                                 min_neighborhood_size=args.min_neighborhood_size, disable_progress_bars=True, verbose=False)
     pipe.find_descriptors_matches(args.matching, reject_threshold=args.reject_threshold,
                                   threshold_multiplier=args.threshold_multiplier)
     logging.info(f"{pipe.matches[0].shape[0]} matches")

@@ -1,6 +1,6 @@
 """GPU drop-ins for shot_fpfh.descriptors (reference descriptors/__init__.py:1-17): the three hot-path
-exports (compute_fpfh_descriptor, compute_normals, ShotMultiprocessor) and the PCA feature helpers that
-share kernel K3 with the normals."""
+exports (compute_fpfh_descriptor, compute_normals, ShotMultiprocessor), the PCA feature helpers that
+share kernel K3 with the normals, and Unique Shape Context (compute_usc_descriptor, K21: not in the reference)."""
 from .fpfh import compute_fpfh_descriptor
 from .normals import compute_normals
 from .pca_features import (
@@ -10,6 +10,7 @@ from .pca_features import (
     compute_sphericity,
 )
 from .shot import ShotMultiprocessor
+from .usc import compute_usc_descriptor
 
 __all__ = [
     "compute_fpfh_descriptor",
@@ -19,4 +20,5 @@ __all__ = [
     "compute_sphericity",
     "compute_local_pca_with_moments",
     "ShotMultiprocessor",
+    "compute_usc_descriptor",
 ]

@@ -1074,6 +1074,21 @@ class Cloud:
         idx = sel[: kept.value].copy()
         return (idx, cnt) if return_counts else idx
 
+    # ---- Unique Shape Context (K21) -------------------------------------------------------------------------
+    def usc_weights(self, density_radius: float, out: Optional[DeviceArray] = None):
+        """sf_usc_weights: 1.0 / (the number of cloud points within density_radius of every point, itself included), float64,
+        caller order; into `out` (a device array of n float64) when given.  Rebuilds the grid: call it BEFORE the search whose
+        lists Neighbors.usc is given."""
+        if out is not None:
+            if out.nbytes < self.n * 8:
+                raise ValueError(f"usc_weights: `out` holds {out.nbytes} bytes, the weights need {self.n * 8}")
+            _ffi.check(self.engine.lib.sf_usc_weights(self.engine.h, self.h, float(density_radius), out.ptr, SF_OUT_DEVICE),
+                       "sf_usc_weights")
+            return out
+        w = np.zeros(self.n, dtype=np.float64)
+        _ffi.check(self.engine.lib.sf_usc_weights(self.engine.h, self.h, float(density_radius), _ptr(w), SF_HOST), "sf_usc_weights")
+        return w
+
     def radius_search_self(self, radius: float, begin: int = 0, end: Optional[int] = None) -> "Neighbors":
         end = self.n if end is None else end
         h = _ffi.check_handle(
@@ -1253,6 +1268,46 @@ class Neighbors:
         if rc == _ffi.SF_ERR_BIN_RANGE:
             raise IndexError(_ffi.last_error())
         _ffi.check(rc, "sf_shot_serial_bins")
+        return res
+
+    def usc(self, weights, min_radius: float, lrf=None, azimuth_bins: int = 14, elevation_bins: int = 14, radius_bins: int = 10,
+            normalize: bool = False, min_neighborhood_size: int = 0, out: Optional[DeviceArray] = None):
+        """sf_usc (K21): the (m, L K J) Unique Shape Context rows of these lists, whose search radius is R.  weights: the
+        cloud's density weights (Cloud.usc_weights, made BEFORE this search), n float64 in the caller's order.  lrf: (m, 3, 3)
+        frames as shot_lrf returns them; None: K4 on these lists.  weights and lrf are host arrays or both device arrays.
+        min_radius: the first radial edge, 0 < min_radius < R (PCL's default is R / 10).  out (a device array of m x L K J float64): the rows stay in HBM."""
+        L, K, J = operator.index(azimuth_bins), operator.index(elevation_bins), operator.index(radius_bins)
+        if L < 2 or L % 2 or K < 1 or J < 1 or L * K * J > _ffi.USC_MAX_BINS:
+            raise ValueError(f"usc: azimuth_bins (even, >= 2) x elevation_bins x radius_bins = {L} x {K} x {J} must make rows of at "
+                             f"most {_ffi.USC_MAX_BINS} bins")
+        D = L * K * J
+        dev_in = isinstance(weights, DeviceArray)
+        if lrf is not None and isinstance(lrf, DeviceArray) != dev_in:
+            raise ValueError("usc: weights and lrf must both be host arrays or both device arrays")
+        if dev_in:
+            if weights.nbytes < self.cloud.n * 8 or (lrf is not None and lrf.nbytes < self.m * 72):
+                raise ValueError("usc: one weight per cloud point and one 3 x 3 frame per keypoint expected")
+            wp, lp = weights.ptr, None if lrf is None else lrf.ptr
+        else:
+            weights = _f64(weights).reshape(-1)
+            if weights.shape[0] != self.cloud.n:
+                raise ValueError("usc: one weight per cloud point expected")
+            if lrf is not None:
+                lrf = _f64(lrf).reshape(-1, 9)
+                if lrf.shape[0] != self.m:
+                    raise ValueError("usc: one local reference frame per keypoint expected")
+            wp, lp = _ptr(weights), _ptr(lrf)
+        if out is None:
+            res = self.engine.host_empty((self.m, D))
+            op, flags = _ptr(res), SF_HOST
+        else:
+            if out.nbytes < self.m * D * 8:
+                raise ValueError(f"usc: `out` holds {out.nbytes} bytes, the rows need {self.m * D * 8}")
+            res, op, flags = out, out.ptr, SF_OUT_DEVICE
+        if dev_in:
+            flags |= SF_IN_DEVICE
+        _ffi.check(self.engine.lib.sf_usc(self.engine.h, self.cloud.h, self.h, lp, wp, float(min_radius), L, K, J, int(bool(normalize)),
+                                          int(min_neighborhood_size), op, flags), "sf_usc")
         return res
 
     def shot_from_moments(self, moments: DeviceArray, first_row: int, normalize: bool, min_neighborhood_size: int,

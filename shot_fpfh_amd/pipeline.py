@@ -17,7 +17,7 @@ import numpy.typing as npt
 
 from . import keypoint_selection as _ks
 from .core import RigidTransform
-from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor
+from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor, compute_usc_descriptor
 from .helpers import write_ply
 from .icp import icp_generalized, icp_point_to_plane, icp_point_to_point, icp_robust, icp_symmetric, icp_trimmed, nearest_within
 from .matching import (
@@ -166,10 +166,26 @@ class RegistrationPipeline:
         self._shot(force_recompute, shot_multiprocessor_config, lambda sm, pts, kp, nrm: sm.compute_descriptor_multiscale(
             point_cloud=pts, keypoints=kp, normals=nrm, radii=radii, voxel_sizes=voxel_sizes, weights=weights))
 
+    def compute_usc_descriptor(self, radius: float, *, min_radius: float | None = None, density_radius: float | None = None,
+                               azimuth_bins: int = 14, elevation_bins: int = 14, radius_bins: int = 10,
+                               local_rf_radius: float | None = None, normalize: bool = False, min_neighborhood_size: int = 0,
+                               force_recompute: bool = False) -> None:
+        """Unique Shape Context rows (`compute_usc_descriptor`, K21; not in the reference) of both clouds' keypoints; the
+        normals are not used."""
+        logging.info("-- Computing Unique Shape Context descriptors --")
+
+        def make(side):
+            points, _, kp = self._cloud(side)
+            return compute_usc_descriptor(points, points[kp], radius, min_radius=min_radius, density_radius=density_radius,
+                                          azimuth_bins=azimuth_bins, elevation_bins=elevation_bins, radius_bins=radius_bins,
+                                          local_rf_radius=local_rf_radius, normalize=normalize,
+                                          min_neighborhood_size=min_neighborhood_size)
+        self._fill("descriptors", force_recompute, make)
+
     def compute_descriptors(
         self,
         radius: float,
-        descriptor_choice: Literal["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale"] = "shot_single_scale",
+        descriptor_choice: Literal["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc"] = "shot_single_scale",
         fpfh_n_bins: int = 5,
         phi: float = 3.0,
         rho: float = 10.0,
@@ -202,6 +218,8 @@ class RegistrationPipeline:
                 return compute_fpfh_descriptor(kp, points, normals, radius=radius, n_bins=fpfh_n_bins,
                                                disable_progress_bars=disable_progress_bars, verbose=verbose)
             self._fill("descriptors", force_recompute, make)
+        elif descriptor_choice == "usc":  # (its own parameters at their defaults: compute_usc_descriptor takes them)
+            self.compute_usc_descriptor(radius, force_recompute=force_recompute)
         else:
             raise ValueError("Incorrect descriptor choice")
 
