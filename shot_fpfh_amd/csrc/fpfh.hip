@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "device_util.h"
+#include "host_stage.h"
 
 namespace {
 
@@ -609,14 +610,9 @@ static int fpfh_run(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const in
     sf_pool_guard tmp(ctx);
     int32_t *pos = nullptr;
     if (kp_idx && m) {
-        const int64_t *src = kp_idx;
-        int64_t *dkp = nullptr;
+        const int64_t *src = nullptr;
         int *dbad = nullptr;
-        if (!(flags & SF_IN_DEVICE)) {
-            SF_CHECK(tmp.alloc(&dkp, (size_t)m));
-            SF_HIP(hipMemcpyAsync(dkp, kp_idx, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-            src = dkp;
-        }
+        SF_CHECK(stage_in(tmp, kp_idx, (size_t)m, flags, &src));
         SF_CHECK(tmp.alloc(&pos, (size_t)m));
         SF_CHECK(tmp.alloc(&dbad, 1));
         SF_HIP(hipMemsetAsync(dbad, 0, sizeof(int), ctx->stream));
@@ -632,11 +628,8 @@ static int fpfh_run(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const in
         }
     }
     const int64_t tot = m * sp->nb3;
-    double *dout = out, *owned = nullptr;
-    if (!(flags & SF_OUT_DEVICE)) {
-        SF_CHECK(tmp.alloc(&owned, (size_t)tot));
-        dout = owned;
-    }
+    double *dout = nullptr;
+    SF_CHECK(stage_out(tmp, out, (size_t)tot, flags, &dout));
     int rc = SF_OK;
     if (m && sp->n_bins > SF_FAST_FPFH_BINS && sp->elem_bytes != 1) {
         if (m > 2147483000LL) { sf_set_error("sf_fpfh: too many keypoints for one launch"); return SF_ERR_UNSUPPORTED; }
@@ -646,10 +639,8 @@ static int fpfh_run(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, sf_spfh *sp, const in
         rc = sp->elem_bytes == 1   ? launch_fpfh_mc(ctx, c, nb, sp, pos, m, dout, cov)
              : sp->elem_bytes == 2 ? launch_fpfh<uint16_t>(ctx, c, nb, sp, pos, m, dout)
                                    : launch_fpfh<uint32_t>(ctx, c, nb, sp, pos, m, dout);
-    if (rc == SF_OK && owned) {
-        if (tot) SF_HIP(hipMemcpyAsync(out, owned, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        SF_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return rc;
+    SF_CHECK(rc);
+    SF_CHECK(finish_out(ctx, out, (size_t)tot, flags, dout));
+    return stage_sync_out(ctx, flags);
 }
 

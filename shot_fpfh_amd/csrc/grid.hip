@@ -7,45 +7,15 @@
 // cell-sorted AoS records {x,y,z,nx,ny,nz} for the list-driven gathers, plus perm / inv_perm (sorted position <-> original index) and
 // cell_start (first sorted position of every cell, x fastest).
 // Roofline: HBM; ~ n * (24 read + 4+4 id/idx + sort passes + 48 gather + 48 write) bytes, one-off.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_reduce.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
-
 #include <algorithm>
 #include <cmath>
 
 #include <cstring>
 
 #include "common.h"
+#include "dev_prims.h"
 #include "device_util.h"
-
-// rocPRIM's radix sort falls back to a merge sort up to 2^20 items (a 1M-point cloud: block sort + 10 merge passes
-// x 2 kernels = 21 launches, 0.16 ms); Onesweep above 64k items does the 16-17 cell-id bits in a few launches.
-// ... and rocPRIM 4.2 carries no tuned Onesweep configuration for gfx950: the generic one sorts 4 bits per pass.  Ten bits per
-// pass (1024-thread blocks, 6 items per thread, match ranking) sorts the 20-bit cell ids of a 1M-point cloud in two passes:
-// 0.117 -> 0.068 ms (8 bits: 0.092-0.102, 11 bits: 0.090, 12 bits: does not fit LDS; tools/ab_k1.sh)
-#ifndef SF_SORT_BITS
-#define SF_SORT_BITS 10
-#endif
-#ifndef SF_SORT_BLOCK
-#define SF_SORT_BLOCK 1024
-#endif
-#ifndef SF_SORT_ITEMS
-#define SF_SORT_ITEMS 6
-#endif
-using sf_onesweep = rocprim::radix_sort_onesweep_config<rocprim::kernel_config<SF_SORT_BLOCK, SF_SORT_ITEMS>, rocprim::kernel_config<SF_SORT_BLOCK, SF_SORT_ITEMS>,
-                                                        SF_SORT_BITS, rocprim::block_radix_rank_algorithm::match>;
-using sf_sort_config = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, sf_onesweep, 65536>;
-
-// The cell-id sort of a grid build: (key, value) pairs of int32, keys of `bits` bits.  (Smaller blocks / fewer items per thread
-// for small inputs were measured on a 190k-point slab: 45-56 us against 50 -- the sort's time there is its nine dependent
-// launches, not its bytes; such builds take the counting path below.)
-static hipError_t sort_cells(void *tmp, size_t &tmp_bytes, int32_t *key_in, int32_t *key_out, int32_t *val_in, int32_t *val_out, size_t n, int bits,
-                             hipStream_t stream)
-{
-    return rocprim::radix_sort_pairs<sf_sort_config>(tmp, tmp_bytes, key_in, key_out, val_in, val_out, n, 0, bits, stream);
-}
+#include "host_stage.h"
 
 namespace {
 
@@ -440,13 +410,8 @@ static int upload_in_zorder(sf_ctx *ctx, sf_cloud *c, const double *src, int fla
     const int64_t n = c->n;
     if (!n) return SF_OK;
     sf_pool_guard tmp(ctx);
-    const double *dsrc = src;
-    if (!(flags & SF_IN_DEVICE)) {
-        double *stage = nullptr;
-        SF_CHECK(tmp.alloc(&stage, (size_t)n * 3));
-        SF_HIP(hipMemcpyAsync(stage, src, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-        dsrc = stage;
-    }
+    const double *dsrc = nullptr;
+    SF_CHECK(stage_in(tmp, src, (size_t)n * 3, flags, &dsrc));
     SF_LAUNCH(ctx, "k0_upload", k_upload_gather, dim3((unsigned)sf_div_up(n, 256)), dim3(256), dsrc, (const int32_t *)c->zperm, n, dst);
     SF_HIP(hipStreamSynchronize(ctx->stream)); // (the caller's buffer / the staging block are free again)
     return SF_OK;
@@ -464,26 +429,16 @@ static int cloud_upload(sf_ctx *ctx, sf_cloud *c, const double *xyz, const doubl
     if (n) {
         // ---- the z-sorted internal order: sort (z, caller index) once, stable ----
         sf_pool_guard tmp(ctx);
-        const double *dsrc = xyz;
-        if (!(flags & SF_IN_DEVICE)) {
-            double *stage = nullptr;
-            SF_CHECK(tmp.alloc(&stage, (size_t)n * 3));
-            SF_HIP(hipMemcpyAsync(stage, xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-            dsrc = stage;
-        }
+        const double *dsrc = nullptr;
+        SF_CHECK(stage_in(tmp, xyz, (size_t)n * 3, flags, &dsrc));
         double *zkey = nullptr;
         int32_t *idx = nullptr;
         SF_CHECK(tmp.alloc(&zkey, (size_t)n));
         SF_CHECK(tmp.alloc(&idx, (size_t)n));
         SF_LAUNCH(ctx, "k0_upload", k_upload_keys, dim3((unsigned)sf_div_up(n, 256)), dim3(256), dsrc, n, zkey, idx);
-        size_t tb = 0;
-        SF_HIP(rocprim::radix_sort_pairs<sf_sort_config>(nullptr, tb, zkey, c->z_orig, idx, c->zperm, (size_t)n, 0, 64, ctx->stream));
-        char *stmp = nullptr;
-        SF_CHECK(tmp.alloc(&stmp, tb ? tb : 8));
-        {
-            sf_launch_timer t_(ctx, "k0_upload");
-            SF_HIP(rocprim::radix_sort_pairs<sf_sort_config>(stmp, tb, zkey, c->z_orig, idx, c->zperm, (size_t)n, 0, 64, ctx->stream));
-        }
+        SF_CHECK(sf_rocprim(ctx, tmp, "k0_upload", true, [&](void *t, size_t &tb) {
+            return rocprim::radix_sort_pairs<sf_sort_config>(t, tb, zkey, c->z_orig, idx, c->zperm, (size_t)n, 0, 64, ctx->stream);
+        }));
         SF_LAUNCH(ctx, "k0_upload", k_upload_gather, dim3((unsigned)sf_div_up(n, 256)), dim3(256), dsrc, (const int32_t *)c->zperm, n,
                   c->xyz_orig);
         SF_HIP(hipStreamSynchronize(ctx->stream));
@@ -826,14 +781,12 @@ static int build_grid(sf_ctx *ctx, sf_cloud *c, double cell, int64_t block_begin
     SF_CHECK(tmp.alloc(&gaps, (size_t)(ncell / SF_LONG_GAP + 2)));
     SF_CHECK(tmp.alloc(&n_gaps, 1));
     if (ns > 0) {
-        size_t tmp_bytes = 0;
-        SF_HIP(sort_cells(nullptr, tmp_bytes, key_in, cid_sorted, val_in, c->perm_int + base, (size_t)ns, bits, ctx->stream));
-        char *stmp = nullptr;
-        SF_CHECK(tmp.alloc(&stmp, tmp_bytes ? tmp_bytes : 8));
-        {
-            sf_launch_timer t_(ctx, "k1_radix_sort");
-            SF_HIP(sort_cells(stmp, tmp_bytes, key_in, cid_sorted, val_in, c->perm_int + base, (size_t)ns, bits, ctx->stream));
-        }
+        // the cell-id sort: (key, value) pairs of int32, keys of `bits` bits.  (Smaller blocks / fewer items per thread for small
+        // inputs were measured on a 190k-point slab: 45-56 us against 50 -- the sort's time there is its nine dependent launches,
+        // not its bytes; such builds take the counting path above.)
+        SF_CHECK(sf_rocprim(ctx, tmp, "k1_radix_sort", true, [&](void *t, size_t &tb) {
+            return rocprim::radix_sort_pairs<sf_sort_config>(t, tb, key_in, cid_sorted, val_in, c->perm_int + base, (size_t)ns, 0, bits, ctx->stream);
+        }));
         SF_LAUNCH(ctx, "k1_gather_sorted", k_gather_sorted, dim3((unsigned)sf_div_up(ns, 256)), dim3(256), c->xyz_orig,
                   (const double *)c->nrm_orig, (const int32_t *)c->perm_int, (const int32_t *)c->zperm, c->perm, base, ns, c->xs, c->ys, c->zs,
                   c->rec, n_gaps);

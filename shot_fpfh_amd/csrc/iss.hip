@@ -20,12 +20,10 @@
 // follows the cell-sorted order, and points with equal neighbour sets differ by that rounding alone, so the keypoints of a
 // cloud must not depend on which radius it happened to be searched with before.  The suppression compares stored values and
 // tests exact ball membership: it gives the same flags on any valid grid and takes whichever is there.
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
 #include <cmath>
 
 #include "eigh3.h"
+#include "host_stage.h"
 #include "search_util.h"
 
 namespace {
@@ -48,14 +46,6 @@ __global__ __launch_bounds__(64) void k_iss_saliency(const double *__restrict__ 
     const int64_t o = perm[i];
     saliency[o] = salient ? e3 : -1.0;
     if (count) count[o] = k;
-}
-
-// caller order -> the cell-sorted order of the current grid (+ the two elements the pair loads may touch past the end)
-__global__ void k_iss_gather(const double *__restrict__ score, const int32_t *__restrict__ perm, int64_t n, double *__restrict__ sorted)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) sorted[i] = score[perm[i]];
-    else if (i < n + 2) sorted[i] = 0.0;
 }
 
 #ifndef SF_ISS_WPB
@@ -120,13 +110,6 @@ struct flag_set {
     __host__ __device__ bool operator()(int64_t i) const { return flag[i] != 0; }
 };
 
-int check_radius(const char *who, const char *what, double r)
-{
-    if (r > 0.0 && std::isfinite(r)) return SF_OK;
-    sf_set_error("%s: %s must be positive and finite (got %g)", who, what, r);
-    return SF_ERR_ARG;
-}
-
 int check_rule(const char *who, double gamma_21, double gamma_32, int min_neighbors)
 {
     if (!(gamma_21 > 0.0 && gamma_21 <= 1.0) || !(gamma_32 > 0.0 && gamma_32 <= 1.0)) {
@@ -165,22 +148,12 @@ int select_dev(sf_ctx *ctx, sf_cloud *c, const double *score, double radius, int
     int32_t *flag = nullptr;
     SF_CHECK(tmp.alloc(&sorted, (size_t)n + 2));
     SF_CHECK(tmp.alloc(&flag, (size_t)n));
-    SF_LAUNCH(ctx, "k10_iss_gather", k_iss_gather, dim3((unsigned)sf_div_up(n + 2, 256)), dim3(256), score, (const int32_t *)c->perm, n, sorted);
+    SF_CHECK(sf_perm_gather(ctx, "k10_iss_gather", c, score, 2, sorted)); // (+ the two elements the pair loads may touch past the end)
     const sf_grid_desc g = sf_make_grid_desc(c);
     SF_LAUNCH(ctx, "k10_iss_nms", k_iss_nms, dim3(sf_xcd_grid(sf_div_up(n, 4 * SF_ISS_WPB))), dim3(64 * SF_ISS_WPB), g,
               (const int32_t *)c->cell_start, (const double *)c->xs, (const double *)c->ys, (const double *)c->zs, (const double *)sorted,
               (const int32_t *)c->perm, n, radius * radius, min_neighbors, flag);
-    rocprim::counting_iterator<int64_t> first(0);
-    const flag_set pred{flag};
-    size_t tb = 0;
-    SF_HIP(rocprim::select(nullptr, tb, first, selected, dnum, (size_t)n, pred, ctx->stream));
-    char *scratch = nullptr;
-    SF_CHECK(tmp.alloc(&scratch, tb ? tb : 8));
-    {
-        sf_launch_timer t_(ctx, "k10_iss_compact");
-        SF_HIP(rocprim::select(scratch, tb, first, selected, dnum, (size_t)n, pred, ctx->stream));
-    }
-    return SF_OK;
+    return sf_select_indices(ctx, tmp, "k10_iss_compact", n, flag_set{flag}, selected, dnum);
 }
 
 // the tail of both selecting entry points: the count to the host (one read-back), then the indices if the host wants them
@@ -205,48 +178,38 @@ extern "C" int sf_iss_saliency(sf_ctx *ctx, sf_cloud *c, double salient_radius, 
                                double *saliency, int32_t *count, int flags)
 {
     if (!ctx || !c || !saliency) { sf_set_error("sf_iss_saliency: null argument"); return SF_ERR_ARG; }
-    SF_CHECK(check_radius("sf_iss_saliency", "salient_radius", salient_radius));
+    SF_CHECK(sf_check_radius("sf_iss_saliency", "salient_radius", salient_radius));
     SF_CHECK(check_rule("sf_iss_saliency", gamma_21, gamma_32, min_neighbors));
     SF_HIP(hipSetDevice(ctx->device));
     const int64_t n = c->n;
     if (!n) return SF_OK;
     sf_pool_guard tmp(ctx);
-    double *dsal = saliency;
-    int32_t *dcnt = count;
-    if (!(flags & SF_OUT_DEVICE)) {
-        SF_CHECK(tmp.alloc(&dsal, (size_t)n));
-        if (count) SF_CHECK(tmp.alloc(&dcnt, (size_t)n));
-    }
+    double *dsal = nullptr;
+    int32_t *dcnt = nullptr;
+    SF_CHECK(stage_out(tmp, saliency, (size_t)n, flags, &dsal));
+    if (count) SF_CHECK(stage_out(tmp, count, (size_t)n, flags, &dcnt));
     SF_CHECK(saliency_dev(ctx, c, salient_radius, gamma_21, gamma_32, min_neighbors, dsal, dcnt));
-    if (!(flags & SF_OUT_DEVICE)) {
-        SF_HIP(hipMemcpyAsync(saliency, dsal, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        if (count) SF_HIP(hipMemcpyAsync(count, dcnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        SF_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SF_OK;
+    SF_CHECK(finish_out(ctx, saliency, (size_t)n, flags, dsal));
+    if (count) SF_CHECK(finish_out(ctx, count, (size_t)n, flags, dcnt));
+    return stage_sync_out(ctx, flags);
 }
 
 extern "C" int sf_iss_select(sf_ctx *ctx, sf_cloud *c, const double *saliency, double non_max_radius, int min_neighbors,
                              int64_t *selected, int64_t *n_selected, int flags)
 {
     if (!ctx || !c || !saliency || !selected || !n_selected) { sf_set_error("sf_iss_select: null argument"); return SF_ERR_ARG; }
-    SF_CHECK(check_radius("sf_iss_select", "non_max_radius", non_max_radius));
+    SF_CHECK(sf_check_radius("sf_iss_select", "non_max_radius", non_max_radius));
     SF_CHECK(check_rule("sf_iss_select", 1.0, 1.0, min_neighbors));
     SF_HIP(hipSetDevice(ctx->device));
     const int64_t n = c->n;
     *n_selected = 0;
     if (!n) return SF_OK;
     sf_pool_guard tmp(ctx);
-    const double *dsal = saliency;
-    if (!(flags & SF_IN_DEVICE)) {
-        double *p = nullptr;
-        SF_CHECK(tmp.alloc(&p, (size_t)n));
-        SF_HIP(hipMemcpyAsync(p, saliency, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        dsal = p;
-    }
-    int64_t *dsel = selected;
+    const double *dsal = nullptr;
+    int64_t *dsel = nullptr;
     size_t *dnum = nullptr;
-    if (!(flags & SF_OUT_DEVICE)) SF_CHECK(tmp.alloc(&dsel, (size_t)n));
+    SF_CHECK(stage_in(tmp, saliency, (size_t)n, flags, &dsal));
+    SF_CHECK(stage_out(tmp, selected, (size_t)n, flags, &dsel));
     SF_CHECK(tmp.alloc(&dnum, 1));
     SF_CHECK(select_dev(ctx, c, dsal, non_max_radius, min_neighbors, dsel, dnum));
     return finish_selection(ctx, dnum, dsel, selected, n_selected, flags);
@@ -256,8 +219,8 @@ extern "C" int sf_iss_keypoints(sf_ctx *ctx, sf_cloud *c, double salient_radius,
                                 int min_neighbors, double *saliency, int64_t *selected, int64_t *n_selected, int flags)
 {
     if (!ctx || !c || !selected || !n_selected) { sf_set_error("sf_iss_keypoints: null argument"); return SF_ERR_ARG; }
-    SF_CHECK(check_radius("sf_iss_keypoints", "salient_radius", salient_radius));
-    SF_CHECK(check_radius("sf_iss_keypoints", "non_max_radius", non_max_radius));
+    SF_CHECK(sf_check_radius("sf_iss_keypoints", "salient_radius", salient_radius));
+    SF_CHECK(sf_check_radius("sf_iss_keypoints", "non_max_radius", non_max_radius));
     SF_CHECK(check_rule("sf_iss_keypoints", gamma_21, gamma_32, min_neighbors));
     SF_HIP(hipSetDevice(ctx->device));
     const int64_t n = c->n;
@@ -266,13 +229,13 @@ extern "C" int sf_iss_keypoints(sf_ctx *ctx, sf_cloud *c, double salient_radius,
     sf_pool_guard tmp(ctx);
     const bool dev_out = (flags & SF_OUT_DEVICE) != 0;
     double *dsal = saliency;
-    int64_t *dsel = selected;
+    int64_t *dsel = nullptr;
     size_t *dnum = nullptr;
-    if (!dev_out || !saliency) SF_CHECK(tmp.alloc(&dsal, (size_t)n));
-    if (!dev_out) SF_CHECK(tmp.alloc(&dsel, (size_t)n));
+    if (!dev_out || !saliency) SF_CHECK(tmp.alloc(&dsal, (size_t)n)); // (wanted on the host, or not wanted at all)
+    SF_CHECK(stage_out(tmp, selected, (size_t)n, flags, &dsel));
     SF_CHECK(tmp.alloc(&dnum, 1));
     SF_CHECK(saliency_dev(ctx, c, salient_radius, gamma_21, gamma_32, min_neighbors, dsal, nullptr));
     SF_CHECK(select_dev(ctx, c, dsal, non_max_radius, min_neighbors, dsel, dnum));
-    if (!dev_out && saliency) SF_HIP(hipMemcpyAsync(saliency, dsal, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (saliency) SF_CHECK(finish_out(ctx, saliency, (size_t)n, flags, dsal));
     return finish_selection(ctx, dnum, dsel, selected, n_selected, flags);
 }

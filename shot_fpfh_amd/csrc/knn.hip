@@ -1,9 +1,5 @@
 // knn.hip -- the k nearest neighbours on the grid: replaces KDTree.query(Q, k) (pca_based_descriptors.py:46, the k-NN branch of
 // compute_normals; icp.py's per-iteration query with k = 1).  (Until round 6: part of search.hip.)
-#include <rocprim/device/device_segmented_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -468,16 +464,9 @@ static int knn_round_large(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const sf_grid_
         SF_HIP(hipMemcpyAsync(dseg, seg.data(), ((size_t)nres + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
         SF_LAUNCH(ctx, "k2_knn", k_knn_sweep<true>, dim3(sf_xcd_grid(nres)), dim3(64), g, c->cell_start, c->xs, c->ys, c->zs, nb->qx,
                   nb->qy, nb->qz, (const int32_t *)dq, nres, R2, (int32_t *)nullptr, (const int64_t *)dseg, din, pin);
-        size_t tb = 0;
-        SF_HIP(rocprim::segmented_radix_sort_pairs(nullptr, tb, din, dout, pin, pout, (unsigned)total, (unsigned)nres, dseg, dseg + 1, 0,
-                                                   64, ctx->stream));
-        char *stmp = nullptr;
-        SF_CHECK(bt.alloc(&stmp, tb ? tb : 8));
-        {
-            sf_launch_timer t_(ctx, "k2_knn_sort");
-            SF_HIP(rocprim::segmented_radix_sort_pairs(stmp, tb, din, dout, pin, pout, (unsigned)total, (unsigned)nres, dseg, dseg + 1, 0,
-                                                       64, ctx->stream));
-        }
+        SF_CHECK(sf_rocprim(ctx, bt, "k2_knn_sort", true, [&](void *t, size_t &tb) {
+            return rocprim::segmented_radix_sort_pairs(t, tb, din, dout, pin, pout, (unsigned)total, (unsigned)nres, dseg, dseg + 1, 0, 64, ctx->stream);
+        }));
         SF_LAUNCH(ctx, "k2_knn", k_knn_take, dim3((unsigned)nres), dim3(256), nres, k, (const int64_t *)dseg, (const double *)dout,
                   (const int32_t *)pout, (const int32_t *)dq, (const int32_t *)c->perm, nb->idx);
         SF_HIP(hipStreamSynchronize(ctx->stream)); // qres / seg are host buffers of the async copies
@@ -586,17 +575,10 @@ extern "C" sf_nbrs *sf_knn_search(sf_ctx *ctx, sf_cloud *c, const double *querie
         return SF_OK;
     };
     auto select_status = [&](bool crowded_only, int32_t *out) -> int { // the queries with status == 2 / != 0, ascending
-        rocprim::counting_iterator<int32_t> first(0);
-        size_t tb = 0, *dnum = nullptr;
+        size_t *dnum = nullptr;
         sf_pool_guard st(ctx);
         SF_CHECK(st.alloc(&dnum, 1));
-        const knn_status_is pred{status, crowded_only};
-        SF_HIP(rocprim::select(nullptr, tb, first, out, dnum, (size_t)m, pred, ctx->stream));
-        char *scratch = nullptr;
-        SF_CHECK(st.alloc(&scratch, tb ? tb : 8));
-        sf_launch_timer t_(ctx, "k2_knn_status");
-        SF_HIP(rocprim::select(scratch, tb, first, out, dnum, (size_t)m, pred, ctx->stream));
-        return SF_OK;
+        return sf_select_indices(ctx, st, "k2_knn_status", m, knn_status_is{status, crowded_only}, out, dnum);
     };
     // Each round answers the queries that have k points within R; the others are retried with R doubled on a coarser
     // grid.  A query far outside the cloud's bounding box (KDTree.query answers those too: ICP feeds it scans that are

@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "device_util.h"
+#include "host_stage.h"
 #include "match.h"
 #include "match_mainloop.h"
 
@@ -277,32 +278,22 @@ extern "C" int sf_match_argmin(sf_ctx *ctx, const double *a, int64_t m1, const d
     if (!ctx || !a || !b || !idx || m1 < 0 || m2 < 0 || d <= 0) { sf_set_error("sf_match_argmin: bad argument"); return SF_ERR_ARG; }
     if (m2 == 0 && m1 > 0) { sf_set_error("sf_match_argmin: empty reference set (argmin of an empty sequence)"); return SF_ERR_ARG; }
     SF_HIP(hipSetDevice(ctx->device));
-    const bool in_dev = flags & SF_IN_DEVICE, out_dev = flags & SF_OUT_DEVICE;
     sf_pool_guard tmp(ctx); // staging buffers: back in the pool on every return path
-    double *da = const_cast<double *>(a), *db = const_cast<double *>(b);
-    if (!in_dev) {
-        SF_CHECK(tmp.alloc(&da, (size_t)std::max<int64_t>(m1 * d, 1)));
-        SF_CHECK(tmp.alloc(&db, (size_t)std::max<int64_t>(m2 * d, 1)));
-        if (m1) SF_HIP(hipMemcpyAsync(da, a, (size_t)(m1 * d) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        if (m2) SF_HIP(hipMemcpyAsync(db, b, (size_t)(m2 * d) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    }
-    int64_t *didx = idx, *dcol = col_idx;
-    double *ddist = dist;
-    if (!out_dev) {
-        SF_CHECK(tmp.alloc(&didx, (size_t)std::max<int64_t>(m1, 1)));
-        if (dist) SF_CHECK(tmp.alloc(&ddist, (size_t)std::max<int64_t>(m1, 1)));
-        if (col_idx) SF_CHECK(tmp.alloc(&dcol, (size_t)std::max<int64_t>(m2, 1)));
-    }
+    const double *da, *db;
+    SF_CHECK(stage_in(tmp, a, (size_t)(m1 * d), flags, &da));
+    SF_CHECK(stage_in(tmp, b, (size_t)(m2 * d), flags, &db));
+    int64_t *didx, *dcol = nullptr;
+    double *ddist = nullptr;
+    SF_CHECK(stage_out(tmp, idx, (size_t)m1, flags, &didx));
+    if (dist) SF_CHECK(stage_out(tmp, dist, (size_t)m1, flags, &ddist));
+    if (col_idx) SF_CHECK(stage_out(tmp, col_idx, (size_t)m2, flags, &dcol));
     if (m1) SF_CHECK(match_dispatch(ctx, da, m1, db, m2, d, didx, ddist, "k8_match_tile", "k8_match_gemm"));
     if (col_idx && m2 && m1)
         SF_CHECK(match_dispatch(ctx, db, m2, da, m1, d, dcol, nullptr, "k8_match_tile_cols", "k8_match_gemm_cols"));
-    if (!out_dev) {
-        if (m1) SF_HIP(hipMemcpyAsync(idx, didx, (size_t)m1 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-        if (dist && m1) SF_HIP(hipMemcpyAsync(dist, ddist, (size_t)m1 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        if (col_idx && m2) SF_HIP(hipMemcpyAsync(col_idx, dcol, (size_t)m2 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (!out_dev || !in_dev) SF_HIP(hipStreamSynchronize(ctx->stream)); // host buffers are the caller's again
-    return SF_OK;
+    SF_CHECK(finish_out(ctx, idx, (size_t)m1, flags, didx));
+    if (dist) SF_CHECK(finish_out(ctx, dist, (size_t)m1, flags, ddist));
+    if (col_idx) SF_CHECK(finish_out(ctx, col_idx, (size_t)m2, flags, dcol));
+    return stage_sync(ctx, flags); // host buffers are the caller's again
 }
 
 extern "C" int sf_rows_nonzero(sf_ctx *ctx, const double *rows_dev, int64_t m, int64_t d, unsigned char *mask_dev)
@@ -446,21 +437,13 @@ extern "C" int sf_ransac_score(sf_ctx *ctx, const double *a, const double *b, in
 {
     if (!ctx || !a || !b || !Rt || !inliers || m < 0 || n_draws < 0) { sf_set_error("sf_ransac_score: bad argument"); return SF_ERR_ARG; }
     SF_HIP(hipSetDevice(ctx->device));
-    const bool in_dev = flags & SF_IN_DEVICE, out_dev = flags & SF_OUT_DEVICE;
     sf_pool_guard tmp(ctx);
-    double *da = const_cast<double *>(a), *db = const_cast<double *>(b), *dR = const_cast<double *>(Rt);
-    if (!in_dev) {
-        SF_CHECK(tmp.alloc(&da, (size_t)std::max<int64_t>(m * 3, 1)));
-        SF_CHECK(tmp.alloc(&db, (size_t)std::max<int64_t>(m * 3, 1)));
-        SF_CHECK(tmp.alloc(&dR, (size_t)std::max<int64_t>(n_draws * 12, 1)));
-        if (m) {
-            SF_HIP(hipMemcpyAsync(da, a, (size_t)m * 24, hipMemcpyHostToDevice, ctx->stream));
-            SF_HIP(hipMemcpyAsync(db, b, (size_t)m * 24, hipMemcpyHostToDevice, ctx->stream));
-        }
-        if (n_draws) SF_HIP(hipMemcpyAsync(dR, Rt, (size_t)n_draws * 96, hipMemcpyHostToDevice, ctx->stream));
-    }
-    int64_t *dinl = inliers;
-    if (!out_dev) SF_CHECK(tmp.alloc(&dinl, (size_t)std::max<int64_t>(n_draws, 1)));
+    const double *da, *db, *dR;
+    SF_CHECK(stage_in(tmp, a, (size_t)m * 3, flags, &da));
+    SF_CHECK(stage_in(tmp, b, (size_t)m * 3, flags, &db));
+    SF_CHECK(stage_in(tmp, Rt, (size_t)n_draws * 12, flags, &dR));
+    int64_t *dinl;
+    SF_CHECK(stage_out(tmp, inliers, (size_t)n_draws, flags, &dinl));
     if (n_draws) {
         SF_HIP(hipMemsetAsync(dinl, 0, (size_t)n_draws * sizeof(int64_t), ctx->stream));
         if (m) {
@@ -477,10 +460,8 @@ extern "C" int sf_ransac_score(sf_ctx *ctx, const double *a, const double *b, in
                       n_draws, dps, thr, lo, hi, reinterpret_cast<unsigned long long *>(dinl));
         }
     }
-    if (!out_dev && n_draws)
-        SF_HIP(hipMemcpyAsync(inliers, dinl, (size_t)n_draws * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (!out_dev || !in_dev) SF_HIP(hipStreamSynchronize(ctx->stream));
-    return SF_OK;
+    SF_CHECK(finish_out(ctx, inliers, (size_t)n_draws, flags, dinl));
+    return stage_sync(ctx, flags);
 }
 
 

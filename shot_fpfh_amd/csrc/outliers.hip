@@ -23,11 +23,9 @@
 // sf_iss_select uses it.
 // What bounds it: the search in front (the mean pass reads 4 (k + 1) B of list and gathers 24 (k + 1) B from L2 per point, an
 // order of magnitude below the search's candidate sweep); the radius filter is the count sweep.
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
 #include <cmath>
 
+#include "host_stage.h"
 #include "search_util.h"
 
 namespace {
@@ -106,13 +104,6 @@ __global__ __launch_bounds__(SF_OUT_FOLD) void k_outlier_fold(const double *__re
 
 int stats_blocks(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>(sf_div_up(n, 1024), 1), 1024); } // (n alone)
 
-// cell-sorted position -> the caller's numbering
-__global__ void k_outlier_scatter(const int32_t *__restrict__ sorted, const int32_t *__restrict__ perm, int64_t n, int32_t *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[perm[i]] = sorted[i];
-}
-
 struct keep_near { // mean[i] <= threshold, the stored one
     const double *mean, *stats;
     __host__ __device__ bool operator()(int64_t i) const { return mean[i] <= stats[2]; }
@@ -161,28 +152,16 @@ template <typename Pred>
 int select_dev(sf_ctx *ctx, int64_t n, Pred pred, int64_t *selected, size_t *dnum)
 {
     sf_pool_guard tmp(ctx);
-    rocprim::counting_iterator<int64_t> first(0);
-    size_t tb = 0;
-    SF_HIP(rocprim::select(nullptr, tb, first, selected, dnum, (size_t)n, pred, ctx->stream));
-    char *scratch = nullptr;
-    SF_CHECK(tmp.alloc(&scratch, tb ? tb : 8));
-    sf_launch_timer t_(ctx, "k20_select");
-    SF_HIP(rocprim::select(scratch, tb, first, selected, dnum, (size_t)n, pred, ctx->stream));
-    return SF_OK;
+    return sf_select_indices(ctx, tmp, "k20_select", n, pred, selected, dnum);
 }
 
 // ball sizes (device, n, caller order) on the grid built for `radius`
 int counts_dev(sf_ctx *ctx, sf_cloud *c, double radius, int32_t *count)
 {
-    const int64_t n = c->n;
-    SF_CHECK(sf_k2_own_grid(ctx, c, radius));
     sf_pool_guard tmp(ctx);
     int32_t *sorted = nullptr;
-    SF_CHECK(tmp.alloc(&sorted, (size_t)n + 1));
-    SF_CHECK(sf_k2_count_self(ctx, c, radius, "k20_ball_count", sorted));
-    SF_LAUNCH(ctx, "k20_scatter", k_outlier_scatter, dim3((unsigned)sf_div_up(n, 256)), dim3(256), (const int32_t *)sorted,
-              (const int32_t *)c->perm, n, count);
-    return SF_OK;
+    SF_CHECK(sf_k2_ball_sizes(ctx, c, tmp, radius, "k20_ball_count", &sorted));
+    return sf_perm_scatter(ctx, "k20_scatter", c, (const int32_t *)sorted, count);
 }
 
 // The tail of both filters: everything the host wants is queued behind the kernels -- the count and the three statistics into
@@ -218,7 +197,7 @@ int check_statistical(const char *who, const sf_cloud *c, int k, double std_rati
 
 int check_radius_rule(const char *who, double radius, int min_neighbors)
 {
-    if (!(radius > 0.0) || !std::isfinite(radius)) { sf_set_error("%s: radius must be positive and finite (got %g)", who, radius); return SF_ERR_ARG; }
+    SF_CHECK(sf_check_radius(who, "radius", radius));
     if (min_neighbors < 0) { sf_set_error("%s: min_neighbors must not be negative (got %d)", who, min_neighbors); return SF_ERR_ARG; }
     return SF_OK;
 }
@@ -232,14 +211,11 @@ extern "C" int sf_knn_mean_distance(sf_ctx *ctx, sf_cloud *c, int k, double *mea
     SF_HIP(hipSetDevice(ctx->device));
     const int64_t n = c->n;
     sf_pool_guard tmp(ctx);
-    double *dmean = mean;
-    if (!(flags & SF_OUT_DEVICE)) SF_CHECK(tmp.alloc(&dmean, (size_t)n));
+    double *dmean = nullptr;
+    SF_CHECK(stage_out(tmp, mean, (size_t)n, flags, &dmean));
     SF_CHECK(mean_dev(ctx, c, k, dmean));
-    if (!(flags & SF_OUT_DEVICE)) {
-        SF_HIP(hipMemcpyAsync(mean, dmean, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        SF_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SF_OK;
+    SF_CHECK(finish_out(ctx, mean, (size_t)n, flags, dmean));
+    return stage_sync_out(ctx, flags);
 }
 
 extern "C" int sf_outliers_statistical(sf_ctx *ctx, sf_cloud *c, int k, double std_ratio, double *mean, double *stats, int64_t *selected,
@@ -253,10 +229,10 @@ extern "C" int sf_outliers_statistical(sf_ctx *ctx, sf_cloud *c, int k, double s
     sf_pool_guard tmp(ctx);
     const bool dev_out = (flags & SF_OUT_DEVICE) != 0;
     double *dmean = mean, *dstats = nullptr;
-    int64_t *dsel = selected;
+    int64_t *dsel = nullptr;
     size_t *dnum = nullptr;
-    if (!dev_out || !mean) SF_CHECK(tmp.alloc(&dmean, (size_t)n));
-    if (!dev_out) SF_CHECK(tmp.alloc(&dsel, (size_t)n));
+    if (!dev_out || !mean) SF_CHECK(tmp.alloc(&dmean, (size_t)n)); // (wanted on the host, or not wanted at all)
+    SF_CHECK(stage_out(tmp, selected, (size_t)n, flags, &dsel));
     SF_CHECK(tmp.alloc(&dstats, 3));
     SF_CHECK(tmp.alloc(&dnum, 1));
     SF_CHECK(mean_dev(ctx, c, k, dmean));
@@ -273,14 +249,11 @@ extern "C" int sf_ball_counts(sf_ctx *ctx, sf_cloud *c, double radius, int32_t *
     const int64_t n = c->n;
     if (!n) return SF_OK;
     sf_pool_guard tmp(ctx);
-    int32_t *dcount = count;
-    if (!(flags & SF_OUT_DEVICE)) SF_CHECK(tmp.alloc(&dcount, (size_t)n));
+    int32_t *dcount = nullptr;
+    SF_CHECK(stage_out(tmp, count, (size_t)n, flags, &dcount));
     SF_CHECK(counts_dev(ctx, c, radius, dcount));
-    if (!(flags & SF_OUT_DEVICE)) {
-        SF_HIP(hipMemcpyAsync(count, dcount, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        SF_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SF_OK;
+    SF_CHECK(finish_out(ctx, count, (size_t)n, flags, dcount));
+    return stage_sync_out(ctx, flags);
 }
 
 extern "C" int sf_outliers_radius(sf_ctx *ctx, sf_cloud *c, double radius, int min_neighbors, int32_t *count, int64_t *selected,
@@ -295,10 +268,10 @@ extern "C" int sf_outliers_radius(sf_ctx *ctx, sf_cloud *c, double radius, int m
     sf_pool_guard tmp(ctx);
     const bool dev_out = (flags & SF_OUT_DEVICE) != 0;
     int32_t *dcount = count;
-    int64_t *dsel = selected;
+    int64_t *dsel = nullptr;
     size_t *dnum = nullptr;
-    if (!dev_out || !count) SF_CHECK(tmp.alloc(&dcount, (size_t)n));
-    if (!dev_out) SF_CHECK(tmp.alloc(&dsel, (size_t)n));
+    if (!dev_out || !count) SF_CHECK(tmp.alloc(&dcount, (size_t)n)); // (wanted on the host, or not wanted at all)
+    SF_CHECK(stage_out(tmp, selected, (size_t)n, flags, &dsel));
     SF_CHECK(tmp.alloc(&dnum, 1));
     SF_CHECK(counts_dev(ctx, c, radius, dcount));
     SF_CHECK(select_dev(ctx, n, keep_dense{dcount, min_neighbors}, dsel, dnum));

@@ -9,17 +9,11 @@
 // coalesced SoA loads, ballots the hits and compacts them with mbcnt prefix counts.
 // Output: CSR in HBM -- int32 sorted positions, int64 offsets -- consumed by K3..K7.
 // Roofline: HBM/L2 bound integer+compare work; algorithmic bytes = 24 B per query in + 4 B per pair out.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_reduce.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <numeric>
 
+#include "host_stage.h"
 #include "search_util.h"
 
 sf_grid_desc sf_make_grid_desc(const sf_cloud *c)
@@ -550,16 +544,7 @@ static int select_slots(sf_ctx *ctx, int64_t m, Pred pred, int64_t expect, int32
     size_t *dnum = nullptr;
     SF_CHECK(tmp.alloc(&dnum, 1));
     SF_CHECK(sf_palloc(ctx, out, (size_t)expect + 1));
-    rocprim::counting_iterator<int32_t> first(0);
-    size_t tb = 0;
-    SF_HIP(rocprim::select(nullptr, tb, first, *out, dnum, (size_t)m, pred, ctx->stream));
-    char *scratch = nullptr;
-    SF_CHECK(tmp.alloc(&scratch, tb ? tb : 8));
-    {
-        sf_launch_timer t_(ctx, "k2_select");
-        SF_HIP(rocprim::select(scratch, tb, first, *out, dnum, (size_t)m, pred, ctx->stream));
-    }
-    return SF_OK;
+    return sf_select_indices(ctx, tmp, "k2_select", m, pred, *out, dnum);
 }
 static int select_longer(sf_ctx *ctx, const int32_t *count, int64_t m, int limit, int64_t expect, int32_t **out)
 {
@@ -677,18 +662,13 @@ int sf_k2_count_sample(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double r2, int32_t
 static int exact_scan_fill(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const sf_grid_desc &g, const dim3 &grid, const dim3 &block, double r2)
 {
     const int64_t m = nb->m;
-    auto in = rocprim::make_transform_iterator(nb->count, to_i64());
-    size_t tb1 = 0;
-    SF_HIP(rocprim::exclusive_scan(nullptr, tb1, in, nb->offset, (int64_t)0, (size_t)(m + 1), rocprim::plus<int64_t>(),
-                                   ctx->stream));
-    void *tmp = nullptr;
-    SF_CHECK(sf_pool_alloc(ctx, tb1 ? tb1 : 8, &tmp));
     {
-        sf_launch_timer t_(ctx, "k2_scan");
-        SF_HIP(rocprim::exclusive_scan(tmp, tb1, in, nb->offset, (int64_t)0, (size_t)(m + 1), rocprim::plus<int64_t>(),
-                                       ctx->stream));
+        sf_pool_guard tmp(ctx); // (the scan's temporary: back in the pool before the index array is taken from it)
+        auto in = rocprim::make_transform_iterator(nb->count, to_i64());
+        SF_CHECK(sf_rocprim(ctx, tmp, "k2_scan", true, [&](void *t, size_t &tb) {
+            return rocprim::exclusive_scan(t, tb, in, nb->offset, (int64_t)0, (size_t)(m + 1), rocprim::plus<int64_t>(), ctx->stream);
+        }));
     }
-    sf_pool_release(ctx, tmp);
     SF_CHECK(sf_palloc(ctx, &nb->idx, (size_t)nb->total + 4));
     nb->cap = 0;
     if (nb->total) {
@@ -849,14 +829,9 @@ static int run_search(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb)
         tmp.held.push_back(sel);
         SF_CHECK(tmp.alloc(&off, (size_t)no));
         auto in = rocprim::make_transform_iterator((const int32_t *)sel, count_of{nb->count});
-        size_t tb = 0;
-        SF_HIP(rocprim::exclusive_scan(nullptr, tb, in, off, (int64_t)0, (size_t)no, rocprim::plus<int64_t>(), ctx->stream));
-        char *scratch = nullptr;
-        SF_CHECK(tmp.alloc(&scratch, tb ? tb : 8));
-        {
-            sf_launch_timer t_(ctx, "k2_scan");
-            SF_HIP(rocprim::exclusive_scan(scratch, tb, in, off, (int64_t)0, (size_t)no, rocprim::plus<int64_t>(), ctx->stream));
-        }
+        SF_CHECK(sf_rocprim(ctx, tmp, "k2_scan", true, [&](void *t, size_t &tb) {
+            return rocprim::exclusive_scan(t, tb, in, off, (int64_t)0, (size_t)no, rocprim::plus<int64_t>(), ctx->stream);
+        }));
         SF_CHECK(sf_palloc(ctx, &nb->idx_ovf, (size_t)ovf_total + 4));
         // offset[q] is an element offset from nb->idx: the overflow area is addressed through the same base pointer
         const int64_t delta = (int64_t)(((intptr_t)nb->idx_ovf - (intptr_t)nb->idx) / (intptr_t)sizeof(int32_t));
@@ -926,29 +901,21 @@ int sf_k2_prepare_queries(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const double *q
     SF_CHECK(sf_palloc(ctx, &nb->qz, mm));
     SF_CHECK(sf_palloc(ctx, &nb->qrow, mm));
     if (m) {
+        sf_pool_guard tmp(ctx);
         int32_t *cid = nullptr, *cid_s = nullptr, *val = nullptr;
-        SF_CHECK(sf_palloc(ctx, &cid, mm));
-        SF_CHECK(sf_palloc(ctx, &cid_s, mm));
-        SF_CHECK(sf_palloc(ctx, &val, mm));
+        SF_CHECK(tmp.alloc(&cid, mm));
+        SF_CHECK(tmp.alloc(&cid_s, mm));
+        SF_CHECK(tmp.alloc(&val, mm));
         sf_grid_desc g = sf_make_grid_desc(c);
         SF_LAUNCH(ctx, "k2_query_cells", k_query_cells, dim3((unsigned)sf_div_up(m, 256)), dim3(256), dq, m, g, cid,
                   val);
         int bits = 1;
         while (((int64_t)1 << bits) < c->ncell) ++bits;
-        size_t tb = 0;
-        SF_HIP(rocprim::radix_sort_pairs<sf_sort_config>(nullptr, tb, cid, cid_s, val, nb->qrow, (size_t)m, 0, bits, ctx->stream));
-        void *tmp = nullptr;
-        SF_CHECK(sf_pool_alloc(ctx, tb ? tb : 8, &tmp));
-        {
-            sf_launch_timer t_(ctx, "k2_query_sort");
-            SF_HIP(rocprim::radix_sort_pairs<sf_sort_config>(tmp, tb, cid, cid_s, val, nb->qrow, (size_t)m, 0, bits, ctx->stream));
-        }
+        SF_CHECK(sf_rocprim(ctx, tmp, "k2_query_sort", true, [&](void *t, size_t &tb) {
+            return rocprim::radix_sort_pairs<sf_sort_config>(t, tb, cid, cid_s, val, nb->qrow, (size_t)m, 0, bits, ctx->stream);
+        }));
         SF_LAUNCH(ctx, "k2_gather_queries", k_gather_queries, dim3((unsigned)sf_div_up(m, 256)), dim3(256), dq,
                   nb->qrow, m, nb->qx, nb->qy, nb->qz);
-        sf_pool_release(ctx, tmp);
-        sf_pool_release(ctx, cid);
-        sf_pool_release(ctx, cid_s);
-        sf_pool_release(ctx, val);
     }
     if (own_dq) {
         SF_HIP(hipStreamSynchronize(ctx->stream)); // the host source buffer of the async copy is the caller's
@@ -1008,25 +975,19 @@ extern "C" int sf_normals_radius(sf_ctx *ctx, sf_cloud *c, const double *queries
     if (queries) SF_CHECK(sf_k2_prepare_queries(ctx, c, &q, queries, flags));
     else { q.self = true; q.self_begin = begin; q.qx = c->xs + begin; q.qy = c->ys + begin; q.qz = c->zs + begin; }
     sf_pool_guard tmp(ctx);
-    double *cov = nullptr, *dout = out;
-    const double *dpre = pre;
-    SF_CHECK(tmp.alloc(&cov, (size_t)(m ? m : 1) * 6));
-    if (!(flags & SF_OUT_DEVICE)) SF_CHECK(tmp.alloc(&dout, (size_t)(m ? m : 1) * 3));
-    if (pre && !(flags & SF_IN_DEVICE)) {
-        double *p = nullptr;
-        SF_CHECK(tmp.alloc(&p, (size_t)(m ? m : 1) * 3));
-        if (m) SF_HIP(hipMemcpyAsync(p, pre, (size_t)m * 24, hipMemcpyHostToDevice, ctx->stream));
-        dpre = p;
-    }
+    double *cov = nullptr, *dout = nullptr;
+    const double *dpre = nullptr;
+    SF_CHECK(tmp.alloc(&cov, (size_t)m * 6));
+    SF_CHECK(stage_out(tmp, out, (size_t)m * 3, flags, &dout));
+    SF_CHECK(stage_in(tmp, pre, (size_t)m * 3, flags, &dpre));
     if (m) {
         sf_grid_desc g = sf_make_grid_desc(c);
         SF_LAUNCH(ctx, "k23_radius_cov", k_radius_cov, dim3(sf_xcd_grid(sf_div_up(m, 4 * SF_K2C_WPB))), dim3(64 * SF_K2C_WPB), g,
                   c->cell_start, c->xs, c->ys, c->zs, q.qx, q.qy, q.qz, m, radius * radius, cov, (double *)nullptr, (int32_t *)nullptr);
         SF_CHECK(sf_launch_pca_solve_normals(ctx, cov, q.qrow, m, dpre, dout));
-        if (dout != out) SF_HIP(hipMemcpyAsync(out, dout, (size_t)m * 24, hipMemcpyDeviceToHost, ctx->stream));
+        SF_CHECK(finish_out(ctx, out, (size_t)m * 3, flags, dout));
     }
-    if ((flags & (SF_IN_DEVICE | SF_OUT_DEVICE)) != (SF_IN_DEVICE | SF_OUT_DEVICE)) SF_HIP(hipStreamSynchronize(ctx->stream));
-    return SF_OK;
+    return stage_sync(ctx, flags);
 }
 
 // (for iss.hip) the grid rule of every search, and the fused sweep over the cloud's own points -- all of them, on the grid the
@@ -1063,6 +1024,15 @@ int sf_k2_count_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, 
               c->xs, c->ys, c->zs, c->xs, c->ys, c->zs, m, radius * radius, 0, count, (int64_t *)nullptr, (int32_t *)nullptr,
               (const int32_t *)nullptr);
     return SF_OK;
+}
+
+// (for outliers.hip and usc.hip) the ball sizes of every cloud point on the grid built for `radius` itself (sf_k2_own_grid), by
+// cell-sorted position, in a buffer of n + 1 words lent by the caller's guard
+int sf_k2_ball_sizes(sf_ctx *ctx, sf_cloud *c, sf_pool_guard &g, double radius, const char *prof, int32_t **count)
+{
+    SF_CHECK(sf_k2_own_grid(ctx, c, radius));
+    SF_CHECK(g.alloc(count, (size_t)c->n + 1));
+    return sf_k2_count_self(ctx, c, radius, prof, *count);
 }
 // ---- caller-supplied neighbourhoods ------------------------------------------------------------------------------------------
 // ShotMultiprocessor.compute_local_rf / compute_descriptor take the lists the caller hands them -- support[neighborhoods[i]],
@@ -1107,7 +1077,7 @@ extern "C" sf_nbrs *sf_nbrs_import(sf_ctx *ctx, sf_cloud *c, const double *queri
         sf_set_error("sf_nbrs_import: bad arguments (m=%lld)", (long long)m);
         return nullptr;
     }
-    if (!(radius > 0.0) || !std::isfinite(radius)) { sf_set_error("sf_nbrs_import: radius must be positive and finite (got %g)", radius); return nullptr; }
+    if (sf_check_radius("sf_nbrs_import", "radius", radius) != SF_OK) return nullptr;
     if (hipSetDevice(ctx->device) != hipSuccess) { sf_set_error("hipSetDevice failed"); return nullptr; }
     const bool dev_in = (flags & SF_IN_DEVICE) != 0;
     // the offsets are looked at on the host (m + 1 words): monotone from 0, no list of 2^31 entries

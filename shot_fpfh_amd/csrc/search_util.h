@@ -1,26 +1,11 @@
-// search_util.h -- what the radius search (search.hip), the k-NN search (knn.hip) and the ISS suppression (iss.hip) share: the
-// sort configuration, the stencil bounds of a query, and the run tables and the candidate step of the K2 family's sweeps.
+// search_util.h -- what the radius search (search.hip), the k-NN search (knn.hip), the ISS suppression (iss.hip), the outlier
+// filters (outliers.hip) and USC (usc.hip) share: the stencil bounds of a query, the run tables and the candidate step of the K2
+// family's sweeps, the maps between the caller's point order and the cell-sorted one, and the prototypes of the sweeps that
+// search.hip runs for the other files.  (The sort configuration and the rocPRIM call helper: dev_prims.h.)
 #pragma once
-#include <rocprim/device/device_radix_sort.hpp>
 #include "common.h"
+#include "dev_prims.h"
 #include "device_util.h"
-
-// (see grid.hip: Onesweep instead of the merge-sort fallback up to 2^20 items)
-// ... and rocPRIM 4.2 carries no tuned Onesweep configuration for gfx950: the generic one sorts 4 bits per pass.  Ten bits per
-// pass (1024-thread blocks, 6 items per thread, match ranking) sorts the 20-bit cell ids of a 1M-point cloud in two passes:
-// 0.117 -> 0.068 ms (8 bits: 0.092-0.102, 11 bits: 0.090, 12 bits: does not fit LDS; tools/ab_k1.sh)
-#ifndef SF_SORT_BITS
-#define SF_SORT_BITS 10
-#endif
-#ifndef SF_SORT_BLOCK
-#define SF_SORT_BLOCK 1024
-#endif
-#ifndef SF_SORT_ITEMS
-#define SF_SORT_ITEMS 6
-#endif
-using sf_onesweep = rocprim::radix_sort_onesweep_config<rocprim::kernel_config<SF_SORT_BLOCK, SF_SORT_ITEMS>, rocprim::kernel_config<SF_SORT_BLOCK, SF_SORT_ITEMS>,
-                                                        SF_SORT_BITS, rocprim::block_radix_rank_algorithm::match>;
-using sf_sort_config = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, sf_onesweep, 65536>;
 
 namespace {
 
@@ -157,6 +142,38 @@ __device__ __forceinline__ int2 sf_k2_hit_pos(int total, unsigned long long m0, 
 
 #define SF_K2_SAMPLE 2048 // queries whose lists are counted before a first search sizes its slots
 
+// ---- the caller's point order <-> the cell-sorted order of the current grid (perm: cell-sorted position -> caller index) ------
+struct sf_identity {
+    template <typename T> __host__ __device__ T operator()(T v) const { return v; }
+};
+// out[perm[i]] = f(sorted[i]), i < n
+template <typename S, typename T, typename F>
+__global__ void k_perm_scatter(const S *__restrict__ sorted, const int32_t *__restrict__ perm, int64_t n, T *__restrict__ out, F f)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[perm[i]] = f(sorted[i]);
+}
+// sorted[i] = src[perm[i]], i < n; sorted[n .. n + pad) = 0 (what a sweep's pair loads may touch past the end)
+template <typename T>
+__global__ void k_perm_gather(const T *__restrict__ src, const int32_t *__restrict__ perm, int64_t n, int pad, T *__restrict__ sorted)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) sorted[i] = src[perm[i]];
+    else if (i < n + pad) sorted[i] = T(0);
+}
+template <typename S, typename T, typename F = sf_identity>
+int sf_perm_scatter(sf_ctx *ctx, const char *name, const sf_cloud *c, const S *sorted, T *out, F f = F())
+{
+    SF_LAUNCH(ctx, name, (k_perm_scatter<S, T, F>), dim3((unsigned)sf_div_up(c->n, 256)), dim3(256), sorted, (const int32_t *)c->perm, c->n, out, f);
+    return SF_OK;
+}
+template <typename T>
+int sf_perm_gather(sf_ctx *ctx, const char *name, const sf_cloud *c, const T *src, int pad, T *sorted)
+{
+    SF_LAUNCH(ctx, name, k_perm_gather<T>, dim3((unsigned)sf_div_up(c->n + pad, 256)), dim3(256), src, (const int32_t *)c->perm, c->n, pad, sorted);
+    return SF_OK;
+}
+
 } // namespace
 
 // search.hip, for knn.hip: queries into processing order, and the lists of a strided sample of them counted at a radius
@@ -169,4 +186,6 @@ int sf_k2_ensure_grid(sf_ctx *ctx, sf_cloud *c, double radius);
 int sf_k2_own_grid(sf_ctx *ctx, sf_cloud *c, double radius);
 int sf_k2_radius_cov_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, double *cov, int32_t *count);
 int sf_k2_count_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, int32_t *count);
+// ... and the prologue of every stage that weighs or filters by density: sf_k2_own_grid, then that sweep into n + 1 words of the guard
+int sf_k2_ball_sizes(sf_ctx *ctx, sf_cloud *c, sf_pool_guard &g, double radius, const char *prof, int32_t **count);
 

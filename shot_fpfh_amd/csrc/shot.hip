@@ -732,12 +732,10 @@ extern "C" int sf_azimuth_idx(sf_ctx *ctx, const double *x, const double *y, int
     const double *dx, *dy;
     SF_CHECK(stage_in(tmp, x, (size_t)n, flags, &dx));
     SF_CHECK(stage_in(tmp, y, (size_t)n, flags, &dy));
-    int64_t *dout = idx;
-    if (!(flags & SF_OUT_DEVICE)) SF_CHECK(tmp.alloc(&dout, (size_t)n));
-    if (n) {
-        SF_LAUNCH(ctx, "k5_azimuth_idx", k_azimuth_idx, dim3((unsigned)sf_div_up(n, 256)), dim3(256), dx, dy, n, dout);
-        if (dout != idx) SF_HIP(hipMemcpyAsync(idx, dout, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
+    int64_t *dout;
+    SF_CHECK(stage_out(tmp, idx, (size_t)n, flags, &dout));
+    if (n) { SF_LAUNCH(ctx, "k5_azimuth_idx", k_azimuth_idx, dim3((unsigned)sf_div_up(n, 256)), dim3(256), dx, dy, n, dout); }
+    SF_CHECK(finish_out(ctx, idx, (size_t)n, flags, dout));
     return stage_sync(ctx, flags);
 }
 
@@ -757,8 +755,7 @@ extern "C" int sf_shot_serial(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int64_t min
     SF_CHECK(sf_launch_shot_lrf(ctx, c, nb, 0, 1, dlrf));
     SF_CHECK(launch_shot(ctx, c, nb, dlrf, 1, min_nb, dout, false));
     SF_CHECK(finish_out(ctx, out, (size_t)m * SF_SHOT_LEN, flags, dout));
-    if (!(flags & SF_OUT_DEVICE)) SF_HIP(hipStreamSynchronize(ctx->stream));
-    return SF_OK;
+    return stage_sync_out(ctx, flags);
 }
 
 // Frames by `frames(dlrf)` (raw axes), then the fused K5, which votes on the neighbours it gathers anyway (the streaming K5
@@ -771,18 +768,14 @@ static int shot_fused(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, F frames, int norma
     const int64_t m = nb->m;
     const bool out_dev = flags & SF_OUT_DEVICE;
     sf_pool_guard tmp(ctx);
-    double *dlrf = lrf, *own_lrf = nullptr, *dout;
-    if (!out_dev || !lrf) { // frames wanted on the host, or not wanted at all: scratch on the device
-        SF_CHECK(tmp.alloc(&own_lrf, (size_t)m * 9));
-        dlrf = own_lrf;
-    }
+    double *dlrf = lrf, *dout;
+    if (!out_dev || !lrf) SF_CHECK(tmp.alloc(&dlrf, (size_t)m * 9)); // frames wanted on the host, or not wanted at all: scratch on the device
     SF_CHECK(stage_out(tmp, out, (size_t)m * SF_SHOT_LEN, flags, &dout));
     SF_CHECK(frames(dlrf));
     SF_CHECK(launch_shot(ctx, c, nb, dlrf, normalize, min_nb, dout, true));
-    if (own_lrf && lrf && m) SF_HIP(hipMemcpyAsync(lrf, own_lrf, (size_t)m * 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (lrf) SF_CHECK(finish_out(ctx, lrf, (size_t)m * 9, flags, dlrf));
     SF_CHECK(finish_out(ctx, out, (size_t)m * SF_SHOT_LEN, flags, dout));
-    if (!out_dev) SF_HIP(hipStreamSynchronize(ctx->stream));
-    return SF_OK;
+    return stage_sync_out(ctx, flags);
 }
 
 // Single-scale SHOT in one go (shot_parallelization.py:135-183: frames and descriptor from the SAME search):

@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "device_util.h"
+#include "host_stage.h"
 
 namespace {
 
@@ -907,11 +908,8 @@ extern "C" int sf_spfh_export(sf_ctx *ctx, sf_cloud *c, sf_spfh *sp, double *out
     SF_HIP(hipSetDevice(ctx->device));
     const int64_t n = sp->n, tot = n * sp->nb3;
     sf_pool_guard tmp(ctx);
-    double *dout = out, *owned = nullptr;
-    if (!(flags & SF_OUT_DEVICE)) {
-        SF_CHECK(tmp.alloc(&owned, (size_t)tot));
-        dout = owned;
-    }
+    double *dout = nullptr;
+    SF_CHECK(stage_out(tmp, out, (size_t)tot, flags, &dout));
     if (tot) {
         const dim3 grid((unsigned)sf_div_up(tot, 256)), block(256);
         if (sp->elem_bytes == 1) {
@@ -925,9 +923,6 @@ extern "C" int sf_spfh_export(sf_ctx *ctx, sf_cloud *c, sf_spfh *sp, double *out
                       c->perm, n, sp->nb3, sp->stride, 0u, dout, (const uint8_t *)nullptr, 0, sp->nb3);
         }
     }
-    if (owned) {
-        if (tot) SF_HIP(hipMemcpyAsync(out, owned, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        SF_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return SF_OK;
+    SF_CHECK(finish_out(ctx, out, (size_t)tot, flags, dout));
+    return stage_sync_out(ctx, flags);
 }

@@ -180,24 +180,16 @@ __global__ __launch_bounds__(256) void k_usc(const double *__restrict__ rec, con
     for (int b = lane; b < D; b += 64) sf_store_stream(o + b, __longlong_as_double((long long)acc_lo[b]) * scale);
 }
 
-// cell-sorted counts -> w = 1 / count in the caller's order; and the caller's weights into cell-sorted order
-__global__ void k_usc_weights(const int32_t *__restrict__ sorted, const int32_t *__restrict__ perm, int64_t n, double *__restrict__ weight)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) weight[perm[i]] = 1.0 / (double)sorted[i];
-}
-__global__ void k_usc_sort_weights(const double *__restrict__ weight, const int32_t *__restrict__ perm, int64_t n, double *__restrict__ sorted)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) sorted[i] = weight[perm[i]];
-}
+struct reciprocal { // a ball size -> its density weight
+    __host__ __device__ double operator()(int32_t count) const { return 1.0 / (double)count; }
+};
 
 // Waves per workgroup for rows of D bins: as many as keep the workgroup's LDS within 64 KiB (4 up to 1024, 2 up to 2048, 1 above).
 int usc_waves(int D) { return D <= 1024 ? 4 : (D <= 2048 ? 2 : 1); }
 
 int usc_check_shape(const char *who, double radius, double min_radius, int64_t L, int64_t K, int64_t J)
 {
-    if (!(radius > 0.0) || !std::isfinite(radius)) { sf_set_error("%s: radius must be positive and finite (got %g)", who, radius); return SF_ERR_ARG; }
+    SF_CHECK(sf_check_radius(who, "radius", radius));
     if (!(min_radius > 0.0) || !(min_radius < radius)) {
         sf_set_error("%s: min_radius must lie strictly between 0 and the radius %g (got %g)", who, radius, min_radius);
         return SF_ERR_ARG;
@@ -254,25 +246,18 @@ extern "C" int sf_usc_tables(double radius, double min_radius, int64_t L_, int64
 extern "C" int sf_usc_weights(sf_ctx *ctx, sf_cloud *c, double density_radius, double *weight, int flags)
 {
     if (!ctx || !c || !weight) { sf_set_error("sf_usc_weights: null argument"); return SF_ERR_ARG; }
-    if (!(density_radius > 0.0) || !std::isfinite(density_radius)) {
-        sf_set_error("sf_usc_weights: density_radius must be positive and finite (got %g)", density_radius);
-        return SF_ERR_ARG;
-    }
+    SF_CHECK(sf_check_radius("sf_usc_weights", "density_radius", density_radius));
     SF_HIP(hipSetDevice(ctx->device));
     const int64_t n = c->n;
     if (!n) return SF_OK;
-    SF_CHECK(sf_k2_own_grid(ctx, c, density_radius));
     sf_pool_guard tmp(ctx);
     int32_t *sorted = nullptr;
     double *dw;
-    SF_CHECK(tmp.alloc(&sorted, (size_t)n + 1));
+    SF_CHECK(sf_k2_ball_sizes(ctx, c, tmp, density_radius, "k21_ball_count", &sorted));
     SF_CHECK(stage_out(tmp, weight, (size_t)n, flags, &dw));
-    SF_CHECK(sf_k2_count_self(ctx, c, density_radius, "k21_ball_count", sorted));
-    SF_LAUNCH(ctx, "k21_weights", k_usc_weights, dim3((unsigned)sf_div_up(n, 256)), dim3(256), (const int32_t *)sorted,
-              (const int32_t *)c->perm, n, dw);
+    SF_CHECK(sf_perm_scatter(ctx, "k21_weights", c, (const int32_t *)sorted, dw, reciprocal())); // (cell-sorted counts -> w = 1 / count, caller order)
     SF_CHECK(finish_out(ctx, weight, (size_t)n, flags, dw));
-    if (!(flags & SF_OUT_DEVICE)) SF_HIP(hipStreamSynchronize(ctx->stream));
-    return SF_OK;
+    return stage_sync_out(ctx, flags);
 }
 
 extern "C" int sf_usc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const double *lrf, const double *weight, double min_radius,
@@ -303,7 +288,7 @@ extern "C" int sf_usc(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const double *lrf, 
         SF_CHECK(sf_launch_shot_lrf(ctx, c, nb, 0, 0, dlrf));
         dlrf_in = dlrf;
     }
-    if (n) SF_LAUNCH(ctx, "k21_sort_weights", k_usc_sort_weights, dim3((unsigned)sf_div_up(n, 256)), dim3(256), dw_in, (const int32_t *)c->perm, n, dws);
+    if (n) SF_CHECK(sf_perm_gather(ctx, "k21_sort_weights", c, dw_in, 0, dws));
     int nmin = (int)std::min<int64_t>(std::max<int64_t>(min_nb, -1), 2147483647LL);
     if (m) {
         const int wv = usc_waves(S.D);

@@ -19,12 +19,10 @@
 // (the Python layer passes np.argsort(inverse) -- the reference's own call on the reference's own array -- which makes
 // the result identical to the reference's on the same NumPy build, ties included).
 // HBM roofline: n x (24 B in + 8 B key + 4 B index, sorted once) + 24 B gather per point in V4; a few hundred us at 1M.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <cmath>
 
 #include "common.h"
+#include "dev_prims.h"
 #include "device_util.h"
 
 struct sf_voxels {
@@ -290,6 +288,7 @@ extern "C" sf_voxels *sf_voxels_build(sf_ctx *ctx, const double *xyz, int64_t n,
         sf_palloc(ctx, &v->perm, (size_t)n) != SF_OK || sf_palloc(ctx, &v->rank, (size_t)n) != SF_OK)
         return fail();
     const dim3 grid((unsigned)sf_div_up(n, 256)), block(256);
+    const auto scratch = [&](size_t bytes, void **p) { return sf_ctx_scratch(ctx, bytes, p); }; // (the sort's and the scan's temporary)
     bool ok = hipMemsetAsync(bad, 0, 2 * sizeof(int), ctx->stream) == hipSuccess; // [0]: non-finite input, [1]: fullest voxel
     {
         sf_launch_timer t_(ctx, "v1_voxel_keys");
@@ -298,20 +297,16 @@ extern "C" sf_voxels *sf_voxels_build(sf_ctx *ctx, const double *xyz, int64_t n,
     }
     {
         sf_launch_timer t_(ctx, "v2_voxel_sort");
-        size_t tb = 0;
-        ok = ok && rocprim::radix_sort_pairs<sf_vox_sort_config>(nullptr, tb, key, skey, val, v->perm, (size_t)n, 0, bx + by + bz, ctx->stream) == hipSuccess;
-        void *ts = nullptr;
-        ok = ok && sf_ctx_scratch(ctx, tb, &ts) == SF_OK;
-        ok = ok && rocprim::radix_sort_pairs<sf_vox_sort_config>(ts, tb, key, skey, val, v->perm, (size_t)n, 0, bx + by + bz, ctx->stream) == hipSuccess;
+        ok = ok && sf_rocprim_in(ctx, scratch, "v2_voxel_sort", false, [&](void *t, size_t &tb) {
+                 return rocprim::radix_sort_pairs<sf_vox_sort_config>(t, tb, key, skey, val, v->perm, (size_t)n, 0, bx + by + bz, ctx->stream);
+             }) == SF_OK;
     }
     {
         sf_launch_timer t_(ctx, "v3_voxel_runs");
         hipLaunchKernelGGL(k_voxel_heads, grid, block, 0, ctx->stream, skey, n, head);
-        size_t tb = 0;
-        ok = ok && rocprim::inclusive_scan(nullptr, tb, head, scan, (size_t)n, rocprim::plus<int32_t>(), ctx->stream) == hipSuccess;
-        void *ts = nullptr;
-        ok = ok && sf_ctx_scratch(ctx, tb, &ts) == SF_OK;
-        ok = ok && rocprim::inclusive_scan(ts, tb, head, scan, (size_t)n, rocprim::plus<int32_t>(), ctx->stream) == hipSuccess;
+        ok = ok && sf_rocprim_in(ctx, scratch, "v3_voxel_runs", false, [&](void *t, size_t &tb) {
+                 return rocprim::inclusive_scan(t, tb, head, scan, (size_t)n, rocprim::plus<int32_t>(), ctx->stream);
+             }) == SF_OK;
         hipLaunchKernelGGL(k_voxel_starts, grid, block, 0, ctx->stream, head, scan, n, v->rank, v->start);
         hipLaunchKernelGGL(k_voxel_maxpop, grid, block, 0, ctx->stream, head, v->rank, v->start, n, bad + 1);
     }
