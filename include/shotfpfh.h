@@ -48,6 +48,7 @@ extern "C" {
 #define SF_SHOT_LEN 352 /* 11 cosine x 8 azimuth x 2 elevation x 2 radial bins (shot.py:195) */
 #define SF_SHOT_MAX_COSINE_BINS 64 /* sf_shot_serial_bins: rows of up to 32 x 64 = 2048 bins */
 #define SF_USC_MAX_BINS 4096 /* sf_usc: azimuth_bins x elevation_bins x radius_bins at most (16 B of LDS per bin and wave) */
+#define SF_PFH_MAX_BINS 16 /* sf_pfh: bins per angle; rows of n_bins^3 <= 4096 doubles, the row cap of sf_usc */
 #define SF_FAST_FPFH_BINS 8 /* n_bins up to here: LDS-histogram K6 and the matrix-core / streaming K7 */
 #define SF_MAX_FPFH_BINS 1290 /* n_bins^3 must fit an int; the reference takes any n_bins (fpfh.py:16).  What bounds n_bins in
                                 practice is the table of n x n_bins^3 32-bit counts in HBM (the reference holds twice that in host RAM) */
@@ -301,6 +302,27 @@ int sf_usc_weights(sf_ctx *ctx, sf_cloud *cloud, double density_radius, double *
 int sf_usc(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, const double *lrf /* m x 9, nullable: K4 on these lists */,
            const double *weight /* n */, double min_radius, int64_t azimuth_bins, int64_t elevation_bins, int64_t radius_bins,
            int normalize, int64_t min_neighborhood_size, double *out /* m x L K J */, int flags);
+
+/* ---- Point Feature Histograms (K22; Rusu et al. 2008, pcl::PFHEstimation; the reference has only its fast form, FPFH) --------
+ * Per keypoint a histogram over S x S x S bins (S = n_bins, 1 <= S <= SF_PFH_MAX_BINS) of the Darboux angles of EVERY unordered
+ * pair of the k entries of its list: the pair with bins (b1, b2, b3) of (theta, alpha, phi) at b1 + S b2 + S^2 b3 of a row of
+ * S^3 doubles, row[b] = (100.0 count[b]) / (k (k - 1) / 2); zeros for k < 2.  Bin contents are integers: a row is exact, a
+ * function of the cloud alone (not of the order of a list or of the cloud), and a call repeats bit for bit.
+ * sf_pfh_tables (host only, no context): what decides a bin, S + 1 entries each, the interior ones 1 .. S - 1 used --
+ *   q = c |c| of c[i] = -1 + 2 i / S; ca, sa = cos, sin of e[i] = -pi + 2 pi i / S ((1, 0) exactly where e[i] = 0); g = the sign
+ *   of e[i].  A pair {s, t}, unfused float64: d = p_t - p_s, d2 = |d|^2 (zero: skipped); a_s = n_s.d, a_t = -(n_t.d); the source
+ *   is the one with the larger |a|, then the larger a, then the point first in (x, y, z) order; t the source: d := -d.  n1 the
+ *   source's normal, n2 the other, num3 the source's a; v = d x n1, v2 = |v|^2 (zero: skipped); num2 = v.n2; w = n1 x v;
+ *   a = w.n2; B = (n1.n2) sqrt(v2), B := 1 where a = B = 0.  b3 = #{i: num3 |num3| >= q[i] d2}, b2 = #{i: num2 |num2| >= q[i] v2},
+ *   b1 = #{i: theta = atan2(a, B) >= e[i]} decided by X_i = (ca[i] a - sa[i] B >= 0) and up = (a >= 0): up or X_i where g[i] < 0,
+ *   up and X_i where g[i] > 0, up where g[i] = 0.  The whole statement: tests/pfh_numpy.py.
+ * sf_pfh: the rows of the queries of `nbrs` (a radius search, or sf_nbrs_import).  The cloud must have normals (sf_cloud_upload
+ *   or sf_cloud_set_normals): SF_ERR_STATE otherwise.  Returns SF_ERR_ARG when a list has 65 536 entries or more (its pairs
+ *   would not fit the 32-bit counters); `out` is then undefined.  flags: SF_OUT_DEVICE = out is a device pointer.  The call
+ *   waits for its kernel (it reads the error word back).  Work is quadratic in the list length: k (k - 1) / 2 pairs of about a
+ *   hundred float64 operations per keypoint. */
+int sf_pfh_tables(int64_t n_bins, double *q /* S + 1 */, double *ca /* S + 1 */, double *sa /* S + 1 */, int32_t *g /* S + 1 */);
+int sf_pfh(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, int64_t n_bins, double *out /* m x S^3 */, int flags);
 
 /* ---- a repeated step as ONE launch (HIP graph) -------------------------------------------------------------------------
  * sf_graph_begin .. sf_graph_end capture every device operation the calls in between issue on the context's streams (nothing

@@ -5,7 +5,7 @@ scripts/register_point_clouds.py, with plain argparse flags instead of its YAML 
     python scripts/register_point_clouds.py scan.ply ref.ply --radius 0.05 --descriptor shot_single_scale \
         --keypoints subsampling --keypoint-size 0.03 --ransac-threshold 0.01 --icp point_to_plane --icp-dmax 0.05
 
-Stages: read PLY (optionally --outliers: stray points removed; + PCA normals, k nearest neighbours) -> keypoints -> SHOT / FPFH descriptors -> matching ->
+Stages: read PLY (optionally --outliers: stray points removed; + PCA normals, k nearest neighbours) -> keypoints -> SHOT / FPFH / USC / PFH descriptors -> matching ->
 RANSAC -> ICP -> overlap metrics; optionally writes the aligned pair as PLY.
 """
 from __future__ import annotations
@@ -46,13 +46,15 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--iss-gamma21", type=float, default=0.975), p.add_argument("--iss-gamma32", type=float, default=0.975)
     p.add_argument("--min-n-neighbors", type=int, default=None)
     p.add_argument("--proportion", type=float, default=0.5, help="share of points kept by --keypoints random")
-    p.add_argument("--descriptor", default="shot_single_scale", choices=["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc"],
-                   help="usc: Unique Shape Context at --radius, 14 x 14 x 10 bins, no normals used")
+    p.add_argument("--descriptor", default="shot_single_scale", choices=["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc", "pfh"],
+                   help="usc: Unique Shape Context at --radius, 14 x 14 x 10 bins, no normals used; "
+                        "pfh: Point Feature Histograms at --radius, every pair of a ball's points (quadratic in the ball size)")
     p.add_argument("--usc-min-radius", type=float, default=None, metavar="R0", help="--descriptor usc: the first radial edge (default --radius / 10)")
     p.add_argument("--usc-density-radius", type=float, default=None, metavar="RD",
                    help="--descriptor usc: the ball whose population weighs a neighbour down (default --radius / 5)")
     p.add_argument("--radius", type=float, required=True)
     p.add_argument("--fpfh-bins", type=int, default=5)
+    p.add_argument("--pfh-bins", type=int, default=5, metavar="S", help="--descriptor pfh: bins per angle, 1 .. 16 (rows of S^3)")
     p.add_argument("--phi", type=float, default=3.0), p.add_argument("--rho", type=float, default=10.0)
     p.add_argument("--n-scales", type=int, default=2)
     p.add_argument("--no-support-subsampling", action="store_true")
@@ -154,8 +156,8 @@ def main(argv=None) -> int:
     if args.descriptor == "usc":
         pipe.compute_usc_descriptor(args.radius, min_radius=args.usc_min_radius, density_radius=args.usc_density_radius)
     else:
-        pipe.compute_descriptors(radius=args.radius, descriptor_choice=args.descriptor, fpfh_n_bins=args.fpfh_bins, phi=args.phi,
-                                 rho=args.rho, n_scales=args.n_scales, subsample_support=not args.no_support_subsampling,
+        pipe.compute_descriptors(radius=args.radius, descriptor_choice=args.descriptor, fpfh_n_bins=args.fpfh_bins, pfh_n_bins=args.pfh_bins,
+                                 phi=args.phi, rho=args.rho, n_scales=args.n_scales, subsample_support=not args.no_support_subsampling,
                                  min_neighborhood_size=args.min_neighborhood_size, disable_progress_bars=True, verbose=False)
     pipe.find_descriptors_matches(args.matching, reject_threshold=args.reject_threshold,
                                   threshold_multiplier=args.threshold_multiplier)

@@ -18,6 +18,7 @@ MAX_COSINE_BINS = 64  # SF_SHOT_MAX_COSINE_BINS: sf_shot_serial_bins takes 1 .. 
 SF_ERR_UNSUPPORTED = -6  # e.g. sf_fpfh_moments: K7's form for this table does not carry the frame moments
 SF_ERR_BIN_RANGE = -7  # sf_shot_serial_bins: a neighbour in cosine bin n (the reference's IndexError)
 USC_MAX_BINS = 4096  # SF_USC_MAX_BINS: sf_usc takes rows of at most this many bins
+PFH_MAX_BINS = 16  # SF_PFH_MAX_BINS: sf_pfh takes 1 .. 16 bins per angle (rows of n_bins^3)
 MAX_FPFH_BINS = 1290  # SF_MAX_FPFH_BINS: n_bins^3 fits an int (n_bins above 8 take the generic kernels; memory is the real bound)
 
 
@@ -90,6 +91,8 @@ SIGNATURES = {
     "sf_usc_tables": (_int, [_f64, _f64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sf_usc_weights": (_int, [_vp, _vp, _f64, _vp, _int]),
     "sf_usc": (_int, [_vp, _vp, _vp, _vp, _vp, _f64, _i64, _i64, _i64, _int, _i64, _vp, _int]),
+    "sf_pfh_tables": (_int, [_i64, _vp, _vp, _vp, _vp]),
+    "sf_pfh": (_int, [_vp, _vp, _vp, _i64, _vp, _int]),
     "sf_sync_count": (C.c_ulonglong, []),
     "sf_graph_begin": (_int, [_vp]),
     "sf_graph_end": (_vp, [_vp]),

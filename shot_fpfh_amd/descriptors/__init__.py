@@ -1,6 +1,7 @@
 """GPU drop-ins for shot_fpfh.descriptors (reference descriptors/__init__.py:1-17): the three hot-path
 exports (compute_fpfh_descriptor, compute_normals, ShotMultiprocessor), the PCA feature helpers that
-share kernel K3 with the normals, and Unique Shape Context (compute_usc_descriptor, K21: not in the reference)."""
+share kernel K3 with the normals, Unique Shape Context (compute_usc_descriptor, K21) and Point Feature Histograms
+(compute_pfh_descriptor, K22): neither is in the reference."""
 from .fpfh import compute_fpfh_descriptor
 from .normals import compute_normals
 from .pca_features import (
@@ -9,6 +10,7 @@ from .pca_features import (
     compute_pca_based_features,
     compute_sphericity,
 )
+from .pfh import compute_pfh_descriptor
 from .shot import ShotMultiprocessor
 from .usc import compute_usc_descriptor
 
@@ -21,4 +23,5 @@ __all__ = [
     "compute_local_pca_with_moments",
     "ShotMultiprocessor",
     "compute_usc_descriptor",
+    "compute_pfh_descriptor",
 ]

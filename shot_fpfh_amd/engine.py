@@ -1310,6 +1310,24 @@ class Neighbors:
                                           int(min_neighborhood_size), op, flags), "sf_usc")
         return res
 
+    def pfh(self, n_bins: int = 5, out: Optional[DeviceArray] = None):
+        """sf_pfh (K22): the (m, n_bins**3) Point Feature Histogram rows of these lists -- every unordered pair of a list's
+        entries binned by its three Darboux angles, 100 x count / (k (k - 1) / 2).  The cloud must have normals.  A list of
+        65 536 entries or more is refused.  out (a device array of m x n_bins**3 float64): the rows stay in HBM."""
+        S = operator.index(n_bins)
+        if not 1 <= S <= _ffi.PFH_MAX_BINS:
+            raise ValueError(f"pfh: n_bins = {S} outside [1, {_ffi.PFH_MAX_BINS}]")
+        D = S ** 3
+        if out is None:
+            res = self.engine.host_empty((self.m, D))
+            op, flags = _ptr(res), SF_HOST
+        else:
+            if out.nbytes < self.m * D * 8:
+                raise ValueError(f"pfh: `out` holds {out.nbytes} bytes, the rows need {self.m * D * 8}")
+            res, op, flags = out, out.ptr, SF_OUT_DEVICE
+        _ffi.check(self.engine.lib.sf_pfh(self.engine.h, self.cloud.h, self.h, S, op, flags), "sf_pfh")
+        return res
+
     def shot_from_moments(self, moments: DeviceArray, first_row: int, normalize: bool, min_neighborhood_size: int,
                           out: DeviceArray, lrf_out: Optional[DeviceArray] = None) -> DeviceArray:
         """shot_single_scale from frame moments Spfh.compute(..., moments_out=) left for these lists; `first_row` = row

@@ -17,7 +17,7 @@ import numpy.typing as npt
 
 from . import keypoint_selection as _ks
 from .core import RigidTransform
-from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor, compute_usc_descriptor
+from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor, compute_pfh_descriptor, compute_usc_descriptor
 from .helpers import write_ply
 from .icp import icp_generalized, icp_point_to_plane, icp_point_to_point, icp_robust, icp_symmetric, icp_trimmed, nearest_within
 from .matching import (
@@ -182,10 +182,19 @@ class RegistrationPipeline:
                                           min_neighborhood_size=min_neighborhood_size)
         self._fill("descriptors", force_recompute, make)
 
+    def compute_pfh_descriptor(self, radius: float, n_bins: int = 5, force_recompute: bool = False) -> None:
+        """Point Feature Histogram rows (`compute_pfh_descriptor`, K22; not in the reference) of both clouds' keypoints."""
+        logging.info("-- Computing Point Feature Histogram descriptors --")
+
+        def make(side):
+            points, normals, kp = self._cloud(side)
+            return compute_pfh_descriptor(kp, points, normals, radius, n_bins)
+        self._fill("descriptors", force_recompute, make)
+
     def compute_descriptors(
         self,
         radius: float,
-        descriptor_choice: Literal["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc"] = "shot_single_scale",
+        descriptor_choice: Literal["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc", "pfh"] = "shot_single_scale",
         fpfh_n_bins: int = 5,
         phi: float = 3.0,
         rho: float = 10.0,
@@ -198,6 +207,8 @@ class RegistrationPipeline:
         disable_progress_bars: bool = False,
         verbose: bool = True,
         force_recompute: bool = False,
+        *,
+        pfh_n_bins: int = 5,
     ) -> None:
         shot_config = dict(normalize=normalize, share_local_rfs=share_local_rfs, min_neighborhood_size=min_neighborhood_size,
                            n_procs=n_procs, disable_progress_bar=disable_progress_bars, verbose=verbose)
@@ -220,6 +231,8 @@ class RegistrationPipeline:
             self._fill("descriptors", force_recompute, make)
         elif descriptor_choice == "usc":  # (its own parameters at their defaults: compute_usc_descriptor takes them)
             self.compute_usc_descriptor(radius, force_recompute=force_recompute)
+        elif descriptor_choice == "pfh":
+            self.compute_pfh_descriptor(radius, n_bins=pfh_n_bins, force_recompute=force_recompute)
         else:
             raise ValueError("Incorrect descriptor choice")
 
