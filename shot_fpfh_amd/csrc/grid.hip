@@ -6,7 +6,8 @@
 // cell-sorted SoA positions (xs, ys, zs) so that a wave scanning a run of cells reads consecutive doubles,
 // cell-sorted AoS records {x,y,z,nx,ny,nz} for the list-driven gathers, plus perm / inv_perm (sorted position <-> original index) and
 // cell_start (first sorted position of every cell, x fastest).
-// Roofline: HBM; ~ n * (24 read + 4+4 id/idx + sort passes + 48 gather + 48 write) bytes, one-off.
+// Traffic: ~ n * (24 read + 4+4 id/idx + sort passes + 48 gather + 48 write) bytes, one-off; the build is bound by its launches and
+// by the issue of its scattered gathers, not by these bytes.
 #include <algorithm>
 #include <cmath>
 
@@ -264,7 +265,10 @@ __global__ void k_cell_count(const double *__restrict__ xyz, int64_t first, int6
 // cell_start[cid_base + c] = base + (number of points in the slab's cells before c) from the counters count[c]; the cells
 // in front of the slab get base, those behind it (and the one-past-the-end entry) base + ns.  Blocks [0, slab_tiles) take the
 // slab's tiles in the order they START (a ticket), so a tile's predecessors are always resident: the look-back cannot starve.
-__global__ __launch_bounds__(SF_SCAN_TPB) void k_cell_scan(int32_t *__restrict__ count, int32_t *__restrict__ cell_start, int64_t ncell, int64_t cid_base,
+// (dst / n_items: where the prefix sums go and how many counters there are -- cell_start + cid_base and slab_cells for the counting
+// build, the row build's row_start and its number of rows; the fill outside the slab is the same for both)
+__global__ __launch_bounds__(SF_SCAN_TPB) void k_cell_scan(int32_t *__restrict__ count, int32_t *__restrict__ dst, int64_t n_items,
+                                                           int32_t *__restrict__ cell_start, int64_t ncell, int64_t cid_base,
                                                            int64_t slab_cells, int64_t slab_tiles, int32_t base, int32_t ns,
                                                            unsigned long long *__restrict__ status)
 {
@@ -285,8 +289,8 @@ __global__ __launch_bounds__(SF_SCAN_TPB) void k_cell_scan(int32_t *__restrict__
     const int64_t t = s_tile;
     unsigned long long *st = status + 1;
     const int64_t c0 = t * SF_SCAN_TILE + (int64_t)tid * SF_SCAN_ITEMS;
-    int32_t *p = cell_start + cid_base + c0, *q = count + c0;
-    const int64_t left = slab_cells - c0;
+    int32_t *p = dst + c0, *q = count + c0;
+    const int64_t left = n_items - c0;
     int v[SF_SCAN_ITEMS];
     int sum = 0;
 #pragma unroll
@@ -376,6 +380,323 @@ __global__ void k_cell_settle(const int2 *__restrict__ slot, const int32_t *__re
         rec[6 * i + 3] = nrm[3 * o + 0];
         rec[6 * i + 4] = nrm[3 * o + 1];
         rec[6 * i + 5] = nrm[3 * o + 2];
+    }
+}
+
+// ---- the row build -----------------------------------------------------------------------------------------------------
+// A ROW is the run of dim[0] fine cells that share (cz, cy): a contiguous run of positions.  When the rows are well filled
+// (a uniform cloud at its own radius: ~865 points in each of 1 156 rows at 1M points) the order is made row by row in LDS:
+//   count   a workgroup takes a tile of consecutive internal points (ascending in z: one or two z-layers), counts them per row
+//           in an LDS window of rows that starts at the layer of the tile's first point (and ends at that of its last), and adds every non-empty counter to the
+//           row's global counter: one global atomic per (tile, row), none of them returning.  A point whose row lies outside
+//           the window (a sparse cloud whose tile spans many layers) adds itself to the global counter directly.
+//   scan    k_cell_scan over the row counters = row_start; the counters go back to zero; cells outside the slab filled
+//   place   the same tiles: the LDS count again, returning (a point's place in the tile's share of its row), one returning global
+//           atomic per (tile, row) for the share's offset, and the point drops its key (cx << 32 | internal index) there
+//   settle  one workgroup per row sorts the row's keys (that is the stable order: ascending cell, ascending internal index
+//           inside it), writes the row's dim[0] entries of the cell table and gathers the points; the row's counter goes back
+//           to zero.  A row of up to SF_ROW_CNT keys and SF_ROW_DX cells by a counting sort on cx in LDS (sf_row_by_cell), one of
+//           up to SF_ROW_CAP keys by a bitonic network in LDS, a longer one by the same network in place in global memory.
+#define SF_ROW_TPB 256
+#ifndef SF_ROW_ITEMS
+#define SF_ROW_ITEMS 4 // points per thread of count and place: tiles of 1 024 points (measured at 1M points: count 0.010 / 0.012 / 0.016 ms
+                       // with tiles of 1 024 / 2 048 / 4 096, place 0.011 / 0.011 / 0.013: profiles/k1_rows_ab.md; -DSF_ROW_ITEMS=8 for an A/B build)
+#endif
+#define SF_ROW_WIN 1024 // rows of a tile's LDS window (4 KB; two z-layers of a grid of up to 512 cells along y)
+#define SF_ROW_CAP 4096 // keys of a row that are sorted in LDS (32 KB: five workgroups per CU)
+#define SF_ROW_MIN_MEAN 32 // points per row, on average, from which the host takes the row build (build_grid)
+
+// rows of the window that a tile uses: the internal order ascends in z, so the tile's last point lies in its highest layer
+__device__ __forceinline__ int sf_row_window(const double *__restrict__ xyz, int64_t first, int64_t t0, int64_t n, int tile, const sf_grid_desc &g,
+                                             int64_t row_base, int64_t w0)
+{
+    const int64_t last = first + (t0 + tile < n ? t0 + tile : n) - 1;
+    const int64_t end = ((int64_t)sf_cell_coord(xyz[3 * last + 2], g.lo[2], g.inv_cell, g.dim[2]) + 1) * g.dim[1] - row_base - w0;
+    return (int)(end < SF_ROW_WIN ? end : SF_ROW_WIN);
+}
+
+template <int ITEMS>
+__global__ __launch_bounds__(SF_ROW_TPB) void k_row_count(const double *__restrict__ xyz, int64_t first, int64_t n, sf_grid_desc g, int64_t row_base,
+                                                          int32_t *__restrict__ row_count, unsigned long long *__restrict__ status, int64_t n_status)
+{
+    __shared__ int s_hist[SF_ROW_WIN];
+    const int tid = threadIdx.x;
+    for (int64_t j = (int64_t)blockIdx.x * SF_ROW_TPB + tid; j < n_status; j += (int64_t)gridDim.x * SF_ROW_TPB) status[j] = 0ull; // (as k_cell_count)
+    const int64_t t0 = (int64_t)blockIdx.x * (ITEMS * SF_ROW_TPB); // (< n: the grid is ceil(n / tile))
+    const int64_t w0 = (int64_t)sf_cell_coord(xyz[3 * (first + t0) + 2], g.lo[2], g.inv_cell, g.dim[2]) * g.dim[1] - row_base;
+    const int wn = sf_row_window(xyz, first, t0, n, ITEMS * SF_ROW_TPB, g, row_base, w0);
+    for (int w = tid; w < wn; w += SF_ROW_TPB) s_hist[w] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int64_t i = t0 + k * SF_ROW_TPB + tid;
+        if (i < n) {
+            const int64_t o = first + i;
+            const int cy = sf_cell_coord(xyz[3 * o + 1], g.lo[1], g.inv_cell, g.dim[1]);
+            const int cz = sf_cell_coord(xyz[3 * o + 2], g.lo[2], g.inv_cell, g.dim[2]);
+            const int64_t row = (int64_t)cz * g.dim[1] + cy - row_base, w = row - w0;
+            if (w >= 0 && w < wn) atomicAdd(&s_hist[w], 1); else atomicAdd(&row_count[row], 1);
+        }
+    }
+    __syncthreads();
+    for (int w = tid; w < wn; w += SF_ROW_TPB) {
+        const int v = s_hist[w];
+        if (v) atomicAdd(&row_count[w0 + w], v); // (v > 0: a point fell into this row, so it is one of the slab's)
+    }
+}
+
+template <int ITEMS>
+__global__ __launch_bounds__(SF_ROW_TPB) void k_row_place(const double *__restrict__ xyz, int64_t first, int64_t n, sf_grid_desc g, int64_t row_base,
+                                                          int32_t *__restrict__ row_count, const int32_t *__restrict__ row_start,
+                                                          unsigned long long *__restrict__ slot)
+{
+    __shared__ int s_hist[SF_ROW_WIN];
+    const int tid = threadIdx.x;
+    const int64_t t0 = (int64_t)blockIdx.x * (ITEMS * SF_ROW_TPB);
+    const int64_t w0 = (int64_t)sf_cell_coord(xyz[3 * (first + t0) + 2], g.lo[2], g.inv_cell, g.dim[2]) * g.dim[1] - row_base;
+    const int wn = sf_row_window(xyz, first, t0, n, ITEMS * SF_ROW_TPB, g, row_base, w0);
+    for (int w = tid; w < wn; w += SF_ROW_TPB) s_hist[w] = 0;
+    __syncthreads();
+    int cxs[ITEMS], rws[ITEMS], pl[ITEMS]; // fine x cell, row (-1: no point), place in the tile's share of the row (-1: outside the window)
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int64_t i = t0 + k * SF_ROW_TPB + tid;
+        rws[k] = -1;
+        cxs[k] = 0;
+        pl[k] = -1;
+        if (i < n) {
+            const int64_t o = first + i;
+            cxs[k] = sf_cell_coord(xyz[3 * o + 0], g.lo[0], g.inv_cell_x, g.dim[0]);
+            const int cy = sf_cell_coord(xyz[3 * o + 1], g.lo[1], g.inv_cell, g.dim[1]);
+            const int cz = sf_cell_coord(xyz[3 * o + 2], g.lo[2], g.inv_cell, g.dim[2]);
+            const int64_t row = (int64_t)cz * g.dim[1] + cy - row_base, w = row - w0;
+            rws[k] = (int)row;
+            if (w >= 0 && w < wn) pl[k] = atomicAdd(&s_hist[w], 1);
+        }
+    }
+    __syncthreads();
+    for (int w = tid; w < wn; w += SF_ROW_TPB) {
+        const int v = s_hist[w];
+        if (v) s_hist[w] = (int)((int64_t)row_start[w0 + w] - first) + atomicAdd(&row_count[w0 + w], v); // first slot of the tile's share
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        if (rws[k] < 0) continue;
+        const int64_t i = t0 + k * SF_ROW_TPB + tid;
+        const int64_t dst = pl[k] >= 0 ? (int64_t)s_hist[rws[k] - w0] + pl[k]
+                                       : (int64_t)row_start[rws[k]] - first + atomicAdd(&row_count[rws[k]], 1);
+        slot[dst] = ((unsigned long long)(unsigned)cxs[k] << 32) | (unsigned long long)(unsigned)(first + i);
+    }
+}
+
+// ascending sort of keys[0, len) by the whole workgroup: a bitonic network whose merges all run upwards (the first step of a
+// merge pairs i with its mirror image in the block, the others i with i + j), so a comparator always leaves the larger key at
+// the higher index and the keys past len, thought of as +inf, never move: any length, no padding.  K: LDS or global memory.
+template <class K>
+__device__ __forceinline__ void sf_row_cmpx(K keys, int64_t a, int64_t b)
+{
+    const unsigned long long x = keys[a], y = keys[b];
+    if (y < x) { keys[a] = y; keys[b] = x; }
+}
+
+template <class K>
+__device__ __forceinline__ void sf_row_sort(K keys, int64_t len)
+{
+    const int tid = threadIdx.x;
+    int64_t pairs = 1;
+    while (2 * pairs < len) pairs <<= 1; // half the next power of two
+    if (len < 2) pairs = 0;
+    for (int64_t h = 1; h <= pairs; h <<= 1) { // merges of blocks of 2h keys
+        for (int64_t t = tid; t < pairs; t += SF_ROW_TPB) {
+            const int64_t off = t & (h - 1), a = ((t - off) << 1) + off, b = ((t - off) << 1) + 2 * h - 1 - off;
+            if (b < len) sf_row_cmpx(keys, a, b);
+        }
+        __syncthreads();
+        for (int64_t j = h >> 1; j >= 1; j >>= 1) {
+            for (int64_t t = tid; t < pairs; t += SF_ROW_TPB) {
+                const int64_t off = t & (j - 1), a = ((t - off) << 1) + off, b = a + j;
+                if (b < len) sf_row_cmpx(keys, a, b);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// the cell table of a sorted row (as k_cell_start: position i starts the cells (cx[i - 1], cx[i]]; a run of more than 8 empty
+// cells is filled by the whole wave)
+template <class K>
+__device__ __forceinline__ void sf_row_cells(K keys, int64_t len, int64_t rs, int64_t cell0, int dx, int32_t *__restrict__ cell_start)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int64_t i0 = 0; i0 <= len; i0 += SF_ROW_TPB) {
+        const int64_t i = i0 + tid;
+        int lo = 0, cnt = 0;
+        if (i <= len) {
+            lo = i == 0 ? 0 : (int)(keys[i - 1] >> 32) + 1;
+            const int hi = i == len ? dx - 1 : (int)(keys[i] >> 32); // inclusive
+            cnt = hi - lo + 1;
+            if (cnt < 0) cnt = 0;
+        }
+        const int32_t val = (int32_t)(rs + i);
+        const bool wide = cnt > 8;
+        if (!wide)
+            for (int t = 0; t < cnt; ++t) cell_start[cell0 + lo + t] = val;
+        unsigned long long todo = __ballot(wide);
+        while (todo) {
+            const int src = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int l0 = __shfl(lo, src), ln = __shfl(cnt, src);
+            const int32_t v = __shfl(val, src);
+            for (int t = lane; t < ln; t += 64) cell_start[cell0 + l0 + t] = v;
+        }
+    }
+}
+
+// the gather of a sorted row (as k_gather_sorted): the low word of keys[i] is the internal index of the point at position rs + i.
+// Four points per thread and round, every load of the four issued before the first store.
+template <class K>
+__device__ __forceinline__ void sf_row_gather(K keys, int64_t len, int64_t rs, const double *__restrict__ xyz, const double *__restrict__ nrm,
+                                              const int32_t *__restrict__ zperm, int32_t *__restrict__ perm, int32_t *__restrict__ perm_int,
+                                              double *__restrict__ xs, double *__restrict__ ys, double *__restrict__ zs, double *__restrict__ rec)
+{
+    const int tid = threadIdx.x;
+    for (int64_t i0 = 0; i0 < len; i0 += 4 * SF_ROW_TPB) {
+        int64_t o[4];
+        int32_t zp[4];
+        double p[4][3], q[4][3];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t i = i0 + u * SF_ROW_TPB + tid;
+            o[u] = i < len ? (int64_t)(unsigned)keys[i] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (o[u] < 0) continue;
+            zp[u] = zperm[o[u]];
+            for (int a = 0; a < 3; ++a) p[u][a] = xyz[3 * o[u] + a];
+            if (nrm)
+                for (int a = 0; a < 3; ++a) q[u][a] = nrm[3 * o[u] + a];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (o[u] < 0) continue;
+            const int64_t i = rs + i0 + u * SF_ROW_TPB + tid;
+            perm_int[i] = (int32_t)o[u];
+            perm[i] = zp[u];
+            xs[i] = p[u][0]; ys[i] = p[u][1]; zs[i] = p[u][2];
+            for (int a = 0; a < 3; ++a) rec[6 * i + a] = p[u][a];
+            if (nrm)
+                for (int a = 0; a < 3; ++a) rec[6 * i + 3 + a] = q[u][a];
+        }
+    }
+}
+
+// A row of at most SF_ROW_CNT keys and at most SF_ROW_DX cells, ordered by a counting sort on cx in LDS (seven barriers where the
+// network takes 55 for a thousand keys): count per cell (what the LDS atomic returns is the key's arbitrary place in its cell),
+// exclusive scan = the row's part of the cell table, the indices dropped at cell start + place, every index ranked among its
+// cell's (a cell holds a point or two; as k_cell_settle), and moved to cell start + rank.  Leaves s_idx[i] = the internal index
+// of position rs + i.  (s_cnt: dx + 1 counters; s_wave: one int per wave)
+#define SF_ROW_CNT 2048                         // keys (eight per thread, in registers across the barriers)
+#define SF_ROW_DX (2 * SF_ROW_CAP - SF_ROW_CNT - 1 - SF_ROW_TPB / 64) // cells: the indices, dx + 1 counters and the waves' sums share the network's 32 KB
+#define SF_ROW_PER (SF_ROW_CNT / SF_ROW_TPB)
+__device__ __forceinline__ void sf_row_by_cell(const unsigned long long *__restrict__ mine, int len, int dx, int *s_idx, int *s_cnt, int *s_wave,
+                                               int64_t rs, int64_t cell0, int32_t *__restrict__ cell_start)
+{
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int c = tid; c <= dx; c += SF_ROW_TPB) s_cnt[c] = 0;
+    int cx[SF_ROW_PER], ix[SF_ROW_PER], at[SF_ROW_PER];
+#pragma unroll
+    for (int k = 0; k < SF_ROW_PER; ++k) {
+        const int i = k * SF_ROW_TPB + tid;
+        cx[k] = -1;
+        ix[k] = at[k] = 0;
+        if (i < len) {
+            const unsigned long long key = mine[i];
+            cx[k] = (int)(key >> 32);
+            ix[k] = (int)(unsigned)key;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SF_ROW_PER; ++k)
+        if (cx[k] >= 0) at[k] = atomicAdd(&s_cnt[cx[k]], 1);
+    __syncthreads();
+    { // exclusive scan of the dx counters, in place: a contiguous run of them per thread, the threads' sums over the wave, the waves' in LDS
+        const int per = (dx + SF_ROW_TPB - 1) / SF_ROW_TPB, c0 = tid * per;
+        int sum = 0;
+        for (int k = 0; k < per; ++k)
+            if (c0 + k < dx) sum += s_cnt[c0 + k];
+        int inc = sum;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(inc, off);
+            if (lane >= off) inc += o;
+        }
+        if (lane == 63) s_wave[w] = inc;
+        __syncthreads();
+        int run = inc - sum;
+        for (int k = 0; k < w; ++k) run += s_wave[k];
+        for (int k = 0; k < per; ++k)
+            if (c0 + k < dx) {
+                const int v = s_cnt[c0 + k];
+                s_cnt[c0 + k] = run;
+                run += v;
+            }
+        if (tid == 0) s_cnt[dx] = len;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SF_ROW_PER; ++k)
+        if (cx[k] >= 0) s_idx[s_cnt[cx[k]] + at[k]] = ix[k];
+    for (int c = tid; c < dx; c += SF_ROW_TPB) cell_start[cell0 + c] = (int32_t)(rs + s_cnt[c]);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SF_ROW_PER; ++k)
+        if (cx[k] >= 0) {
+            const int lo = s_cnt[cx[k]], hi = s_cnt[cx[k] + 1];
+            int r = 0;
+            for (int j = lo; j < hi; ++j) r += s_idx[j] < ix[k] ? 1 : 0;
+            at[k] = lo + r;
+        }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SF_ROW_PER; ++k)
+        if (cx[k] >= 0) s_idx[at[k]] = ix[k];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(SF_ROW_TPB) void k_row_settle(unsigned long long *__restrict__ slot, const int32_t *__restrict__ row_start,
+                                                           int32_t *__restrict__ row_count, int64_t rows, int64_t cid_base, int dx, int64_t base,
+                                                           int64_t ns, int32_t *__restrict__ cell_start, const double *__restrict__ xyz,
+                                                           const double *__restrict__ nrm, const int32_t *__restrict__ zperm,
+                                                           int32_t *__restrict__ perm, int32_t *__restrict__ perm_int, double *__restrict__ xs,
+                                                           double *__restrict__ ys, double *__restrict__ zs, double *__restrict__ rec)
+{
+    __shared__ unsigned long long s_keys[SF_ROW_CAP]; // (the counting form: SF_ROW_CNT indices, dx + 1 counters, at the end a sum per wave)
+    const int tid = threadIdx.x;
+    // (workgroups are dealt round-robin over the 8 XCDs: each XCD takes a contiguous run of rows, so the rows of a z-layer, which
+    // gather from the same stretch of the internal order, meet in one L2.  For speed only: any placement gives the same result)
+    const int64_t per_xcd = (rows + 7) / 8, r = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    if (r >= rows) return;
+    const int64_t rs = row_start[r], re = r + 1 < rows ? (int64_t)row_start[r + 1] : base + ns, len = re - rs;
+    if (tid == 0) row_count[r] = 0; // (zero between builds, as the counting build leaves its counters)
+    unsigned long long *mine = slot + (rs - base);
+    const int64_t cell0 = cid_base + r * dx;
+    if (len <= SF_ROW_CNT && dx <= SF_ROW_DX) {
+        int *s_idx = (int *)s_keys;
+        sf_row_by_cell(mine, (int)len, dx, s_idx, s_idx + SF_ROW_CNT, s_idx + 2 * SF_ROW_CAP - SF_ROW_TPB / 64, rs, cell0, cell_start);
+        sf_row_gather(s_idx, len, rs, xyz, nrm, zperm, perm, perm_int, xs, ys, zs, rec);
+    } else if (len <= SF_ROW_CAP) { // (more keys or more cells than the counting form holds: the network, in LDS)
+        for (int i = tid; i < (int)len; i += SF_ROW_TPB) s_keys[i] = mine[i];
+        __syncthreads();
+        sf_row_sort(s_keys, len);
+        sf_row_cells(s_keys, len, rs, cell0, dx, cell_start);
+        sf_row_gather(s_keys, len, rs, xyz, nrm, zperm, perm, perm_int, xs, ys, zs, rec);
+    } else { // (rare by the host's rule: the same network over global memory, in place)
+        sf_row_sort(mine, len);
+        sf_row_cells(mine, len, rs, cell0, dx, cell_start);
+        sf_row_gather(mine, len, rs, xyz, nrm, zperm, perm, perm_int, xs, ys, zs, rec);
     }
 }
 
@@ -728,37 +1049,74 @@ static int build_grid(sf_ctx *ctx, sf_cloud *c, double cell, int64_t block_begin
     const bool force_radix = getenv("SF_K1_RADIX") != nullptr; // (read at every build: the tests compare the two paths in one process)
     // (the counting build ranks every point among the points of its cell, pop compares per point: grids with a handful of points per
     // cell only -- a mean population above 64 goes to the sort, whose cost does not depend on how the points pile up)
-    if (ns > 0 && !force_radix && slab_cells <= SF_COUNT_CELLS_PER_POINT * ns && ns <= 64 * slab_cells) {
-        // ---- the counting build (see k_cell_count): fill, count, scan, place, settle ----
-        const int64_t slab_tiles = sf_div_up(slab_cells, (int64_t)SF_SCAN_TILE), n_status = slab_tiles + 1;
+    // SF_K1_ROWS (read at every build, like SF_K1_RADIX, which wins): 0 never the row build, anything else always, unset the rule
+    // below.  The row build gives a workgroup to every row of the slab, so the rows must be worth one: a mean population of at
+    // least SF_ROW_MIN_MEAN = 32 points (half a wave per sorting pass; an empty row still costs a dispatch and a dim[0]-cell
+    // fill, which the counting build's scan does at streaming speed), and short enough for the counting form of the settle with
+    // room for uneven filling: a mean of at most SF_ROW_CNT / 2 = 1 024 (a uniform row of 1 024 points on average holds more than
+    // 2 048 with probability < 1e-100; up to SF_ROW_CAP = four times the mean a row is still sorted in LDS, by the network).
+    // Both from dims and ns alone: no read-back.
+    const char *rows_env = getenv("SF_K1_ROWS");
+    const int64_t rows = slab_cells / c->dim[0]; // (slab_cells is whole layers of dim[0] * dim[1] cells)
+    const bool rows_rule = rows * SF_ROW_MIN_MEAN <= ns && ns * 2 <= rows * SF_ROW_CNT;
+    const bool use_rows = ns > 0 && !force_radix && (rows_env ? atoi(rows_env) != 0 : rows_rule);
+    const bool count_ok = ns > 0 && !force_radix && slab_cells <= SF_COUNT_CELLS_PER_POINT * ns && ns <= 64 * slab_cells;
+    const bool use_count = !use_rows && count_ok;
+    if (use_rows || use_count) {
+        // ---- the row build (see k_row_count) and the counting build (see k_cell_count): fill, count, scan, place, settle ----
+        const int64_t n_count = use_rows ? rows : slab_cells; // counters: one per row / per cell of the slab
+        const int64_t slab_tiles = sf_div_up(n_count, (int64_t)SF_SCAN_TILE), n_status = slab_tiles + 1;
         const int64_t fill_blocks = sf_div_up(ncell + 1 - slab_cells, (int64_t)SF_SCAN_TILE);
-        int32_t *cid = nullptr, *place = nullptr;
+        int32_t *cid = nullptr, *place = nullptr, *row_start = nullptr;
         int2 *slot = nullptr;
         unsigned long long *status = nullptr;
-        SF_CHECK(tmp.alloc(&cid, (size_t)ns));
-        SF_CHECK(tmp.alloc(&place, (size_t)ns));
+        if (use_rows) {
+            SF_CHECK(tmp.alloc(&row_start, (size_t)rows));
+        } else {
+            SF_CHECK(tmp.alloc(&cid, (size_t)ns));
+            SF_CHECK(tmp.alloc(&place, (size_t)ns));
+        }
         SF_CHECK(tmp.alloc(&slot, (size_t)ns));
         SF_CHECK(tmp.alloc(&status, (size_t)n_status));
         int32_t *start_rel = c->cell_start + cid_base;
-        // (the counters are zero between builds: k_cell_scan writes them back.  A build that did not get as far as its scan --
+        // (the counters are zero between builds: k_cell_scan / k_row_settle write them back.  A build that did not get as far --
         // a launch that failed, an error left on the device by whatever ran before -- leaves them as they are: zeroed again)
         if (hipPeekAtLastError() != hipSuccess) c->count_dirty = true;
-        if (c->cell_count_cap < slab_cells || c->count_dirty) { // (first build of this cloud with a slab this large)
-            if (c->cell_count_cap < slab_cells) {
+        // (a slab that the counting build could take as well gets that build's counters, one per cell: the cloud's builds may
+        // alternate between the two forms, radius by radius, and keep one block)
+        const int64_t n_alloc = count_ok ? slab_cells : n_count;
+        if (c->cell_count_cap < n_alloc || c->count_dirty) { // (first build of this cloud with a slab this large)
+            if (c->cell_count_cap < n_alloc) {
                 if (c->cell_count) sf_pool_release(ctx, c->cell_count);
                 c->cell_count = nullptr;
                 c->cell_count_cap = 0;
-                SF_CHECK(sf_pool_alloc(ctx, (size_t)slab_cells * sizeof(int32_t), (void **)&c->cell_count));
-                c->cell_count_cap = slab_cells;
+                SF_CHECK(sf_pool_alloc(ctx, (size_t)n_alloc * sizeof(int32_t), (void **)&c->cell_count));
+                c->cell_count_cap = n_alloc;
             }
             sf_launch_timer t_(ctx, "k1_cell_zero");
             SF_HIP(hipMemsetAsync(c->cell_count, 0, (size_t)c->cell_count_cap * sizeof(int32_t), ctx->stream));
         }
         c->count_dirty = true;
+        if (use_rows) {
+            static_assert(sizeof(int2) == sizeof(unsigned long long), "");
+            unsigned long long *keys = (unsigned long long *)slot;
+            const int64_t row_base = cid_base / c->dim[0];
+            const dim3 tiles((unsigned)sf_div_up(ns, (int64_t)SF_ROW_ITEMS * SF_ROW_TPB)), tpb(SF_ROW_TPB);
+            SF_LAUNCH(ctx, "k1_cell_count", k_row_count<SF_ROW_ITEMS>, tiles, tpb, c->xyz_orig, base, ns, g, row_base, c->cell_count, status, n_status);
+            SF_LAUNCH(ctx, "k1_cell_scan", k_cell_scan, dim3((unsigned)(slab_tiles + fill_blocks)), dim3(SF_SCAN_TPB), c->cell_count, row_start, rows,
+                      c->cell_start, ncell, cid_base, slab_cells, slab_tiles, (int32_t)base, (int32_t)ns, status);
+            SF_LAUNCH(ctx, "k1_cell_place", k_row_place<SF_ROW_ITEMS>, tiles, tpb, c->xyz_orig, base, ns, g, row_base, c->cell_count,
+                      (const int32_t *)row_start, keys);
+            SF_LAUNCH(ctx, "k1_cell_settle", k_row_settle, dim3((unsigned)(8 * ((rows + 7) / 8))), tpb, keys, (const int32_t *)row_start, c->cell_count, rows, cid_base,
+                      c->dim[0], base, ns, c->cell_start, c->xyz_orig, (const double *)c->nrm_orig, (const int32_t *)c->zperm, c->perm, c->perm_int,
+                      c->xs, c->ys, c->zs, c->rec);
+            c->count_dirty = false;
+            return SF_OK;
+        }
         SF_LAUNCH(ctx, "k1_cell_count", k_cell_count, dim3((unsigned)sf_div_up(std::max(ns, n_status), 256)), dim3(256), c->xyz_orig, base, ns, g,
                   (int)cid_base, c->cell_count, cid, place, status, n_status);
-        SF_LAUNCH(ctx, "k1_cell_scan", k_cell_scan, dim3((unsigned)(slab_tiles + fill_blocks)), dim3(SF_SCAN_TPB), c->cell_count, c->cell_start, ncell,
-                  cid_base, slab_cells, slab_tiles, (int32_t)base, (int32_t)ns, status);
+        SF_LAUNCH(ctx, "k1_cell_scan", k_cell_scan, dim3((unsigned)(slab_tiles + fill_blocks)), dim3(SF_SCAN_TPB), c->cell_count, start_rel, slab_cells,
+                  c->cell_start, ncell, cid_base, slab_cells, slab_tiles, (int32_t)base, (int32_t)ns, status);
         c->count_dirty = false;
         SF_LAUNCH(ctx, "k1_cell_place", k_cell_place, dim3((unsigned)sf_div_up(ns, 256)), dim3(256), (const int32_t *)cid,
                   (const int32_t *)place, (const int32_t *)start_rel, base, ns, slot);

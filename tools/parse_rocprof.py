@@ -45,6 +45,7 @@ SHORT_RE = [
     (r"k_fpfh_tail", "k7_fpfh_tail"), (r"k_spfh<[^>]*, true>", "k6_spfh_tail"), (r"k_pca_cov<0, true>", "k3_normals_tail"),
     (r"k_cell_fill_long", "k1_cell_start"), (r"k_cell_count", "k1_cell_count"), (r"k_cell_scan", "k1_cell_scan"), (r"k_cell_place", "k1_cell_place"),
     (r"k_cell_settle", "k1_cell_settle"),
+    (r"k_row_count", "k1_cell_count"), (r"k_row_place", "k1_cell_place"), (r"k_row_settle", "k1_cell_settle"),  # (the row build keeps the timer names)
 ]
 
 
