@@ -250,7 +250,11 @@ int sf_eigh3(sf_ctx *ctx, const double *lower /* m x 6: a11 a21 a31 a22 a32 a33 
  * sf_shot_lrf (K4): get_local_rf (shot.py:16-48) for every query of `nbrs`; radius = the search
  *   radius of `nbrs`.  lrf is m x 9, row-major 3x3 with COLUMNS x, y, z (shot.py:48).
  * sf_shot (K5): compute_single_shot_descriptor (shot.py:175-306) incl. the last-writer-wins
- *   semantics of the ten fancy-index "+=" statements (shot.py:244-298).  out is m x 352. */
+ *   semantics of the ten fancy-index "+=" statements (shot.py:244-298).  out is m x 352.
+ *   Neighbours at EQUAL distance (the reference leaves their order to np.argsort, shot.py:218): the ten statements see the
+ *   neighbours in one order, ascending distance and among bit-equal distances ascending index in the caller's cloud array,
+ *   so among equally far neighbours the one with the largest index writes last -- whatever kernel form serves the keypoint,
+ *   for searched and imported lists, in every entry point that computes SHOT rows. */
 int sf_shot_lrf(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, double *lrf /* m x 9 */, int flags);
 int sf_shot(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, const double *lrf /* m x 9 */, int normalize,
             int64_t min_neighborhood_size, double *out /* m x 352 */, int flags);
@@ -265,7 +269,8 @@ int sf_azimuth_idx(sf_ctx *ctx, const double *x, const double *y, int64_t n, int
 /* compute_shot_descriptor, the reference's serial variant (shot.py:310-499; "debug only", not in descriptors.__all__):
  * per keypoint the gate `#(rho > 0) > min_neighborhood_size` (:360), the frame from the neighbours at NON-ZERO distance
  * only (:361-363 -- the keypoint and its duplicates neither weigh in the covariance normaliser nor vote), the ten
- * statements of sf_shot, and a row that is always L2-normalised (:496-497). */
+ * statements of sf_shot -- with sf_shot's order among neighbours at equal distance (ascending index in the caller's cloud
+ * array) -- and a row that is always L2-normalised (:496-497). */
 int sf_shot_serial(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, int64_t min_neighborhood_size, double *out /* m x 352 */,
                    int flags);
 /* sf_shot_serial with n_cosine_bins = n, the one bin count the reference lets a caller change (shot.py:316, 328): rows of 32 n

@@ -231,6 +231,9 @@ def shot_lrf(cloud, keypoints, radius):
 
 
 def shot(cloud, normals, keypoints, radius, lrf, normalize=True, min_neighborhood_size=100):
+    """compute_single_shot_descriptor per keypoint on the lists of radius_search.  The ten statements see the neighbours in ONE
+    order: ascending rho and, among bit-equal rho, ascending index in `cloud` (cmp_rho breaks ties by list position and the
+    lists ascend in index) -- the contract K5 is held to where the reference's np.argsort(rho) leaves the order open."""
     p, nrm, q = _f64(cloud), _f64(normals), _f64(keypoints)
     lrf = _f64(lrf).reshape(-1, 9)
     out = np.zeros((q.shape[0], 352))

@@ -71,7 +71,8 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
                                                  const int32_t *__restrict__ cnt, const int32_t *__restrict__ idx,
                                                  const int32_t *__restrict__ qrow, const shot_consts &K,
                                                  double *__restrict__ lrf, int normalize, int64_t min_nb,
-                                                 double *__restrict__ out, int64_t q, unsigned long long *slot)
+                                                 double *__restrict__ out, int64_t q, unsigned long long *slot,
+                                                 const shot_ties &ties)
 {
     // FUSED: `lrf` holds the raw axes written by k_shot_lrf(raw = 1); the sign votes (shot.py:40-45) are taken
     // here from the gathered neighbours and the finished frame is written back before it is used.
@@ -156,8 +157,12 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
     // conflicts of the random 8-byte atomics -- tools/pmc_k5.sh).  sX (352 slots) serves S1 (B), then S9 (G).
     unsigned long long *const sX = slot + 352;
     double *const acc = reinterpret_cast<double *>(slot);
-    constexpr unsigned long long SHOT_CLAIMED = ~0ull; // no rho has this bit pattern
+    // (a claimed sX slot holds its key with the sign bit set -- no rho has it -- so a second holder of that key knows what it met)
     constexpr unsigned WON_A = 1u << 28, WON_CD = 1u << 29, WON_EF = 1u << 30; // flags kept in bins1 (bit 31 = valid)
+    // bit 27: this neighbour met another holder of its winning key (shot_core.h); the wave reports the keypoint if any did.  (A bit
+    // of a register the chunk holds anyway: the scalar stream is what holds this kernel back, and a lane mask kept to the end is
+    // two scalar registers it lacks.)
+    constexpr unsigned MET = 1u << 27;
     shot_kept g[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -188,6 +193,7 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
                 f = WON_A;
                 if (shot_writes_cd(odd, other_shell)) f |= WON_CD;
                 if (shot_writes_ef(key, other_half, up)) f |= WON_EF;
+                if (key == other_half) f |= MET;
             }
             g[c].bins1 |= f;
         }
@@ -206,10 +212,12 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
             shot_weights(g[c], K, vA, v_cd[c], v_ef[c], adth);
             SF_K5_MARK(9, NCH);
             g[c].tdot = adth;
-            // compare-and-swap, not a plain store: two neighbours at exactly the same distance (duplicated points) hold the
-            // same key, and the ADDS below must come from one of them only (their values are equal; which one of two
-            // distinct equidistant neighbours writes last is undefined in the reference too)
-            if ((g[c].bins1 & WON_A) && atomicCAS(&sA[iA], key, tag_value(vA)) != key) g[c].bins1 &= ~(WON_A | WON_CD | WON_EF);
+            // compare-and-swap, not a plain store: two neighbours at exactly the same distance hold the same key, and the ADDS
+            // below must come from one of them only.  Their values differ unless they are one point named twice (another
+            // direction, another normal): the holder that finds the slot taken reports the tie, and the row is computed again
+            // under the full order (rho, caller index) by k_shot_tied
+            const bool lost = (g[c].bins1 & WON_A) && atomicCAS(&sA[iA], key, tag_value(vA)) != key;
+            if (lost) g[c].bins1 = (g[c].bins1 & ~WON_A) | MET; // (WON_CD / WON_EF are read under WON_A only)
         }
     }
     SF_SHOT_SYNC();
@@ -242,7 +250,9 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
                 const unsigned long long key = shot_key(g[c]);
                 const unsigned iW = stmt ? shot_slot_g<11>(g[c]) : shot_slot_b<11>(g[c]);
                 const double val = stmt ? g[c].tdot : fabs(g[c].dc); // S1's range mask is always true for cf in 0..10
-                if (atomicCAS(&sX[iW], key, SHOT_CLAIMED) == key && val != 0.0) unsafeAtomicAdd(&acc[iW], -val);
+                const unsigned long long was = atomicCAS(&sX[iW], key, shot_claimed(key));
+                if (was == key && val != 0.0) unsafeAtomicAdd(&acc[iW], -val);
+                if (was == shot_claimed(key)) g[c].bins1 |= MET;
             }
         }
         SF_SHOT_SYNC();
@@ -271,6 +281,10 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
         const int b = 2 * lane + 128 * u;
         if (b < 352) sf_store_stream2(o + b, __builtin_fma(vals[u].x, nscale, 0.0), __builtin_fma(vals[u].y, nscale, 0.0));
     }
+    unsigned met = 0u;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) met |= g[c].bins1;
+    if (__ballot((met & MET) != 0u) && lane == 0) shot_report_tie(ties, q);
 }
 
 
@@ -281,8 +295,9 @@ __device__ __forceinline__ void shot_cached_body(const double *__restrict__ rec,
 // fast path, S3/S4 and S6/S7 writers read off the S2 election), streamed: the list is swept three times, 128 neighbours in
 // flight -- (V) sign votes of the frame + the gate, (1) geometry -> the three elections (64-bit LDS atomic max on rho's bit
 // pattern for S2.., S1, S9), (2) geometry again -> weights -> every elected writer claims its (statement, bin) once (a bit
-// per slot: two neighbours at exactly the same distance hold the same key) and ADDS its value into a float64 accumulator
-// row with ds_add_f64.  LDS per wave: 3 x 352 keys + 352 accumulators + 3 x 352 claim bits = 11.4 KB.  A wave's LDS
+// per slot: two neighbours at exactly the same distance hold the same key; the second to come has met a tie, whose order is
+// (rho, caller index) -- the keypoint is reported and k_shot_tied computes its row, shot_core.h) and ADDS its value into a
+// float64 accumulator row with ds_add_f64.  LDS per wave: 3 x 352 keys + 352 accumulators + 3 x 352 claim bits = 11.4 KB.  A wave's LDS
 // instructions execute in program order and no two lanes of one instruction target the same slot (one claimed writer per
 // statement and bin), so every bit of the row is reproducible.  (Until round 4 this was `k_shot`, a two-sweep kernel on
 // libm's atan2 / acos with five election tables: 2.3x the time per neighbour of the cached form.)
@@ -304,7 +319,7 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
                                              const int32_t *__restrict__ qrow,
                                              int64_t m, shot_consts K, double *__restrict__ lrf, int normalize,
                                              int64_t min_nb, double *__restrict__ out, const int32_t *__restrict__ sel,
-                                             int64_t nsel, int64_t view_first, int lo)
+                                             int64_t nsel, int64_t view_first, int lo, shot_ties ties)
 {
     __shared__ __attribute__((aligned(16))) shot_long_lds lds_all[SF_SHOT_LONG_WPB];
     const int lane = threadIdx.x & 63;
@@ -384,9 +399,14 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
     }
     SF_SHOT_SYNC();
     // ---- sweep 2: every elected writer claims its slot and adds its value ----
-    auto claim = [&](int table, unsigned slot_) -> bool { // true for exactly one of the neighbours holding the winning key
+    // true for exactly one of the neighbours holding the winning key; another holder that comes later has met a tie (its
+    // values are its own: shot_core.h) and the row is computed again by k_shot_tied
+    bool tie = false;
+    auto claim = [&](int table, unsigned slot_) -> bool {
         const unsigned bit = 1u << (slot_ & 31u);
-        return (atomicOr(&L.claim[table][slot_ >> 5], bit) & bit) == 0u;
+        const bool first = (atomicOr(&L.claim[table][slot_ >> 5], bit) & bit) == 0u;
+        tie |= !first;
+        return first;
     };
     for (int t0 = 0; t0 < k; t0 += 128) {
         shot_kept g[2];
@@ -401,6 +421,7 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
                 const bool winB = L.keyB[iB] == key, winG = L.keyG[iG] == key;
                 double vA, v_cd, v_ef, adth;
                 shot_weights(g[u], K, vA, v_cd, v_ef, adth);
+                tie |= own == key && other_half == key;
                 if (own == key && claim(0, iA)) {
                     unsafeAtomicAdd(&L.acc[iA], vA);
                     if (shot_writes_cd(iA & 1u, other_shell) && v_cd != 0.0) unsafeAtomicAdd(&L.acc[iA ^ 1u], v_cd);
@@ -430,6 +451,7 @@ __global__ __launch_bounds__(64 * SF_SHOT_LONG_WPB) void k_shot_long(const doubl
         const int b = lane + 64 * u;
         if (b < 352) sf_store_stream(o + b, vals[u] * scale);
     }
+    if (__ballot(tie) && lane == 0) shot_report_tie(ties, q);
 }
 
 template <int NCH, bool FUSED>
@@ -440,7 +462,8 @@ __global__ __launch_bounds__(64 * SF_SHOT_WPB) void k_shot_cached(const double *
                                                     const int32_t *__restrict__ qrow,
                                                     int64_t m, shot_consts K, double *__restrict__ lrf,
                                                     int normalize, int64_t min_nb, double *__restrict__ out, int limit,
-                                                    const int32_t *__restrict__ sel, int64_t nsel, int64_t view_first)
+                                                    const int32_t *__restrict__ sel, int64_t nsel, int64_t view_first,
+                                                    shot_ties ties)
 {
     __shared__ __attribute__((aligned(16))) unsigned long long slots[SF_SHOT_WPB][704];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -454,10 +477,10 @@ __global__ __launch_bounds__(64 * SF_SHOT_WPB) void k_shot_cached(const double *
     // has one of 160+), but nearly every keypoint fits one chunk less: a wave-uniform branch picks the body that
     // matches THIS keypoint, so the gather, votes and distance tests of an empty last chunk are never issued.
     if (NCH >= 3 && sf_uniform(cnt[q]) <= 64 * (NCH - 1)) {
-        shot_cached_body<(NCH >= 3 ? NCH - 1 : NCH), FUSED>(rec, qx, qy, qz, offset, cnt, idx, qrow, K, lrf, normalize, min_nb, out, q, slot);
+        shot_cached_body<(NCH >= 3 ? NCH - 1 : NCH), FUSED>(rec, qx, qy, qz, offset, cnt, idx, qrow, K, lrf, normalize, min_nb, out, q, slot, ties);
         return;
     }
-    shot_cached_body<NCH, FUSED>(rec, qx, qy, qz, offset, cnt, idx, qrow, K, lrf, normalize, min_nb, out, q, slot);
+    shot_cached_body<NCH, FUSED>(rec, qx, qy, qz, offset, cnt, idx, qrow, K, lrf, normalize, min_nb, out, q, slot, ties);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -467,9 +490,11 @@ __global__ __launch_bounds__(64 * SF_SHOT_WPB) void k_shot_cached(const double *
 // ONE gather, the geometry evaluated ONCE (the streaming form evaluates it twice, once to elect and once to add, because no
 // single wave can keep 12 registers per chunk for a list of any length), the election tables are the workgroup's.  All three
 // elections (S2.., S1, S9) run in one phase on three key tables; the winners then replace their key by their value (one
-// compare-and-swap claims the slot and stores: duplicated points hold the same key) and the S3/S4 and S6/S7 writers store
-// into a value table of their own (two addends per slot at most: commutative), so the row is the sum of the four tables in a
-// fixed order -- every bit of it independent of how the waves were scheduled and of the team's size.  Four
+// compare-and-swap claims the slot and stores) and the S3/S4 and S6/S7 writers store into a value table of their own (two
+// addends per slot at most: commutative), so the row is the sum of the four tables in a fixed order -- every bit of it
+// independent of how the waves were scheduled and of the team's size AS LONG AS no two neighbours hold the same winning key:
+// which of two such holders claims first is a race between waves.  The one that finds the slot taken raises a flag, the
+// keypoint is reported and k_shot_tied computes its row under the order (rho, caller index) -- shot_core.h.  Four
 // workgroup barriers per keypoint.  LDS: 4 x 352 x 8 B + 256 B = 11.3 KB per team.
 // --------------------------------------------------------------------------------------------------
 #ifndef SF_TEAM_NCH
@@ -478,7 +503,7 @@ __global__ __launch_bounds__(64 * SF_SHOT_WPB) void k_shot_cached(const double *
 struct shot_team_lds {
     unsigned long long keyA[352], keyB[352], keyG[352]; // keys (rho's bit pattern), then tagged values: S2+S5+S8+S10, S1, S9
     double vx[352];                                      // S3/S4 + S6/S7 by destination bin (two addends at most: see below)
-    __attribute__((aligned(16))) int red[16][4];         // per wave: gate count and the two sign votes
+    __attribute__((aligned(16))) int red[16][4];         // per wave: gate count and the two sign votes; [0][3]: a tie was met
 };
 
 template <int NCH, int NW, bool FUSED>
@@ -489,7 +514,7 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
                                                        int64_t m, shot_consts K, double *__restrict__ lrf, int normalize,
                                                        int64_t min_nb, double *__restrict__ out,
                                                        const int32_t *__restrict__ sel, int64_t nsel, int64_t view_first,
-                                                       int lo)
+                                                       int lo, shot_ties ties)
 {
     __shared__ __attribute__((aligned(16))) shot_team_lds L;
     const int lane = threadIdx.x & 63;
@@ -544,6 +569,7 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
         L.red[wave][0] = npos;
         L.red[wave][1] = xneg;
         L.red[wave][2] = zneg;
+        L.red[wave][3] = 0;
     }
     __syncthreads(); // the cleared tables, the waves' counts
     npos = xneg = zneg = 0;
@@ -568,6 +594,7 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
         return;
     }
     constexpr unsigned WON_B = 1u << 26, WON_G = 1u << 27, WON_A = 1u << 28, WON_CD = 1u << 29, WON_EF = 1u << 30;
+    constexpr unsigned TIE = 1u << 25; // this lane met another holder of its winning key (shot_core.h)
     // ---- the three elections ----
     shot_kept g[NCH];
 #pragma unroll
@@ -594,6 +621,7 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
                 f = WON_A;
                 if (shot_writes_cd(odd, other_shell)) f |= WON_CD;
                 if (shot_writes_ef(key, other_half, up)) f |= WON_EF;
+                if (other_half == key) f |= TIE;
             }
             if (L.keyB[shot_slot_b<11>(g[c])] == key) f |= WON_B;
             if (L.keyG[shot_slot_g<11>(g[c])] == key) f |= WON_G;
@@ -610,14 +638,22 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
             double vA, v_cd, v_ef, adth;
             shot_weights(g[c], K, vA, v_cd, v_ef, adth);
             const unsigned f = g[c].bins1;
-            if ((f & WON_A) && atomicCAS(&L.keyA[iA], key, tag_value(vA)) == key) {
-                // (a bin receives at most one S3/S4 value -- from the winner of bin ^ 1 -- and one S6/S7 value -- from the winner
-                // of bin ^ 2: two addends into a slot that starts at +0 give the same sum in either order)
-                if ((f & WON_CD) && v_cd != 0.0) unsafeAtomicAdd(&L.vx[iA ^ 1u], v_cd);
-                if ((f & WON_EF) && v_ef != 0.0) unsafeAtomicAdd(&L.vx[iA ^ 2u], v_ef);
+            // (a holder of a winning key whose compare-and-swap finds the slot taken has met a tie: which of the two got there
+            // first is a race between waves, and the row is computed again under the full order by k_shot_tied)
+            bool met = f & TIE;
+            if (f & WON_A) {
+                if (atomicCAS(&L.keyA[iA], key, tag_value(vA)) == key) {
+                    // (a bin receives at most one S3/S4 value -- from the winner of bin ^ 1 -- and one S6/S7 value -- from the
+                    // winner of bin ^ 2: two addends into a slot that starts at +0 give the same sum in either order)
+                    if ((f & WON_CD) && v_cd != 0.0) unsafeAtomicAdd(&L.vx[iA ^ 1u], v_cd);
+                    if ((f & WON_EF) && v_ef != 0.0) unsafeAtomicAdd(&L.vx[iA ^ 2u], v_ef);
+                } else {
+                    met = true;
+                }
             }
-            if (f & WON_B) atomicCAS(&L.keyB[shot_slot_b<11>(g[c])], key, tag_value(fabs(g[c].dc)));
-            if (f & WON_G) atomicCAS(&L.keyG[shot_slot_g<11>(g[c])], key, tag_value(adth));
+            if (f & WON_B) met |= atomicCAS(&L.keyB[shot_slot_b<11>(g[c])], key, tag_value(fabs(g[c].dc))) != key;
+            if (f & WON_G) met |= atomicCAS(&L.keyG[shot_slot_g<11>(g[c])], key, tag_value(adth)) != key;
+            if (met) L.red[0][3] = 1;
         }
     }
     __syncthreads();
@@ -625,6 +661,7 @@ __global__ __launch_bounds__(64 * NW) void k_shot_team(const double *__restrict_
     //      with three writers, each repeating the sums and the norm for a third of the stores, the launch took 6 % longer --
     //      the team is bound by the vector instructions it issues, like the cached form) ----
     if (wave != 0) return;
+    if (L.red[0][3] && lane == 0) shot_report_tie(ties, q);
     double2 vals[3];
     double ss = 0.0;
 #pragma unroll
@@ -666,15 +703,20 @@ static int launch_shot_as(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double *dlrf, i
     const int64_t min_nb = nmin;
     const sf_dispatch d = sf_nbrs_dispatch(nb);
     const int32_t *const none = nullptr;
+    // neighbours at equal distance: every form reports the keypoints whose elections met one, k_shot_tied computes their rows
+    // again under the order (rho, caller index) -- shot_core.h
+    sf_pool_guard tmp(ctx);
+    shot_ties ties;
+    SF_CHECK(sf_shot_ties_begin(ctx, tmp, m, &ties));
     const dim3 block(64 * SF_SHOT_WPB), block_streaming(64 * SF_SHOT_LONG_WPB);
 #define SF_SHOT_ARGS c->rec, nb->qx, nb->qy, nb->qz, nb->offset, nb->count, nb->idx, nb->qrow, m, K, dlrf, normalize, min_nb, dout
     // the cached form over all m (sel = none) or over a selection; the streaming form likewise; the team of NW waves
 #define SF_SHOT_CACHED(NAME, N, COUNT, LIMIT, SELP)                                                                  \
-    SF_LAUNCH(ctx, NAME, (k_shot_cached<N, FUSED>), dim3(sf_xcd_grid(sf_div_up(COUNT, SF_SHOT_WPB))), block, SF_SHOT_ARGS, LIMIT, SELP, (int64_t)(COUNT), d.view_first)
+    SF_LAUNCH(ctx, NAME, (k_shot_cached<N, FUSED>), dim3(sf_xcd_grid(sf_div_up(COUNT, SF_SHOT_WPB))), block, SF_SHOT_ARGS, LIMIT, SELP, (int64_t)(COUNT), d.view_first, ties)
 #define SF_SHOT_STREAM(NAME, SEL, COUNT, SELP, LO)                                                                    \
-    SF_LAUNCH(ctx, NAME, (k_shot_long<FUSED, SEL>), dim3(sf_xcd_grid(sf_div_up(COUNT, SF_SHOT_LONG_WPB))), block_streaming, SF_SHOT_ARGS, SELP, (int64_t)(COUNT), d.view_first, LO)
+    SF_LAUNCH(ctx, NAME, (k_shot_long<FUSED, SEL>), dim3(sf_xcd_grid(sf_div_up(COUNT, SF_SHOT_LONG_WPB))), block_streaming, SF_SHOT_ARGS, SELP, (int64_t)(COUNT), d.view_first, LO, ties)
 #define SF_SHOT_TEAM(NW)                                                                                              \
-    SF_LAUNCH(ctx, "k5_shot_tail", (k_shot_team<SF_TEAM_NCH, NW, FUSED>), dim3(sf_xcd_grid(d.n_tail)), dim3(64 * NW), SF_SHOT_ARGS, d.tail_sel, d.n_tail, d.view_first, 255)
+    SF_LAUNCH(ctx, "k5_shot_tail", (k_shot_team<SF_TEAM_NCH, NW, FUSED>), dim3(sf_xcd_grid(d.n_tail)), dim3(64 * NW), SF_SHOT_ARGS, d.tail_sel, d.n_tail, d.view_first, 255, ties)
     if (d.chunks == 1) { SF_SHOT_CACHED("k5_shot", 1, m, d.limit, none); }
     else if (d.chunks == 2) { SF_SHOT_CACHED("k5_shot", 2, m, d.limit, none); }
     else if (d.chunks == 3) { SF_SHOT_CACHED("k5_shot", 3, m, d.limit, none); }
@@ -698,7 +740,7 @@ static int launch_shot_as(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double *dlrf, i
 #undef SF_SHOT_STREAM
 #undef SF_SHOT_CACHED
 #undef SF_SHOT_ARGS
-    return SF_OK;
+    return sf_shot_ties_finish<11>(ctx, c, nb, K, dlrf, FUSED, 11, normalize, dout, ties);
 }
 
 static int launch_shot(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, double *dlrf, int normalize, int64_t min_nb, double *dout, bool fused)

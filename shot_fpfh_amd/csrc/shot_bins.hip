@@ -8,10 +8,11 @@
 // four tables of 32 n 8-byte slots -- the keys of the S2+S5+S8+S10 (A), S1 (B) and S9 (G) elections, later their tagged values,
 // and vx, the S3/S4 + S6/S7 addends by destination bin -- 1 KiB x n, 64 KiB at n = 64; the waves per workgroup follow from n
 // (shot_bins_waves).  Three sweeps over the list, each recomputing the geometry (no wave can keep a list of any length in
-// registers): (1) the three elections (64-bit LDS atomic max on rho's bit pattern) and the gate count; (2) every winner of A
-// claims its slot -- compare-and-swap of its key into the key with the sign bit set, which the other winners of the quad still
-// read as that key -- and adds its S3/S4, S6/S7 values into vx, the winners of B and G replace their key by their tagged
-// value; (3) the claimed A slots receive their tagged value.  The row is ((A + vx) + B) + G per bin in that fixed order: vx
+// registers): (1) the three elections (64-bit LDS atomic max on rho's bit pattern) and the gate count; (2) every winner of A, B
+// and G claims its slot -- compare-and-swap of its key into the key with the sign bit set, which the other winners of the quad
+// still read as that key, and which tells a second holder of that key that it has met a tie (shot_core.h: the keypoint is
+// reported and its row computed again by k_shot_tied) -- and the winner of A adds its S3/S4, S6/S7 values into vx; (3) the
+// claimed slots receive their tagged value.  The row is ((A + vx) + B) + G per bin in that fixed order: vx
 // receives two addends at most (from the winners of bin ^ 1 and bin ^ 2), so every bit of the row is independent of the
 // order of the atomics, and at n = 11 the sums equal the team form's (k_shot_team) bin for bin.
 // HBM roofline, algorithmic bytes: the 256 n B row + 24 B keypoint + 72 B frame per keypoint, plus the list (4 B per entry)
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
                                                    const int64_t *__restrict__ offset, const int32_t *__restrict__ cnt,
                                                    const int32_t *__restrict__ idx, const int32_t *__restrict__ qrow, int64_t m,
                                                    shot_consts K, const double *__restrict__ lrf, int n, int min_nb,
-                                                   double *__restrict__ out, int *__restrict__ err)
+                                                   double *__restrict__ out, int *__restrict__ err, shot_ties ties)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned long long shot_bins_lds[];
     const int lane = threadIdx.x & 63;
@@ -89,7 +90,8 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
     }
     SF_SHOT_SYNC();
 
-    // ---- sweep 2: A claimed (key -> key | sign), S3/S4 and S6/S7 added into vx; B and G resolved ----
+    // ---- sweep 2: A, B and G claimed (key -> key | sign), S3/S4 and S6/S7 added into vx ----
+    bool tie = false;
     for (int t0 = 0; t0 < k; t0 += 128) {
         shot_kept g[2];
         unsigned long long pos[2], over[2];
@@ -103,18 +105,23 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
                 const unsigned long long own = keyA[iA], other_shell = keyA[iA ^ 1u], other_half = keyA[iA ^ 2u] & ~SHOT_BINS_SIGN;
                 double vA, v_cd, v_ef, adth;
                 shot_weights(g[u], K, vA, v_cd, v_ef, adth);
-                if (own == key && atomicCAS(&keyA[iA], key, key | SHOT_BINS_SIGN) == key) {
-                    if (shot_writes_cd(iA & 1u, other_shell) && v_cd != 0.0) unsafeAtomicAdd(&vx[iA ^ 1u], v_cd);
-                    if (shot_writes_ef(key, other_half, iA & 2u) && v_ef != 0.0) unsafeAtomicAdd(&vx[iA ^ 2u], v_ef);
+                if ((own & ~SHOT_BINS_SIGN) == key) {
+                    tie |= other_half == key;
+                    if (atomicCAS(&keyA[iA], key, shot_claimed(key)) == key) {
+                        if (shot_writes_cd(iA & 1u, other_shell) && v_cd != 0.0) unsafeAtomicAdd(&vx[iA ^ 1u], v_cd);
+                        if (shot_writes_ef(key, other_half, iA & 2u) && v_ef != 0.0) unsafeAtomicAdd(&vx[iA ^ 2u], v_ef);
+                    } else {
+                        tie = true; // (another holder of this key was here first)
+                    }
                 }
-                atomicCAS(&keyB[shot_slot_b<0>(g[u])], key, tag_value(fabs(g[u].dc)));
-                atomicCAS(&keyG[shot_slot_g<0>(g[u])], key, tag_value(adth));
+                tie |= atomicCAS(&keyB[shot_slot_b<0>(g[u])], key, shot_claimed(key)) == shot_claimed(key);
+                tie |= atomicCAS(&keyG[shot_slot_g<0>(g[u])], key, shot_claimed(key)) == shot_claimed(key);
             }
         }
     }
     SF_SHOT_SYNC();
 
-    // ---- sweep 3: the claimed A slots receive their value ----
+    // ---- sweep 3: the claimed slots receive their value ----
     for (int t0 = 0; t0 < k; t0 += 128) {
         shot_kept g[2];
         unsigned long long pos[2], over[2];
@@ -123,11 +130,14 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
         for (int u = 0; u < 2; ++u) {
             if (g[u].bins1 >> 31) {
                 const unsigned long long claimed = shot_key(g[u]) | SHOT_BINS_SIGN;
-                const unsigned iA = shot_slot_a<0>(g[u]);
-                if (keyA[iA] == claimed) {
+                const unsigned iA = shot_slot_a<0>(g[u]), iB = shot_slot_b<0>(g[u]), iG = shot_slot_g<0>(g[u]);
+                const bool wA = keyA[iA] == claimed, wB = keyB[iB] == claimed, wG = keyG[iG] == claimed;
+                if (wA || wB || wG) {
                     double vA, v_cd, v_ef, adth;
                     shot_weights(g[u], K, vA, v_cd, v_ef, adth);
-                    atomicCAS(&keyA[iA], claimed, tag_value(vA));
+                    if (wA) atomicCAS(&keyA[iA], claimed, tag_value(vA));
+                    if (wB) atomicCAS(&keyB[iB], claimed, tag_value(fabs(g[u].dc)));
+                    if (wG) atomicCAS(&keyG[iG], claimed, tag_value(adth));
                 }
             }
         }
@@ -145,6 +155,7 @@ __global__ __launch_bounds__(256) void k_shot_bins(const double *__restrict__ re
         const double v = ((shot_untag(keyA[b]) + vx[b]) + shot_untag(keyB[b])) + shot_untag(keyG[b]);
         sf_store_stream(o + b, v * scale);
     }
+    if (__ballot(tie) && lane == 0) shot_report_tie(ties, q);
 }
 
 } // namespace
@@ -177,14 +188,17 @@ extern "C" int sf_shot_serial_bins(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, int64_
     shot_consts K;
     int nmin;
     SF_CHECK(sf_shot_consts(ctx, nb->radius, min_nb, &K, &nmin)); // (the coefficients: once per context; K5 shares them)
+    shot_ties ties;
+    SF_CHECK(sf_shot_ties_begin(ctx, guard, m, &ties));
     if (m) {
         const int w = shot_bins_waves(n);
         const size_t lds = (size_t)w * 4 * row * sizeof(unsigned long long);
         sf_launch_timer t_(ctx, "k5_shot_bins");
         hipLaunchKernelGGL(k_shot_bins, dim3(sf_xcd_grid(sf_div_up(m, w))), dim3(64 * w), lds, ctx->stream, c->rec, nb->qx, nb->qy,
-                           nb->qz, nb->offset, nb->count, nb->idx, nb->qrow, m, K, (const double *)dlrf, n, nmin, dout, derr);
+                           nb->qz, nb->offset, nb->count, nb->idx, nb->qrow, m, K, (const double *)dlrf, n, nmin, dout, derr, ties);
         SF_HIP(hipGetLastError());
     }
+    if (m) SF_CHECK(sf_shot_ties_finish<0>(ctx, c, nb, K, dlrf, false, n, 1, dout, ties));
     SF_CHECK(finish_out(ctx, out, (size_t)m * row, flags, dout));
     int herr = 0;
     SF_HIP(hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));

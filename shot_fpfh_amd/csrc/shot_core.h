@@ -402,9 +402,10 @@ __device__ inline bool shot_geometry(double cx, double cy, double cz, double d2,
 // Who writes what, from the A keys read back after the election: the neighbour's own, the one of the other radial shell
 // (slot ^ 1) and of the other half-space (slot ^ 2).  The winner of A (own == key) also writes S3/S4 when it is the farthest of
 // its cell over BOTH shells -- every rho of the outer shell (odd) exceeds every rho of the inner one -- and S6/S7 when it is the
-// farther of the two half-spaces' winners; equal distances there are undefined in the reference (unstable argsort,
-// shot.py:218): z > 0 (up) here.  The forms that hold their neighbours in registers keep the answers as flags of bins1, the
-// streamed forms ask where they add.
+// farther of the two half-spaces' winners.  Equal distances there are a tie like any other (the larger caller index writes
+// last): the body that sees `key == other_half` reports the keypoint and k_shot_tied computes the row, so what this rule
+// answers on equality (z > 0) never reaches a caller.  The forms that hold their neighbours in registers keep the answers as
+// flags of bins1, the streamed forms ask where they add.
 __device__ inline bool shot_writes_cd(bool odd, unsigned long long other_shell) { return odd || other_shell == 0ull; }
 __device__ inline bool shot_writes_ef(unsigned long long key, unsigned long long other_half, bool up)
 {
@@ -509,6 +510,136 @@ __device__ inline double shot_row_scale(double ss, int normalize, bool negated)
     return nrm > 0.0 ? (normalize ? (negated ? -inv_nrm : inv_nrm) : (negated ? -1.0 : 1.0)) : (negated ? -0.0 : 0.0);
 }
 
+// ---- neighbours at EQUAL distance -----------------------------------------------------------------------------------------
+// The contract: the ten statements see the neighbours at non-zero distance in ONE total order -- ascending rho,
+// and among bit-equal rho ascending index in the caller's cloud array -- so the last writer of a bin is the farthest neighbour
+// and, among equally far ones, the one with the largest caller index, in all ten statements alike.  The elections of the four
+// bodies above compare rho alone; two holders of a winning key are told apart by whoever reaches the slot first.  So every body
+// NOTICES such a meeting where it costs nothing -- the compare-and-swap or claim of a holder that finds the slot taken by another
+// holder of its own key, and the comparison of the two half-spaces' winners that comes out equal -- and reports the keypoint
+// (shot_report_tie); its row is then computed again by k_shot_tied, which holds the full order (rho, caller index) in every
+// election.  A list without such a meeting takes the same instructions as before plus the tests of a wave-uniform flag; a list
+// with one is walked nine more times by one wave (three tables, three sweeps each): what a tie costs.
+// Which rows are computed again depends on the list alone (a tie either stands in it or does not), not on who won the race.
+// (one pointer: the count, then the list -- every register a launch argument holds to the kernel's end is one the register-cached
+// forms do not have; the list has room for the call's m keypoints, and a keypoint is reported at most once)
+struct shot_ties {
+    int32_t *buf; // [0]: how many keypoints were reported; [1 + i]: the i-th of them (processing slot)
+};
+__device__ inline unsigned long long shot_claimed(unsigned long long key) { return key | 0x8000000000000000ull; }
+// (one lane of the wave -- of the team -- that served keypoint q calls this once)
+__device__ inline void shot_report_tie(const shot_ties &T, int64_t q)
+{
+    T.buf[1 + atomicAdd(T.buf, 1)] = (int32_t)q;
+}
+
+// Rows of the reported keypoints under the full order.  One wave per keypoint, the list streamed 128 neighbours at a time, per
+// table T = A (S2+S5+S8+S10, and S3/S4, S6/S7 off it), B (S1), G (S9) three sweeps: (a) the largest rho of every slot, (b) among
+// the holders of that rho the largest caller index (perm[] of the cell-sorted position), (c) the one neighbour that holds both
+// claims the slot (a bit: a list that was imported may name a point twice, both entries carry equal values) and writes.  S3/S4
+// and S6/S7 go to vx as in the team form; between the half-spaces the pair (rho, index) decides.  The row is ((A + vx) + B) + G
+// per bin in that order, whatever the order of the list: bit-identical however the keypoint is served.
+// LDS per wave, S = 32 n slots: key (8 B), row (8 B), vx (8 B), top (4 B) per slot, S / 32 claim words.
+// N: 11, or 0 for a run-time count n.  fused: the frames at `lrf` were written by a fused body, which leaves a frame that no vote
+// flipped as K4 stored it and reads a y component of -0 as +0 (shot_finish_frame).
+__host__ __device__ inline size_t shot_tied_words(int n) { return (size_t)112 * n + (size_t)((n + 1) >> 1); } // 8-byte words
+template <int N>
+__global__ __launch_bounds__(256) void k_shot_tied(const double *__restrict__ rec, const int32_t *__restrict__ perm,
+                                                   const double *__restrict__ qx, const double *__restrict__ qy,
+                                                   const double *__restrict__ qz, const int64_t *__restrict__ offset,
+                                                   const int32_t *__restrict__ cnt, const int32_t *__restrict__ idx,
+                                                   const int32_t *__restrict__ qrow, int64_t m, shot_consts K,
+                                                   const double *__restrict__ lrf, int fused, int n_, int normalize,
+                                                   double *__restrict__ out, shot_ties T)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long shot_tied_lds[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nw = blockDim.x >> 6;
+    const int n = N ? N : n_;
+    const double nd = (double)n;
+    const int S = 32 * n;
+    unsigned long long *const key = shot_tied_lds + shot_tied_words(n) * wave;
+    double *const rowv = reinterpret_cast<double *>(key + S);
+    double *const vx = rowv + S;
+    unsigned *const top = reinterpret_cast<unsigned *>(vx + S);
+    unsigned *const claim = top + S;
+    int64_t nt = sf_uniform(T.buf[0]);
+    nt = nt < m ? nt : m; // (one entry per keypoint at most: never more than m)
+    for (int64_t t = (int64_t)blockIdx.x * nw + wave; t < nt; t += (int64_t)gridDim.x * nw) {
+        const int64_t q = sf_uniform(T.buf[1 + t]);
+        if (q < 0 || q >= m) continue;
+        const int64_t s = offset[q];
+        const int k = sf_uniform(cnt[q]);
+        const int64_t row = qrow ? qrow[q] : q;
+        double *o = out + (int64_t)S * row;
+        const double px = qx[q], py = qy[q], pz = qz[q];
+        double E[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) E[i] = lrf[9 * row + i];
+        if (fused) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) E[3 * i + 1] = E[3 * i + 1] == 0.0 ? 0.0 : E[3 * i + 1];
+        }
+        for (int b = lane; b < 2 * S; b += 64) rowv[b] = 0.0; // (row and vx)
+        // one sweep: f(geometry, caller index + 1) for every neighbour at non-zero distance whose bins are in range
+        auto sweep = [&](auto f) {
+            for (int t0 = 0; t0 < k; t0 += 128) {
+                shot_kept g[2];
+                unsigned long long pos[2], over[2];
+                shot_geometry128<N, false>(rec, idx + s, t0, k, lane, px, py, pz, E, K.half_r, n, nd, g, pos, over);
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    if (g[u].bins1 >> 31) f(g[u], (unsigned)perm[idx[s + t0 + 64 * u + lane]] + 1u);
+            }
+        };
+        for (int table = 0; table < 3; ++table) {
+            auto slot_of = [&](const shot_kept &g) {
+                return table == 0 ? shot_slot_a<N>(g) : (table == 1 ? shot_slot_b<N>(g) : shot_slot_g<N>(g));
+            };
+            for (int b = lane; b < S; b += 64) { key[b] = 0ull; top[b] = 0u; }
+            for (int b = lane; b < n; b += 64) claim[b] = 0u;
+            SF_SHOT_SYNC();
+            sweep([&](const shot_kept &g, unsigned me) { atomicMax(&key[slot_of(g)], shot_key(g)); });
+            SF_SHOT_SYNC();
+            sweep([&](const shot_kept &g, unsigned me) {
+                const unsigned i = slot_of(g);
+                if (key[i] == shot_key(g)) atomicMax(&top[i], me);
+            });
+            SF_SHOT_SYNC();
+            sweep([&](const shot_kept &g, unsigned me) {
+                const unsigned i = slot_of(g);
+                const unsigned long long mine = shot_key(g);
+                if (key[i] != mine || top[i] != me) return;
+                const unsigned bit = 1u << (i & 31u);
+                if (atomicOr(&claim[i >> 5], bit) & bit) return; // (the same point named twice)
+                double vA, v_cd, v_ef, adth;
+                shot_weights(g, K, vA, v_cd, v_ef, adth);
+                if (table == 0) { // (bit 1 of a slot: z > 0, bit 0: outer shell)
+                    rowv[i] = vA;
+                    const unsigned long long other_half = key[i ^ 2u];
+                    const bool far = mine > other_half || (mine == other_half && me > top[i ^ 2u]);
+                    if (shot_writes_cd(i & 1u, key[i ^ 1u]) && v_cd != 0.0) unsafeAtomicAdd(&vx[i ^ 1u], v_cd);
+                    if (far && v_ef != 0.0) unsafeAtomicAdd(&vx[i ^ 2u], v_ef);
+                } else {
+                    const double v = table == 1 ? fabs(g.dc) : adth;
+                    if (v != 0.0) rowv[i] += v; // (one writer per slot)
+                }
+            });
+            SF_SHOT_SYNC();
+            if (table == 0) {
+                for (int b = lane; b < S; b += 64) rowv[b] += vx[b];
+                SF_SHOT_SYNC();
+            }
+        }
+        double ss = 0.0;
+        for (int b = lane; b < S; b += 64) ss += rowv[b] * rowv[b];
+        const double scale = shot_row_scale(ss, normalize, false);
+        for (int b = lane; b < S; b += 64) sf_store_stream(o + b, rowv[b] * scale);
+        SF_SHOT_SYNC();
+    }
+}
+
 // ---- host: what every K5 launch is given ----
 // The radius-derived constants as the reference's own expressions (shot.py:95-117, 235), the polynomial coefficients (uploaded
 // once per context), and min_nb clamped into [-1, 2^31 - 1]: a list holds fewer than 2^31 points, so "more than min_nb
@@ -521,6 +652,29 @@ static inline int sf_shot_consts(sf_ctx *ctx, double r_, int64_t min_nb, shot_co
     }
     *K = shot_consts{r_, r_ / 2, r_ / 4, r_ * 3 / 4, 1.0 / (r_ / 2), ctx->shot_coef};
     *min_nb32 = (int)std::min<int64_t>(std::max<int64_t>(min_nb, -1), 2147483647LL);
+    return SF_OK;
+}
+
+// The report list of one call's K5 launches (m entries and the counter, zeroed), and the launch that computes the reported rows
+// again (k_shot_tied; n: cosine bins at run time when N = 0).  The launch is unconditional -- the count stays on the device --
+// and small: its waves walk the report list in strides and end at once when it is empty.
+static inline int sf_shot_ties_begin(sf_ctx *ctx, sf_pool_guard &guard, int64_t m, shot_ties *T)
+{
+    SF_CHECK(guard.alloc(&T->buf, (size_t)m + 1));
+    SF_HIP(hipMemsetAsync(T->buf, 0, sizeof(int32_t), ctx->stream));
+    return SF_OK;
+}
+template <int N>
+static inline int sf_shot_ties_finish(sf_ctx *ctx, sf_cloud *c, sf_nbrs *nb, const shot_consts &K, const double *dlrf, bool fused,
+                                      int n, int normalize, double *dout, const shot_ties &T)
+{
+    const int w = n <= 16 ? 4 : (n <= 32 ? 2 : 1); // waves per workgroup: at most 57.6 KB of LDS
+    const size_t lds = (size_t)w * shot_tied_words(n) * sizeof(unsigned long long);
+    const int64_t blocks = std::min<int64_t>(sf_div_up(nb->m, w), 1024);
+    sf_launch_timer t_(ctx, "k5_shot_ties");
+    hipLaunchKernelGGL(k_shot_tied<N>, dim3((unsigned)blocks), dim3(64 * w), lds, ctx->stream, c->rec, (const int32_t *)c->perm, nb->qx,
+                       nb->qy, nb->qz, nb->offset, nb->count, nb->idx, nb->qrow, nb->m, K, dlrf, (int)fused, n, normalize, dout, T);
+    SF_HIP(hipGetLastError());
     return SF_OK;
 }
 

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import FAMILIES, _unit, family, load_golden
+from shot_ties_numpy import edge_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -149,10 +150,42 @@ def test_normals_and_pca_vs_oracle(eng, O, name, seed):
             assert np.abs(nk - nk_o)[simple_k].max() < 1e-6
 
 
+def _eigen_gaps(p, kp, off, idx, r):
+    """Smallest relative gap between two eigenvalues of every keypoint's weighted covariance (shot.py:27-36); 0 for an empty list."""
+    gaps = np.zeros(len(kp))
+    for i in range(len(kp)):
+        d = p[idx[off[i]:off[i + 1]]] - kp[i]
+        w = r - np.linalg.norm(d, axis=1)
+        if len(d) and w.sum() > 0:
+            ev = np.linalg.eigvalsh(d.T @ (d * w[:, None]) / w.sum())
+            gaps[i] = np.diff(ev).min() / max(ev[2], 1e-300)
+    return gaps
+
+
+def _edge_margins(p, nr, kp, off, idx, frames, r):
+    """Per keypoint, how far its neighbours' bin-deciding quantities stay from their edges (shot_ties_numpy.edge_margin)."""
+    out = np.zeros(len(kp))
+    for i in range(len(kp)):
+        d = p[idx[off[i]:off[i + 1]]] - kp[i]
+        rho = np.linalg.norm(d, axis=1)
+        if not (rho > 0).any():
+            continue
+        loc = (d @ frames[i])[rho > 0]
+        cpos = (np.clip(nr[idx[off[i]:off[i + 1]]] @ frames[i][:, 2], -1, 1)[rho > 0] + 1.0) * 11 / 2.0 - 0.5
+        out[i] = edge_margin(dict(local=loc, rho=rho[rho > 0], cos_bin_pos=cpos), r)
+    return out
+
+
 @pytest.mark.parametrize("seed", SEEDS)
-@pytest.mark.parametrize("name", ["uniform", "clustered", "rough_plane", "far_origin"])
+@pytest.mark.parametrize("name", ["uniform", "clustered", "rough_plane", "far_origin", "lattice", "duplicates"])
 def test_shot_vs_oracle(eng, O, name, seed):
-    """parallel (frame from the full support) and serial (frame without the keypoint) SHOT, random settings"""
+    """parallel (frame from the full support) and serial (frame without the keypoint) SHOT, random settings.  The lattice and
+    the duplicates hold neighbours at equal distance in every list: the oracle breaks such ties by the caller's index, and so
+    does K5.  On the full lattice nearly every support is symmetric -- two or three equal eigenvalues, a frame
+    that is LAPACK's rounding -- and where it is not, the frame lies along the lattice and puts the neighbours ON the bin edges,
+    where the last bit of an eigenvector decides.  So there every row is compared on seeded rotations handed in, and the rows on
+    the engine's own frames only where the frame is defined and no neighbour is within 1e-9 of an edge (the keypoints off the
+    lattice, mostly)."""
     from shot_fpfh_amd.descriptors import ShotMultiprocessor
     from shot_fpfh_amd.descriptors.shot import compute_shot_descriptor
 
@@ -170,7 +203,23 @@ def test_shot_vs_oracle(eng, O, name, seed):
         assert np.array_equal(got.any(axis=1), want.any(axis=1)), f"{name}: gate differs (r={r}, mn={mn})"
         # a support of fewer than 4 points spans no frame (two eigenvalues are zero: any basis of their plane is "the"
         # eigenvectors), so with a permissive gate such rows are whatever LAPACK's rounding makes them
-        framed = np.diff(O.radius_search(p, kp, r)[0]) >= 5
+        off, idx = O.radius_search(p, kp, r)
+        framed = np.diff(off) >= 5
+        if name == "lattice":
+            framed &= _eigen_gaps(p, kp, off, idx, r) >= 1e-6
+            framed &= _edge_margins(p, nr, kp, off, idx, O.shot_lrf(p, kp, r), r) > 1e-9
+            q, rr = np.linalg.qr(rng.standard_normal((len(kp), 3, 3)))
+            frames = np.ascontiguousarray(q * np.sign(np.diagonal(rr, axis1=1, axis2=2))[:, None, :])
+            cloud = eng.cloud(p, nr)
+            nb = cloud.radius_search(kp, r)
+            try:
+                handed = np.array(nb.shot(frames, norm, mn))
+            finally:
+                nb.free()
+                cloud.free()
+            assert np.abs(handed - O.shot(p, nr, kp, r, frames, norm, mn)).max() < 1e-9, f"{name} r={r} mn={mn} norm={norm}"
+            if not framed.any():
+                continue
         err = np.abs(got - want)[framed].max()
         assert err < 1e-9, f"{name} r={r} mn={mn} norm={norm}: {err}"
         got_s = compute_shot_descriptor(kp, p, nr, r, min_neighborhood_size=mn)

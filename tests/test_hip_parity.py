@@ -164,7 +164,11 @@ def test_shot_duplicates_edge(O):
         d = sm.compute_descriptor_single_scale(e["cloud"], e["normals"], e["keypoints"], float(e["radius"]))
     off, idx, dist = O.radius_search(e["cloud"], e["keypoints"], float(e["radius"]), return_distance=True)
     tied = np.array([len(np.unique(dist[off[i]:off[i + 1]])) < off[i + 1] - off[i] for i in range(len(off) - 1)])
-    assert close(d, e["shot_m5"])[~tied].all()  # rows with tied rho are undefined in the reference itself
+    assert close(d, e["shot_m5"])[~tied].all()  # rows with tied rho are undefined in the reference itself ...
+    # ... and defined here: among neighbours at equal distance the larger index in the caller's cloud writes last (DESIGN.md 3,
+    # K5), which is how the oracle breaks its ties
+    want = O.shot_single_scale(e["cloud"], e["normals"], e["keypoints"], float(e["radius"]), True, 5)
+    assert tied.sum() >= 5 and np.abs(d - want)[tied].max() < 1e-9, np.abs(d - want)[tied].max()
 
 
 # ---- K6 + K7 ------------------------------------------------------------------------------------------------
