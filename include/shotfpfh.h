@@ -195,10 +195,11 @@ int sf_normals(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, const double *pre, d
  * flags: SF_OUT_DEVICE = saliency / count are device pointers. */
 int sf_iss_saliency(sf_ctx *ctx, sf_cloud *cloud, double salient_radius, double gamma_21, double gamma_32, int min_neighbors,
                     double *saliency /* n */, int32_t *count /* nullable, n */, int flags);
-/* Non-maximum suppression of ANY per-point score (caller order, n values): point i is selected <=> score[i] > 0, the ball of
- * non_max_radius around it holds at least min_neighbors points, and none of them has a strictly larger score (exact float64
- * comparisons: points that tie are all kept).  selected (room for n): the int64 indices in ascending caller order;
- * *n_selected (host): how many.  flags: SF_IN_DEVICE = score is a device pointer, SF_OUT_DEVICE = selected is one. */
+/* Non-maximum suppression of ANY per-point score (caller order, n values) -- ISS saliencies and Harris responses (K23) alike:
+ * point i is selected <=> score[i] > 0, the ball of non_max_radius around it holds at least min_neighbors points, and none of
+ * them has a strictly larger score (exact float64 comparisons: points that tie are all kept).  selected (room for n): the
+ * int64 indices in ascending caller order; *n_selected (host): how many.  flags: SF_IN_DEVICE = score is a device pointer,
+ * SF_OUT_DEVICE = selected is one. */
 int sf_iss_select(sf_ctx *ctx, sf_cloud *cloud, const double *saliency /* n */, double non_max_radius, int min_neighbors,
                   int64_t *selected /* n */, int64_t *n_selected, int flags);
 /* sf_iss_saliency followed by sf_iss_select without the saliency leaving the device; bit-identical to the two calls.
@@ -206,6 +207,31 @@ int sf_iss_select(sf_ctx *ctx, sf_cloud *cloud, const double *saliency /* n */, 
 int sf_iss_keypoints(sf_ctx *ctx, sf_cloud *cloud, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
                      int min_neighbors, double *saliency /* nullable, n */, int64_t *selected /* n */, int64_t *n_selected,
                      int flags);
+/* ---- Harris 3D keypoints (K23): the detector of pcl::HarrisKeypoint3D on the normals; the reference has none ----
+ * With B the ball of `radius` around point i (i included, |p_j - p_i|^2 <= radius^2), k = |B| and C = (1 / k) sum over B of
+ * n_j n_j^T (the normals as uploaded: not normalised, not centred, their sign does not matter):
+ *   SF_HARRIS_HARRIS     0.04 + det C - 0.04 trace(C)^2 (= det C for unit normals)
+ *   SF_HARRIS_NOBLE      det C / trace C
+ *   SF_HARRIS_LOWE       det C / trace(C)^2
+ *   SF_HARRIS_TOMASI     the smallest eigenvalue of C
+ *   SF_HARRIS_CURVATURE  e3 / (e1 + e2 + e3), e1 >= e2 >= e3 the eigenvalues of the mean-centred POSITION covariance of B (the
+ *                        numbers sf_iss_saliency decomposes; needs no normals)
+ * response[i] = that value, or -1.0 when k < min_neighbors, the trace is not above 0, the matrix is numerically rank-deficient
+ * (det <= 1e-12 trace^3; tomasi: lambda_min <= 1e-12 trace; curvature: e3 <= 1e-12 e1) or the value is not > threshold (a NaN
+ * is not).  threshold >= 0 and finite, min_neighbors >= 1, else SF_ERR_ARG; a method that needs normals on a cloud without them:
+ * SF_ERR_STATE.  count (nullable): the ball sizes; tensor (nullable, n x 6): C as xx yx zx yy zy zz -- for SF_HARRIS_CURVATURE
+ * the position covariance.  Everything in the caller's point order.  The pass runs on the grid sf_cloud_build_grid makes for
+ * `radius` (rebuilt if the cloud carries another one), so its bits do not depend on earlier searches.
+ * flags: SF_OUT_DEVICE = response / count / tensor are device pointers.
+ * Non-maximum suppression of a response array is sf_iss_select: it serves both detectors. */
+enum { SF_HARRIS_HARRIS = 0, SF_HARRIS_NOBLE = 1, SF_HARRIS_LOWE = 2, SF_HARRIS_TOMASI = 3, SF_HARRIS_CURVATURE = 4 };
+int sf_harris_response(sf_ctx *ctx, sf_cloud *cloud, double radius, int method, double threshold, int min_neighbors,
+                       double *response /* n */, int32_t *count /* nullable, n */, double *tensor /* nullable, n x 6 */, int flags);
+/* sf_harris_response followed by sf_iss_select(non_max_radius) without the response leaving the device; bit-identical to the
+ * two calls.  response (nullable, n): receives the scores; flags: SF_OUT_DEVICE = response and selected are device pointers. */
+int sf_harris_keypoints(sf_ctx *ctx, sf_cloud *cloud, double radius, double non_max_radius, int method, double threshold,
+                        int min_neighbors, double *response /* nullable, n */, int64_t *selected /* n */, int64_t *n_selected,
+                        int flags);
 /* ---- Outlier removal (K20): the filters PCL and Open3D run in front of the normals; the reference has neither ----
  * Statistical: mean[i] = (sum of the distances from point i to its k + 1 nearest cloud points) / k -- the nearest is the point
  * itself or an exact duplicate, distance 0 -- i.e. the mean distance to the k nearest OTHER points; mu = sum(mean) / n,

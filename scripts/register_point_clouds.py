@@ -39,11 +39,18 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--outlier-std-ratio", type=float, default=2.0, metavar="S")
     p.add_argument("--outlier-radius", type=float, default=None, metavar="R")
     p.add_argument("--outlier-min-neighbors", type=int, default=2, metavar="N")
-    p.add_argument("--keypoints", default="subsampling", choices=["random", "iterative", "subsampling", "subsampling_with_density", "iss"])
+    p.add_argument("--keypoints", default="subsampling", choices=["random", "iterative", "subsampling", "subsampling_with_density", "iss", "harris"],
+                   help="iss: Intrinsic Shape Signatures on the positions; harris: Harris 3D on the normals (corners and creases)")
     p.add_argument("--keypoint-size", type=float, default=None,
-                   help="sphere / voxel size of the keypoint selection (iss: the salient radius, default 6 x the cloud's resolution)")
+                   help="sphere / voxel size of the keypoint selection (iss: the salient radius, harris: the radius of the tensor; "
+                        "default for both 6 x the cloud's resolution)")
     p.add_argument("--iss-non-max-radius", type=float, default=None, help="iss: suppression radius (default 4 x the cloud's resolution)")
     p.add_argument("--iss-gamma21", type=float, default=0.975), p.add_argument("--iss-gamma32", type=float, default=0.975)
+    p.add_argument("--harris-method", default="harris", choices=["harris", "noble", "lowe", "tomasi", "curvature"],
+                   help="harris: the response -- 0.04 + det - 0.04 tr^2, det / tr, det / tr^2, the smallest eigenvalue of the normals' "
+                        "tensor, or the surface variation of the positions (needs no normals)")
+    p.add_argument("--harris-threshold", type=float, default=0.0, metavar="T", help="harris: the smallest response kept (not negative)")
+    p.add_argument("--harris-non-max-radius", type=float, default=None, metavar="R", help="harris: suppression radius (default --keypoint-size)")
     p.add_argument("--min-n-neighbors", type=int, default=None)
     p.add_argument("--proportion", type=float, default=0.5, help="share of points kept by --keypoints random")
     p.add_argument("--descriptor", default="shot_single_scale", choices=["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc", "pfh"],
@@ -105,6 +112,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--outliers radius needs --outlier-radius")
     if args.descriptor != "usc" and (args.usc_min_radius is not None or args.usc_density_radius is not None):
         p.error("--usc-min-radius and --usc-density-radius need --descriptor usc")
+    if args.harris_threshold < 0.0:
+        p.error("--harris-threshold must not be negative")
     if args.icp_loss is not None and args.icp_loss_scale is None:
         p.error("--icp-loss needs --icp-loss-scale")
     if args.icp_loss is None and (args.icp_loss_scale is not None or args.icp_loss_scale_start is not None):
@@ -152,7 +161,8 @@ def main(argv=None) -> int:
                                     ref_kept=ref_kept)
     pipe.select_keypoints(args.keypoints, neighborhood_size=args.keypoint_size, min_n_neighbors=args.min_n_neighbors,
                           proportion_picked=args.proportion, iss_non_max_radius=args.iss_non_max_radius,
-                          iss_gamma_21=args.iss_gamma21, iss_gamma_32=args.iss_gamma32)
+                          iss_gamma_21=args.iss_gamma21, iss_gamma_32=args.iss_gamma32, harris_method=args.harris_method,
+                          harris_threshold=args.harris_threshold, harris_non_max_radius=args.harris_non_max_radius)
     if args.descriptor == "usc":
         pipe.compute_usc_descriptor(args.radius, min_radius=args.usc_min_radius, density_radius=args.usc_density_radius)
     else:

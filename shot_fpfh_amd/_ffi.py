@@ -76,6 +76,8 @@ SIGNATURES = {
     "sf_iss_saliency": (_int, [_vp, _vp, _f64, _f64, _f64, _int, _vp, _vp, _int]),
     "sf_iss_select": (_int, [_vp, _vp, _vp, _f64, _int, _vp, _vp, _int]),
     "sf_iss_keypoints": (_int, [_vp, _vp, _f64, _f64, _f64, _f64, _int, _vp, _vp, _vp, _int]),
+    "sf_harris_response": (_int, [_vp, _vp, _f64, _int, _f64, _int, _vp, _vp, _vp, _int]),
+    "sf_harris_keypoints": (_int, [_vp, _vp, _f64, _f64, _int, _f64, _int, _vp, _vp, _vp, _int]),
     "sf_knn_mean_distance": (_int, [_vp, _vp, _int, _vp, _int]),
     "sf_outliers_statistical": (_int, [_vp, _vp, _int, _f64, _vp, _vp, _vp, _vp, _int]),
     "sf_ball_counts": (_int, [_vp, _vp, _f64, _vp, _int]),

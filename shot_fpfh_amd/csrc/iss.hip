@@ -138,8 +138,10 @@ int saliency_dev(sf_ctx *ctx, sf_cloud *c, double radius, double gamma_21, doubl
     return SF_OK;
 }
 
+} // namespace
+
 // the selected points of a score in the caller's order (device), ascending, and their number (device word *dnum)
-int select_dev(sf_ctx *ctx, sf_cloud *c, const double *score, double radius, int min_neighbors, int64_t *selected, size_t *dnum)
+int sf_k10_select_dev(sf_ctx *ctx, sf_cloud *c, const double *score, double radius, int min_neighbors, int64_t *selected, size_t *dnum)
 {
     const int64_t n = c->n;
     SF_CHECK(sf_k2_ensure_grid(ctx, c, radius));
@@ -157,7 +159,7 @@ int select_dev(sf_ctx *ctx, sf_cloud *c, const double *score, double radius, int
 }
 
 // the tail of both selecting entry points: the count to the host (one read-back), then the indices if the host wants them
-int finish_selection(sf_ctx *ctx, const size_t *dnum, const int64_t *dsel, int64_t *selected, int64_t *n_selected, int flags)
+int sf_k10_finish_selection(sf_ctx *ctx, const size_t *dnum, const int64_t *dsel, int64_t *selected, int64_t *n_selected, int flags)
 {
     void *pin = nullptr;
     SF_CHECK(sf_ctx_pinned(ctx, &pin));
@@ -171,8 +173,6 @@ int finish_selection(sf_ctx *ctx, const size_t *dnum, const int64_t *dsel, int64
     }
     return SF_OK;
 }
-
-} // namespace
 
 extern "C" int sf_iss_saliency(sf_ctx *ctx, sf_cloud *c, double salient_radius, double gamma_21, double gamma_32, int min_neighbors,
                                double *saliency, int32_t *count, int flags)
@@ -211,8 +211,8 @@ extern "C" int sf_iss_select(sf_ctx *ctx, sf_cloud *c, const double *saliency, d
     SF_CHECK(stage_in(tmp, saliency, (size_t)n, flags, &dsal));
     SF_CHECK(stage_out(tmp, selected, (size_t)n, flags, &dsel));
     SF_CHECK(tmp.alloc(&dnum, 1));
-    SF_CHECK(select_dev(ctx, c, dsal, non_max_radius, min_neighbors, dsel, dnum));
-    return finish_selection(ctx, dnum, dsel, selected, n_selected, flags);
+    SF_CHECK(sf_k10_select_dev(ctx, c, dsal, non_max_radius, min_neighbors, dsel, dnum));
+    return sf_k10_finish_selection(ctx, dnum, dsel, selected, n_selected, flags);
 }
 
 extern "C" int sf_iss_keypoints(sf_ctx *ctx, sf_cloud *c, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
@@ -235,7 +235,7 @@ extern "C" int sf_iss_keypoints(sf_ctx *ctx, sf_cloud *c, double salient_radius,
     SF_CHECK(stage_out(tmp, selected, (size_t)n, flags, &dsel));
     SF_CHECK(tmp.alloc(&dnum, 1));
     SF_CHECK(saliency_dev(ctx, c, salient_radius, gamma_21, gamma_32, min_neighbors, dsal, nullptr));
-    SF_CHECK(select_dev(ctx, c, dsal, non_max_radius, min_neighbors, dsel, dnum));
+    SF_CHECK(sf_k10_select_dev(ctx, c, dsal, non_max_radius, min_neighbors, dsel, dnum));
     if (saliency) SF_CHECK(finish_out(ctx, saliency, (size_t)n, flags, dsal));
-    return finish_selection(ctx, dnum, dsel, selected, n_selected, flags);
+    return sf_k10_finish_selection(ctx, dnum, dsel, selected, n_selected, flags);
 }

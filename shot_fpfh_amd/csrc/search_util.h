@@ -1,5 +1,5 @@
-// search_util.h -- what the radius search (search.hip), the k-NN search (knn.hip), the ISS suppression (iss.hip), the outlier
-// filters (outliers.hip) and USC (usc.hip) share: the stencil bounds of a query, the run tables and the candidate step of the K2
+// search_util.h -- what the radius search (search.hip), the k-NN search (knn.hip), the ISS suppression (iss.hip), the Harris
+// tensor sweep (harris.hip), the outlier filters (outliers.hip) and USC (usc.hip) share: the stencil bounds of a query, the run tables and the candidate step of the K2
 // family's sweeps, the maps between the caller's point order and the cell-sorted one, and the prototypes of the sweeps that
 // search.hip runs for the other files.  (The sort configuration and the rocPRIM call helper: dev_prims.h.)
 #pragma once
@@ -188,4 +188,9 @@ int sf_k2_radius_cov_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *p
 int sf_k2_count_self(sf_ctx *ctx, sf_cloud *c, double radius, const char *prof, int32_t *count);
 // ... and the prologue of every stage that weighs or filters by density: sf_k2_own_grid, then that sweep into n + 1 words of the guard
 int sf_k2_ball_sizes(sf_ctx *ctx, sf_cloud *c, sf_pool_guard &g, double radius, const char *prof, int32_t **count);
+// iss.hip, for harris.hip: K10's selection chain on any per-point score in the caller's order (device).  sf_k10_select_dev: the
+// suppression over the balls of `radius` on whichever grid serves it, then the selected indices, ascending, and their number
+// (device word *dnum); sf_k10_finish_selection: the count to the host (one read-back), then the indices if the host wants them
+int sf_k10_select_dev(sf_ctx *ctx, sf_cloud *c, const double *score, double radius, int min_neighbors, int64_t *selected, size_t *dnum);
+int sf_k10_finish_selection(sf_ctx *ctx, const size_t *dnum, const int64_t *dsel, int64_t *selected, int64_t *n_selected, int flags);
 

@@ -33,6 +33,15 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+HARRIS_METHODS = ("harris", "noble", "lowe", "tomasi", "curvature")  # SF_HARRIS_HARRIS .. SF_HARRIS_CURVATURE, in the enum's order
+
+
+def harris_method_id(method: str) -> int:
+    if method not in HARRIS_METHODS:
+        raise ValueError(f"unknown Harris response method {method!r}: one of {', '.join(HARRIS_METHODS)}")
+    return HARRIS_METHODS.index(method)
+
+
 def fpfh_edges(n_bins: int) -> np.ndarray:
     """The 3 x (n_bins+1) bin edges np.histogramdd derives from `bins=n_bins` and the ranges of
     fpfh.py:82-87.  Computed with np.linspace on the host so the device compares against the very
@@ -1029,6 +1038,34 @@ class Cloud:
                                                    C.byref(k), SF_HOST), "sf_iss_keypoints")
         idx = sel[: k.value].copy()
         return (idx, sal) if return_saliency else idx
+
+    # ---- Harris 3D keypoints (K23) ------------------------------------------------------------------------
+    def harris_response(self, radius: float, method: str = "harris", threshold: float = 0.0, min_neighbors: int = 5,
+                        return_counts: bool = False, return_tensor: bool = False):
+        """sf_harris_response: the Harris response of every point's ball of normals (`method`: HARRIS_METHODS; "curvature"
+        takes the position covariance and needs no normals), -1.0 where the rule rejects the point; caller order [, the ball
+        sizes] [, the (n, 6) matrices xx yx zx yy zy zz]."""
+        res = np.zeros(self.n, dtype=np.float64)
+        cnt = np.zeros(self.n, dtype=np.int32) if return_counts else None
+        ten = np.zeros((self.n, 6), dtype=np.float64) if return_tensor else None
+        _ffi.check(self.engine.lib.sf_harris_response(self.engine.h, self.h, float(radius), harris_method_id(method), float(threshold),
+                                                     int(min_neighbors), _ptr(res), _ptr(cnt), _ptr(ten), SF_HOST), "sf_harris_response")
+        out = (res,) + ((cnt,) if return_counts else ()) + ((ten,) if return_tensor else ())
+        return out if len(out) > 1 else res
+
+    def harris_keypoints(self, radius: float, non_max_radius: Optional[float] = None, method: str = "harris", threshold: float = 0.0,
+                         min_neighbors: int = 5, return_response: bool = False):
+        """sf_harris_keypoints: the response and K10's suppression (`non_max_radius`, None: `radius`), the response staying on
+        the device in between; the selected indices, int64, ascending [, the response]."""
+        res = np.zeros(self.n, dtype=np.float64) if return_response else None
+        sel = np.zeros(max(self.n, 1), dtype=np.int64)
+        k = C.c_int64(0)
+        r_n = float(radius) if non_max_radius is None else float(non_max_radius)
+        _ffi.check(self.engine.lib.sf_harris_keypoints(self.engine.h, self.h, float(radius), r_n, harris_method_id(method),
+                                                      float(threshold), int(min_neighbors), _ptr(res), _ptr(sel), C.byref(k), SF_HOST),
+                   "sf_harris_keypoints")
+        idx = sel[: k.value].copy()
+        return (idx, res) if return_response else idx
 
     # ---- outlier removal (K20) ----------------------------------------------------------------------------
     def knn_mean_distance(self, k: int) -> np.ndarray:

@@ -5,7 +5,9 @@ query_radius, the lists come from the uniform-grid radius search on the MI355X (
 remaining logic is index bookkeeping and stays on the host.
 
 `select_keypoints_iss` (with `cloud_resolution` and `iss_saliency`) has no counterpart in the reference: the ISS
-detector (Zhong 2009, the rule of PCL's and Open3D's detectors), which looks at the geometry -- kernels K10.
+detector (Zhong 2009, the rule of PCL's and Open3D's detectors), which looks at the geometry -- kernels K10.  Nor have
+`harris_response` and `select_keypoints_harris`: the Harris 3D detector of PCL, which scores how the normals of a ball turn
+-- kernels K23, with K10's suppression.
 """
 from __future__ import annotations
 
@@ -15,7 +17,7 @@ import numpy as np
 import numpy.typing as npt
 
 from .core import grid_subsampling, voxel_closest_to_barycentre
-from .engine import default_engine
+from .engine import default_engine, harris_method_id
 
 __all__ = [
     "select_keypoints_iteratively",
@@ -26,6 +28,8 @@ __all__ = [
     "cloud_resolution",
     "iss_saliency",
     "select_keypoints_iss",
+    "harris_response",
+    "select_keypoints_harris",
 ]
 
 # module-level generator with the reference's seed (keypoint_selection.py:8); its state persists across calls
@@ -195,5 +199,98 @@ def select_keypoints_iss(
             salient_radius = 6.0 * rho if salient_radius is None else salient_radius
             non_max_radius = 4.0 * rho if non_max_radius is None else non_max_radius
         return cloud.iss_keypoints(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, return_saliency)
+    finally:
+        cloud.free()
+
+
+# ---- Harris 3D: the response of the normals' tensor + K10's non-maximum suppression on the device (K23) ---------------
+def _harris_rule(method: str, threshold: float, min_neighbors: int) -> None:
+    harris_method_id(method)  # (ValueError for an unknown one)
+    if not (np.isfinite(float(threshold)) and float(threshold) >= 0.0):
+        raise ValueError(f"threshold must be finite and not negative (got {threshold}): the suppression only considers responses above 0")
+    if int(min_neighbors) < 1:
+        raise ValueError(f"min_neighbors must be at least 1 (got {min_neighbors})")
+
+
+def _harris_normals(points, normals, method: str):
+    """the normals as an (N, 3) float64 array, or None where the method needs none"""
+    if normals is None:
+        if method != "curvature":
+            raise ValueError(f'method "{method}" is computed from the normals: pass them, or use method="curvature"')
+        return None
+    normals = np.ascontiguousarray(normals, dtype=np.float64)
+    if normals.shape != points.shape:
+        raise ValueError(f"normals must have the shape of points {points.shape}, got {normals.shape}")
+    if not np.isfinite(normals).all():
+        raise ValueError("normals hold a non-finite component")
+    return normals
+
+
+def harris_response(
+    points: npt.NDArray[np.float64],
+    normals: Optional[npt.NDArray[np.float64]],
+    radius: float,
+    *,
+    method: str = "harris",
+    threshold: float = 0.0,
+    min_neighbors: int = 5,
+    engine=None,
+) -> npt.NDArray[np.float64]:
+    """Harris 3D response of every point (pcl::HarrisKeypoint3D's rule).  With C the mean of n n^T over the ball of `radius`
+    around the point (itself included; the normals as given, their sign does not matter): "harris" 0.04 + det C - 0.04 tr(C)^2,
+    "noble" det C / tr C, "lowe" det C / tr(C)^2, "tomasi" the smallest eigenvalue of C, "curvature" the surface variation
+    e3 / (e1 + e2 + e3) of the ball's position covariance (`normals` may be None) -- or -1.0 where the ball holds fewer than
+    `min_neighbors` points, the matrix is numerically rank-deficient (a flat patch) or the value is not above `threshold`."""
+    points = _iss_points(points)
+    radius = _iss_radius("radius", radius)
+    _harris_rule(method, threshold, min_neighbors)
+    normals = _harris_normals(points, normals, method)
+    if points.shape[0] == 0:
+        return np.zeros(0, dtype=np.float64)
+    cloud = (engine or default_engine()).cloud(points, normals)
+    try:
+        return cloud.harris_response(radius, method, threshold, min_neighbors)
+    finally:
+        cloud.free()
+
+
+def select_keypoints_harris(
+    points: npt.NDArray[np.float64],
+    normals: Optional[npt.NDArray[np.float64]] = None,
+    radius: Optional[float] = None,
+    non_max_radius: Optional[float] = None,
+    *,
+    method: str = "harris",
+    threshold: float = 0.0,
+    min_neighbors: int = 5,
+    return_response: bool = False,
+    engine=None,
+):
+    """Harris 3D keypoints: the points whose response (harris_response) is positive, that have at least `min_neighbors`
+    points within `non_max_radius` (themselves included) and none among them with a strictly larger response -- exact ties are
+    all kept.  int64 indices into `points`, ascending [, the response of every point].  `radius` None: 6 times the cloud's
+    resolution (cloud_resolution), as ISS; `non_max_radius` None: `radius`, as PCL uses one radius.  `normals` None is accepted
+    for method="curvature" alone."""
+    points = _iss_points(points)
+    if radius is not None:
+        radius = _iss_radius("radius", radius)
+    if non_max_radius is not None:
+        non_max_radius = _iss_radius("non_max_radius", non_max_radius)
+    _harris_rule(method, threshold, min_neighbors)
+    normals = _harris_normals(points, normals, method)
+    n = points.shape[0]
+    if n == 0:
+        empty = np.zeros(0, dtype=np.int64)
+        return (empty, np.zeros(0, dtype=np.float64)) if return_response else empty
+    if radius is None and n < 2:
+        raise ValueError("an automatic Harris radius needs at least two points")
+    cloud = (engine or default_engine()).cloud(points, normals)
+    try:
+        if radius is None:
+            rho = cloud.resolution(points)
+            if not rho > 0.0:
+                raise ValueError("an automatic Harris radius needs a cloud resolution above 0 (every point has an exact duplicate)")
+            radius = 6.0 * rho
+        return cloud.harris_keypoints(radius, non_max_radius, method, threshold, min_neighbors, return_response)
     finally:
         cloud.free()

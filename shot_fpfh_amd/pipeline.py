@@ -108,7 +108,7 @@ class RegistrationPipeline:
     # ---- stage 1: keypoints (pipeline.py:53-130) ---------------------------------------------------------
     def select_keypoints(
         self,
-        selection_algorithm: Literal["random", "iterative", "subsampling", "subsampling_with_density", "iss"],
+        selection_algorithm: Literal["random", "iterative", "subsampling", "subsampling_with_density", "iss", "harris"],
         *,
         neighborhood_size: float | None = None,
         min_n_neighbors: int | None = None,
@@ -117,23 +117,38 @@ class RegistrationPipeline:
         iss_non_max_radius: float | None = None,
         iss_gamma_21: float = 0.975,
         iss_gamma_32: float = 0.975,
+        harris_method: str = "harris",
+        harris_threshold: float = 0.0,
+        harris_non_max_radius: float | None = None,
     ) -> None:
         """"iss" (not in the reference): `neighborhood_size` is the salient radius, `iss_non_max_radius` the suppression
-        radius (None: 6 resp. 4 times the cloud's resolution), `min_n_neighbors` the smallest ball when given (else 5)."""
+        radius (None: 6 resp. 4 times the cloud's resolution), `min_n_neighbors` the smallest ball when given (else 5).
+        "harris" (not in the reference either): Harris 3D on each side's stored normals -- `neighborhood_size` is the radius of
+        the tensor (None: 6 times the cloud's resolution), `harris_non_max_radius` that of the suppression (None: the same),
+        `harris_method` one of harris / noble / lowe / tomasi / curvature (the last needs no normals), `harris_threshold` the
+        smallest response kept, `min_n_neighbors` as for "iss"."""
         if selection_algorithm == "random":
             assert 0 <= proportion_picked <= 1, "Incorrect proportion passed."
-        pick = {
-            "random": lambda p: _ks.select_query_indices_randomly(p.shape[0], int(p.shape[0] * proportion_picked)),
-            "iterative": lambda p: _ks.select_keypoints_iteratively(p, neighborhood_size),
-            "subsampling": lambda p: _ks.select_keypoints_subsampling(p, neighborhood_size),
-            "subsampling_with_density": lambda p: _ks.select_keypoints_with_density_threshold(p, neighborhood_size, min_n_neighbors),
-            "iss": lambda p: _ks.select_keypoints_iss(p, neighborhood_size, iss_non_max_radius, iss_gamma_21, iss_gamma_32,
-                                                      5 if min_n_neighbors is None else min_n_neighbors),
+        if selection_algorithm == "harris" and harris_method != "curvature":
+            for side in ("scan", "ref"):
+                if getattr(self, f"{side}_normals") is None:
+                    raise ValueError(f'select_keypoints("harris", harris_method="{harris_method}") is computed from the normals '
+                                     f'and {side}_normals is None: pass normals, or use harris_method="curvature"')
+        min_ball = 5 if min_n_neighbors is None else min_n_neighbors
+        pick = {  # (points, normals of a side; only "harris" looks at the normals)
+            "random": lambda p, nr: _ks.select_query_indices_randomly(p.shape[0], int(p.shape[0] * proportion_picked)),
+            "iterative": lambda p, nr: _ks.select_keypoints_iteratively(p, neighborhood_size),
+            "subsampling": lambda p, nr: _ks.select_keypoints_subsampling(p, neighborhood_size),
+            "subsampling_with_density": lambda p, nr: _ks.select_keypoints_with_density_threshold(p, neighborhood_size, min_n_neighbors),
+            "iss": lambda p, nr: _ks.select_keypoints_iss(p, neighborhood_size, iss_non_max_radius, iss_gamma_21, iss_gamma_32, min_ball),
+            "harris": lambda p, nr: _ks.select_keypoints_harris(
+                p, None if harris_method == "curvature" else nr, neighborhood_size, harris_non_max_radius, method=harris_method,
+                threshold=harris_threshold, min_neighbors=min_ball),
         }.get(selection_algorithm)
         if pick is None:
             raise ValueError("Incorrect keypoint selection algorithm.")
         logging.info(f"-- Selecting keypoints: {selection_algorithm} --")
-        self._fill("keypoints", force_recompute, lambda side: pick(getattr(self, side)))
+        self._fill("keypoints", force_recompute, lambda side: pick(getattr(self, side), getattr(self, f"{side}_normals")))
         for side in ("scan", "ref"):
             logging.info(f"{getattr(self, side + '_keypoints').shape[0]} descriptors selected on {side} out of "
                          f"{getattr(self, side).shape[0]} points.")
