@@ -49,6 +49,7 @@ extern "C" {
 #define SF_SHOT_MAX_COSINE_BINS 64 /* sf_shot_serial_bins: rows of up to 32 x 64 = 2048 bins */
 #define SF_USC_MAX_BINS 4096 /* sf_usc: azimuth_bins x elevation_bins x radius_bins at most (16 B of LDS per bin and wave) */
 #define SF_PFH_MAX_BINS 16 /* sf_pfh: bins per angle; rows of n_bins^3 <= 4096 doubles, the row cap of sf_usc */
+#define SF_SPIN_MAX_WIDTH 44 /* sf_spin_images: image_width at most; rows of (W + 1)(2 W + 1) <= 4005 doubles, within the row cap of sf_usc */
 #define SF_FAST_FPFH_BINS 8 /* n_bins up to here: LDS-histogram K6 and the matrix-core / streaming K7 */
 #define SF_MAX_FPFH_BINS 1290 /* n_bins^3 must fit an int; the reference takes any n_bins (fpfh.py:16).  What bounds n_bins in
                                 practice is the table of n x n_bins^3 32-bit counts in HBM (the reference holds twice that in host RAM) */
@@ -354,6 +355,34 @@ int sf_usc(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, const double *lrf /* m x
  *   hundred float64 operations per keypoint. */
 int sf_pfh_tables(int64_t n_bins, double *q /* S + 1 */, double *ca /* S + 1 */, double *sa /* S + 1 */, int32_t *g /* S + 1 */);
 int sf_pfh(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, int64_t n_bins, double *out /* m x S^3 */, int flags);
+
+/* ---- Spin images (K24; Johnson, Hebert 1999, pcl::SpinImageEstimation; the reference has none) --------------------------------
+ * Per keypoint p with axis n (its normal, used as given: neither normalised nor centred) a 2-D image over the cylindrical
+ * coordinates of its neighbours about the line through p along n: alpha, the distance from the line, and beta, the signed height
+ * along it.  W = image_width, 1 <= W <= SF_SPIN_MAX_WIDTH; the signed image has (W + 1) x (2 W + 1) nodes, the unsigned one
+ * (|beta|) (W + 1) x (W + 1); node (iu, iv) at iu NV + iv of a row of D = (W + 1) NV doubles.  The image covers the cylinder of
+ * radius and half-height R / sqrt 2, inscribed in the search ball of radius R.  No local reference frame.
+ * sf_spin_scale (host only, no context): *inv_bin = (W sqrt(2.0)) / radius, bins per unit length (PCL's bin_size = R / W / sqrt 2).
+ * A list entry at x with normal m, unfused float64: d = x - p, d2 = (dx dx + dy dy) + dz dz, beta = (nx dx + ny dy) + nz dz,
+ *   a2 = d2 - beta beta (0 when negative), alpha = sqrt(a2) correctly rounded, u = alpha inv_bin, t = beta inv_bin (signed) or
+ *   |beta| inv_bin.  It contributes iff d2 > 0, u <= W, |t| <= W and, with use_min_cos, c >= min_cos (signed) or |c| >= min_cos of
+ *   c = (nx mx + ny my) + nz mz; a NaN contributes nothing.  v = t + W (signed) or t.  With iu = floor(u), qu = floor((u - iu) 65536)
+ *   and the same for v, it adds the INTEGER weights (65536 - qu)(65536 - qv), qu (65536 - qv), (65536 - qu) qv, qu qv to nodes
+ *   (iu, iv), (iu + 1, iv), (iu, iv + 1), (iu + 1, iv + 1) -- 2^32 in all, a zero weight not added.  Bin contents are integers: a
+ *   row is exact, a function of the cloud alone (not of the order of a list or of the cloud), and a call repeats bit for bit.
+ *   With c contributing entries: zeros when c <= min_neighborhood_size, else row[b] = (double)count[b] 2^-32, or with
+ *   normalize != 0 (double)count[b] / ((double)c 2^32) (the row sums to 1).  The whole statement: tests/spin_numpy.py.
+ * sf_spin_images: the rows of the queries of `nbrs` (a radius search, or sf_nbrs_import), whose radius is R.  axes: m x 3, by
+ *   query row.  Positions alone suffice unless use_min_cos != 0, which needs the cloud's normals (SF_ERR_STATE without them).
+ *   contrib (nullable): c per query.  Returns SF_ERR_ARG for image_width outside [1, SF_SPIN_MAX_WIDTH], a null pointer,
+ *   non-finite host axes, min_cos outside [-1, 1], or a list of 2^24 entries or more (`out` is then undefined).
+ *   flags: SF_IN_DEVICE = axes is a device pointer, SF_OUT_DEVICE = out and contrib are.  The call waits for its kernel (it reads
+ *   the error word back).  Not built: PCL's angular and radial image domains, a rotation axis other than the one given per
+ *   keypoint, sharded (block-grid) clouds, compressed (PCA) images. */
+int sf_spin_scale(double radius, int64_t image_width, double *inv_bin);
+int sf_spin_images(sf_ctx *ctx, sf_cloud *cloud, sf_nbrs *nbrs, const double *axes /* m x 3 */, int64_t image_width,
+                   int signed_beta, int use_min_cos, double min_cos, int normalize, int64_t min_neighborhood_size,
+                   double *out /* m x D */, int32_t *contrib /* m, nullable */, int flags);
 
 /* ---- a repeated step as ONE launch (HIP graph) -------------------------------------------------------------------------
  * sf_graph_begin .. sf_graph_end capture every device operation the calls in between issue on the context's streams (nothing

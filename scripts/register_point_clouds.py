@@ -53,15 +53,20 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--harris-non-max-radius", type=float, default=None, metavar="R", help="harris: suppression radius (default --keypoint-size)")
     p.add_argument("--min-n-neighbors", type=int, default=None)
     p.add_argument("--proportion", type=float, default=0.5, help="share of points kept by --keypoints random")
-    p.add_argument("--descriptor", default="shot_single_scale", choices=["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc", "pfh"],
+    p.add_argument("--descriptor", default="shot_single_scale", choices=["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc", "pfh", "spin"],
                    help="usc: Unique Shape Context at --radius, 14 x 14 x 10 bins, no normals used; "
-                        "pfh: Point Feature Histograms at --radius, every pair of a ball's points (quadratic in the ball size)")
+                        "pfh: Point Feature Histograms at --radius, every pair of a ball's points (quadratic in the ball size); "
+                        "spin: spin images about each keypoint's normal at --radius, no local reference frame")
     p.add_argument("--usc-min-radius", type=float, default=None, metavar="R0", help="--descriptor usc: the first radial edge (default --radius / 10)")
     p.add_argument("--usc-density-radius", type=float, default=None, metavar="RD",
                    help="--descriptor usc: the ball whose population weighs a neighbour down (default --radius / 5)")
     p.add_argument("--radius", type=float, required=True)
     p.add_argument("--fpfh-bins", type=int, default=5)
     p.add_argument("--pfh-bins", type=int, default=5, metavar="S", help="--descriptor pfh: bins per angle, 1 .. 16 (rows of S^3)")
+    p.add_argument("--spin-width", type=int, default=8, metavar="W", help="--descriptor spin: bins per image side, 1 .. 44")
+    p.add_argument("--spin-signed", action="store_true",
+                   help="--descriptor spin: keep the sign of the height along the normal (rows of (W + 1)(2 W + 1); needs consistently "
+                        "oriented normals).  Default: the image folded over the tangent plane, (W + 1)^2, blind to the normals' signs")
     p.add_argument("--phi", type=float, default=3.0), p.add_argument("--rho", type=float, default=10.0)
     p.add_argument("--n-scales", type=int, default=2)
     p.add_argument("--no-support-subsampling", action="store_true")
@@ -167,6 +172,7 @@ def main(argv=None) -> int:
         pipe.compute_usc_descriptor(args.radius, min_radius=args.usc_min_radius, density_radius=args.usc_density_radius)
     else:
         pipe.compute_descriptors(radius=args.radius, descriptor_choice=args.descriptor, fpfh_n_bins=args.fpfh_bins, pfh_n_bins=args.pfh_bins,
+                                 spin_width=args.spin_width, spin_signed=args.spin_signed,
                                  phi=args.phi, rho=args.rho, n_scales=args.n_scales, subsample_support=not args.no_support_subsampling,
                                  min_neighborhood_size=args.min_neighborhood_size, disable_progress_bars=True, verbose=False)
     pipe.find_descriptors_matches(args.matching, reject_threshold=args.reject_threshold,

@@ -7,7 +7,7 @@ No PyTorch, no CPU fallback.
 """
 from . import _ffi
 from ._ffi import ShotFpfhError
-from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor, compute_normals
+from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor, compute_normals, compute_spin_image_descriptor
 from .engine import Cloud, DeviceArray, Engine, Neighbors, Spfh, default_engine
 from .helpers import get_data, read_ply, write_ply
 from .icp import icp_symmetric
@@ -37,6 +37,7 @@ __all__ = [
     "compute_fpfh_descriptor",
     "compute_normals",
     "ShotMultiprocessor",
+    "compute_spin_image_descriptor",
     "basic_matching",
     "match_descriptors",
     "ransac_on_matches",

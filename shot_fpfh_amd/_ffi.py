@@ -19,6 +19,7 @@ SF_ERR_UNSUPPORTED = -6  # e.g. sf_fpfh_moments: K7's form for this table does n
 SF_ERR_BIN_RANGE = -7  # sf_shot_serial_bins: a neighbour in cosine bin n (the reference's IndexError)
 USC_MAX_BINS = 4096  # SF_USC_MAX_BINS: sf_usc takes rows of at most this many bins
 PFH_MAX_BINS = 16  # SF_PFH_MAX_BINS: sf_pfh takes 1 .. 16 bins per angle (rows of n_bins^3)
+SPIN_MAX_WIDTH = 44  # SF_SPIN_MAX_WIDTH: sf_spin_images takes image widths 1 .. 44 (rows of at most 45 x 89 nodes)
 MAX_FPFH_BINS = 1290  # SF_MAX_FPFH_BINS: n_bins^3 fits an int (n_bins above 8 take the generic kernels; memory is the real bound)
 
 
@@ -95,6 +96,8 @@ SIGNATURES = {
     "sf_usc": (_int, [_vp, _vp, _vp, _vp, _vp, _f64, _i64, _i64, _i64, _int, _i64, _vp, _int]),
     "sf_pfh_tables": (_int, [_i64, _vp, _vp, _vp, _vp]),
     "sf_pfh": (_int, [_vp, _vp, _vp, _i64, _vp, _int]),
+    "sf_spin_scale": (_int, [_f64, _i64, _vp]),
+    "sf_spin_images": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _f64, _int, _i64, _vp, _vp, _int]),
     "sf_sync_count": (C.c_ulonglong, []),
     "sf_graph_begin": (_int, [_vp]),
     "sf_graph_end": (_vp, [_vp]),

@@ -1,7 +1,7 @@
 """GPU drop-ins for shot_fpfh.descriptors (reference descriptors/__init__.py:1-17): the three hot-path
 exports (compute_fpfh_descriptor, compute_normals, ShotMultiprocessor), the PCA feature helpers that
-share kernel K3 with the normals, Unique Shape Context (compute_usc_descriptor, K21) and Point Feature Histograms
-(compute_pfh_descriptor, K22): neither is in the reference."""
+share kernel K3 with the normals, Unique Shape Context (compute_usc_descriptor, K21), Point Feature Histograms
+(compute_pfh_descriptor, K22) and spin images (compute_spin_image_descriptor, K24): none of the three is in the reference."""
 from .fpfh import compute_fpfh_descriptor
 from .normals import compute_normals
 from .pca_features import (
@@ -12,6 +12,7 @@ from .pca_features import (
 )
 from .pfh import compute_pfh_descriptor
 from .shot import ShotMultiprocessor
+from .spin import compute_spin_image_descriptor
 from .usc import compute_usc_descriptor
 
 __all__ = [
@@ -24,4 +25,5 @@ __all__ = [
     "ShotMultiprocessor",
     "compute_usc_descriptor",
     "compute_pfh_descriptor",
+    "compute_spin_image_descriptor",
 ]

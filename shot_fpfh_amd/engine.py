@@ -1365,6 +1365,60 @@ class Neighbors:
         _ffi.check(self.engine.lib.sf_pfh(self.engine.h, self.cloud.h, self.h, S, op, flags), "sf_pfh")
         return res
 
+    def spin_images(self, axes, image_width: int = 8, *, signed_beta: bool = True, min_cos: Optional[float] = None,
+                    normalize: bool = False, min_neighborhood_size: int = 0, out: Optional[DeviceArray] = None,
+                    return_counts: bool = False):
+        """sf_spin_images (K24): the (m, D) spin images of these lists about `axes` ((m, 3): each keypoint's normal, used as
+        given; a host array or a device array), D = (W + 1)(2 W + 1) with signed_beta, (W + 1)^2 without (|beta|: for normals of
+        arbitrary sign).  min_cos: the support angle's cosine, in [-1, 1] -- needs the cloud's normals; None: positions alone.
+        normalize: rows sum to 1.  A keypoint with at most min_neighborhood_size contributing entries gets zeros.  out (a device
+        array of m x D float64): the rows stay in HBM.  return_counts: (rows, the contributing entries per keypoint, int32)."""
+        W = operator.index(image_width)
+        if not 1 <= W <= _ffi.SPIN_MAX_WIDTH:
+            raise ValueError(f"spin_images: image_width = {W} outside [1, {_ffi.SPIN_MAX_WIDTH}]")
+        use_cos = min_cos is not None
+        mc = float(min_cos) if use_cos else 0.0
+        if use_cos and not -1.0 <= mc <= 1.0:
+            raise ValueError(f"spin_images: min_cos must lie in [-1, 1] (got {mc})")
+        D = (W + 1) * (2 * W + 1 if signed_beta else W + 1)
+        flags = SF_HOST
+        if isinstance(axes, DeviceArray):
+            if axes.nbytes < self.m * 24:
+                raise ValueError("spin_images: one axis per keypoint expected")
+            ap, flags = axes.ptr, SF_IN_DEVICE
+        else:
+            axes = _f64(axes).reshape(-1, 3)
+            if axes.shape[0] != self.m:
+                raise ValueError("spin_images: one axis per keypoint expected")
+            if not np.isfinite(axes).all():
+                raise ValueError("spin_images: the axes must be finite")
+            ap = _ptr(axes)
+        counts = cd = None
+        if out is None:
+            res = self.engine.host_empty((self.m, D))
+            op = _ptr(res)
+            if return_counts:
+                counts = np.zeros(self.m, dtype=np.int32)
+                cp = _ptr(counts)
+        else:
+            if out.nbytes < self.m * D * 8:
+                raise ValueError(f"spin_images: `out` holds {out.nbytes} bytes, the rows need {self.m * D * 8}")
+            res, op = out, out.ptr
+            flags |= SF_OUT_DEVICE
+            if return_counts:
+                cd = self.engine.empty((self.m,), np.int32)
+                cp = cd.ptr
+        try:
+            _ffi.check(self.engine.lib.sf_spin_images(self.engine.h, self.cloud.h, self.h, ap, W, int(bool(signed_beta)), int(use_cos),
+                                                      mc, int(bool(normalize)), int(min_neighborhood_size), op,
+                                                      cp if return_counts else None, flags), "sf_spin_images")
+            if cd is not None:
+                counts = cd.to_host()
+        finally:
+            if cd is not None:
+                cd.free()
+        return (res, counts) if return_counts else res
+
     def shot_from_moments(self, moments: DeviceArray, first_row: int, normalize: bool, min_neighborhood_size: int,
                           out: DeviceArray, lrf_out: Optional[DeviceArray] = None) -> DeviceArray:
         """shot_single_scale from frame moments Spfh.compute(..., moments_out=) left for these lists; `first_row` = row

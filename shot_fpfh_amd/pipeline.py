@@ -17,7 +17,13 @@ import numpy.typing as npt
 
 from . import keypoint_selection as _ks
 from .core import RigidTransform
-from .descriptors import ShotMultiprocessor, compute_fpfh_descriptor, compute_pfh_descriptor, compute_usc_descriptor
+from .descriptors import (
+    ShotMultiprocessor,
+    compute_fpfh_descriptor,
+    compute_pfh_descriptor,
+    compute_spin_image_descriptor,
+    compute_usc_descriptor,
+)
 from .helpers import write_ply
 from .icp import icp_generalized, icp_point_to_plane, icp_point_to_point, icp_robust, icp_symmetric, icp_trimmed, nearest_within
 from .matching import (
@@ -206,10 +212,27 @@ class RegistrationPipeline:
             return compute_pfh_descriptor(kp, points, normals, radius, n_bins)
         self._fill("descriptors", force_recompute, make)
 
+    def compute_spin_image_descriptor(self, radius: float, image_width: int = 8, signed: bool = False, *,
+                                      min_cos: float | None = None, normalize: bool = False, min_neighborhood_size: int = 0,
+                                      force_recompute: bool = False) -> None:
+        """Spin images (`compute_spin_image_descriptor`, K24; not in the reference) of both clouds' keypoints about their own
+        normals.  The default here is the UNSIGNED image (signed=False, rows of (W + 1)^2), because a pipeline's normals usually
+        come from compute_normals, whose sign is arbitrary; the function's own default is PCL's signed image, for consistently
+        oriented normals.  min_cos, normalize and min_neighborhood_size reach the descriptor through this method only:
+        compute_descriptors(descriptor_choice="spin") passes the radius, spin_width and spin_signed and leaves these three at
+        their defaults here (its own normalize and min_neighborhood_size are SHOT's, with SHOT's defaults, as for "usc" and "pfh")."""
+        logging.info("-- Computing spin image descriptors --")
+
+        def make(side):
+            points, normals, kp = self._cloud(side)
+            return compute_spin_image_descriptor(kp, points, normals, radius, image_width, signed_beta=signed, min_cos=min_cos,
+                                                 normalize=normalize, min_neighborhood_size=min_neighborhood_size)
+        self._fill("descriptors", force_recompute, make)
+
     def compute_descriptors(
         self,
         radius: float,
-        descriptor_choice: Literal["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc", "pfh"] = "shot_single_scale",
+        descriptor_choice: Literal["fpfh", "shot_single_scale", "shot_bi_scale", "shot_multiscale", "usc", "pfh", "spin"] = "shot_single_scale",
         fpfh_n_bins: int = 5,
         phi: float = 3.0,
         rho: float = 10.0,
@@ -224,6 +247,8 @@ class RegistrationPipeline:
         force_recompute: bool = False,
         *,
         pfh_n_bins: int = 5,
+        spin_width: int = 8,
+        spin_signed: bool = False,
     ) -> None:
         shot_config = dict(normalize=normalize, share_local_rfs=share_local_rfs, min_neighborhood_size=min_neighborhood_size,
                            n_procs=n_procs, disable_progress_bar=disable_progress_bars, verbose=verbose)
@@ -248,6 +273,8 @@ class RegistrationPipeline:
             self.compute_usc_descriptor(radius, force_recompute=force_recompute)
         elif descriptor_choice == "pfh":
             self.compute_pfh_descriptor(radius, n_bins=pfh_n_bins, force_recompute=force_recompute)
+        elif descriptor_choice == "spin":  # (unsigned by default; normalize / min_neighborhood_size above are SHOT's and not passed on)
+            self.compute_spin_image_descriptor(radius, image_width=spin_width, signed=spin_signed, force_recompute=force_recompute)
         else:
             raise ValueError("Incorrect descriptor choice")
 
